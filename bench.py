@@ -146,6 +146,44 @@ def algorithmic_bytes(xsize, ysize, coeff_bytes):
     return wp * hp * 3 * coeff_bytes + (wp * hp // 64) * 18 + xsize * ysize * 12
 
 
+DUMP_BUDGET_BYTES = 48 << 20  # row samples; the per-array statistics and row indices add a few kB (cap: 64 MB)
+DUMP_SEED = 0x4A584C
+
+
+def dump_outputs(directory, arrays):
+    """`--dump-outputs DIR`: what the timed path computed in its last step, so that two builds can be compared output for
+    output.  Per array `name` (a tensor on the device, any dtype): DIR/name.npy = the whole array in float32 when it fits
+    the budget, else a fixed seeded sample of whole rows in float32, with DIR/name_rows.npy = the indices of those rows
+    (float64).  A row = the trailing axes merged until it holds at least 1024 elements: one image row of an [H, W, C] or
+    a [C, H, W] frame.  DIR/name_stats.npy = float64 [sum, sum of squares, min, max, number of elements] of the WHOLE
+    array, so that no sample hides a difference elsewhere."""
+    import numpy as np
+    import torch
+    os.makedirs(directory, exist_ok=True)
+    share = DUMP_BUDGET_BYTES // max(1, len(arrays))
+    for name, a in arrays.items():
+        a = a.detach()
+        dt = torch.float64 if a.dtype == torch.float64 else torch.float32
+        row_len, axis = 1, a.dim()
+        while axis > 0 and row_len < 1024:
+            axis -= 1
+            row_len *= a.shape[axis]
+        rows = a.reshape(-1, max(1, row_len))
+        n_rows, row_bytes = rows.shape[0], rows.shape[1] * (8 if dt == torch.float64 else 4)
+        if n_rows * row_bytes <= share:
+            np.save(os.path.join(directory, name + ".npy"), a.to(dt).cpu().numpy())
+        else:
+            k = max(1, share // row_bytes)
+            pick = np.sort(np.random.default_rng(DUMP_SEED).choice(n_rows, size=k, replace=False))
+            idx = torch.from_numpy(pick).to(a.device)
+            np.save(os.path.join(directory, name + ".npy"), rows.index_select(0, idx).to(dt).cpu().numpy())
+            np.save(os.path.join(directory, name + "_rows.npy"), pick.astype(np.float64))
+        w = a.to(torch.float64)
+        stats = [w.sum().item(), (w * w).sum().item(), w.min().item(), w.max().item(), float(a.numel())]
+        np.save(os.path.join(directory, name + "_stats.npy"), np.array(stats, np.float64))
+        del w
+
+
 def resolve_mix(name):
     from libjxl_amd import synth
     named = {"d1": synth.MIX_D1, "dct8": synth.MIX_DCT8, "dct32": synth.MIX_DCT32, "all": synth.MIX_ALL}
@@ -604,6 +642,8 @@ def single_process_multi(args, torch):
     sync()
     dt = time.perf_counter() - t0
     clk = clocks.stop()
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, {"frame": full})
     host_frame = None
     try:  # every stripe through its own device's PCIe link into a host frame (jxlhip_decode_frame_host)
         import numpy as np
@@ -681,6 +721,9 @@ def main():
     ap.add_argument("--calib-copy", action="store_true",
                     help="run one known-size (1 GiB) device copy so PMC passes can be calibrated")
     ap.add_argument("--cpu-sample", type=int, nargs=2, default=None)
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed (the decoded frame; a fixed, "
+                         "seeded row sample when it is larger than the budget) as DIR/<name>.npy: see dump_outputs()")
     args = ap.parse_args()
 
     import torch
@@ -854,6 +897,13 @@ def main():
     note("set-up done; timed steps")
     dt = timed(step_one if world == 1 else step, tag="value")
     note("timed steps done")
+    if args.dump_outputs:  # (before any side measurement reuses the buffers)
+        if world == 1:
+            dump_outputs(args.dump_outputs, {"frame": out})
+        elif gather and rank == 0:
+            dump_outputs(args.dump_outputs, {"frame": full})
+        elif not gather:
+            dump_outputs(args.dump_outputs, {f"stripe_rank{rank}": out})
     # N > 1: what arrived on rank 0 is the frame one GPU decodes (checked once, untimed: a whole-frame context on rank 0's
     # device; the stripes' two-phase / fused kernels and the whole frame's are held bit-identical by the test suite)
     gathered_equals_one_gpu = gathered_checksum = one_gpu_checksum = None

@@ -68,7 +68,10 @@ def outputs():
 def build(verbose=False):
     if not B.available():
         if all(os.path.exists(o) for o in outputs()):
-            return outputs()[:2]  # prebuilt, travelled with the snapshot
+            # prebuilt, travelled with the snapshot (from another directory: an older build named its libraries by path)
+            B.relocate_prebuilt(outputs() + [os.path.join(B.OUT, n) for n in
+                                             ("libjxl_dec_ref.so", "libjxl_dec_hip.so", "libjxl_dec_ref_v8.so")])
+            return outputs()[:2]
         raise RuntimeError("reference tree not present and no prebuilt djxl")
     dec_ref, dec_hip = S.build()
     os.makedirs(OBJ, exist_ok=True)
@@ -96,17 +99,19 @@ def build(verbose=False):
         r = subprocess.run(cmd, capture_output=True, text=True)
         if r.returncode:
             raise RuntimeError("link failed: %s\n%s" % (" ".join(cmd[:6]), r.stderr[-6000:]))
-    link([B.CXX, "-shared", "-fPIC", "-o", thr_so] + thr_objs + ["-lpthread"])
+    link([B.CXX, "-shared", "-fPIC", "-o", thr_so, "-Wl,-soname," + os.path.basename(thr_so)] + thr_objs + ["-lpthread"])
     libs = []
     if lcms:
         local = os.path.join(B.OUT, "liblcms2.so.2")
         if not os.path.exists(local):
             shutil.copy(LCMS_LIB, local)  # a binary of this image, beside the tools that load it ($ORIGIN)
         libs = [local]
-    rpath = ["-Wl,-rpath,$ORIGIN", "-Wl,-rpath,$ORIGIN/../../libjxl_amd/csrc", "-Wl,-rpath," + HIPLIB_DIR]
+    # relocatable: every library is recorded by its bare name and looked up relative to the tool (oracle/_ref/ travels to
+    # other machines and directories); -rpath-link only lets the linker find libjxl_hip.so behind libjxl_dec_hip.so here
+    rpath = ["-Wl,-rpath,$ORIGIN", "-Wl,-rpath,$ORIGIN/../../libjxl_amd/csrc", "-Wl,-rpath-link," + HIPLIB_DIR]
     link([B.CXX, "-o", os.path.join(B.OUT, "djxl_ref")] + tool_objs + [dec_ref, thr_so] + libs + ["-lpthread", "-lm"] + rpath)
     link([B.CXX, "-o", os.path.join(B.OUT, "djxl_hip")] + tool_objs +
-         [dec_hip, os.path.join(HIPLIB_DIR, "libjxl_threads_hip.so")] + libs + ["-lpthread", "-lm"] + rpath)
+         [dec_hip, "-L" + HIPLIB_DIR, "-l:libjxl_threads_hip.so"] + libs + ["-lpthread", "-lm"] + rpath)
     # djxl_ref_v8: the same tool on the decoder whose hot path runs libjxl's 8-lane SIMD code (bench.py's e2e block: the
     # honest CPU partner of djxl_hip; the tests keep the one-lane djxl_ref as their checker)
     dec_ref_v8 = S.build_ref_v8()

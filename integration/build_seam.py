@@ -144,11 +144,14 @@ def build(verbose=False):
     assert len(dec_frame_obj) == 1
     others = [o for o in objs if o != dec_frame_obj[0]]
     link = ["-Wl,--gc-sections", "-Wl,-Bsymbolic", "-Wl,--no-undefined", "-lpthread", "-lm"]
+    # relocatable: a SONAME, so that the tools linked against these libraries record the bare file name (not this
+    # checkout's absolute path), and libjxl_hip.so found relative to the library -- oracle/_ref/ travels to other
+    # machines and directories
     for so, parts, libs in ((ref_so, objs + extra_objs, []),
                             (hip_so, others + extra_objs + [o_patched, o_seam],
-                             ["-L" + HIPLIB_DIR, "-l:libjxl_hip.so", "-Wl,-rpath," + HIPLIB_DIR,
-                              "-Wl,-rpath,$ORIGIN/../../libjxl_amd/csrc"])):
-        r = subprocess.run([B.CXX, "-shared", "-fPIC", "-o", so] + parts + link + libs, capture_output=True, text=True)
+                             ["-L" + HIPLIB_DIR, "-l:libjxl_hip.so", "-Wl,-rpath,$ORIGIN/../../libjxl_amd/csrc"])):
+        r = subprocess.run([B.CXX, "-shared", "-fPIC", "-o", so, "-Wl,-soname," + os.path.basename(so)] + parts + link + libs,
+                           capture_output=True, text=True)
         if r.returncode:
             raise RuntimeError("link %s failed:\n%s" % (so, r.stderr[-6000:]))
     if verbose:
@@ -178,7 +181,8 @@ def build_ref_v8(verbose=False):
         extra_objs.append(o)
     objs = [o for o in objs if not o.endswith("jxl__encode.o")]
     link = ["-Wl,--gc-sections", "-Wl,-Bsymbolic", "-Wl,--no-undefined", "-lpthread", "-lm"]
-    r = subprocess.run([B.CXX, "-shared", "-fPIC", "-o", so] + objs + extra_objs + link, capture_output=True, text=True)
+    r = subprocess.run([B.CXX, "-shared", "-fPIC", "-o", so, "-Wl,-soname," + os.path.basename(so)] + objs + extra_objs + link,
+                       capture_output=True, text=True)
     if r.returncode:
         raise RuntimeError("link %s failed:\n%s" % (so, r.stderr[-6000:]))
     if verbose:

@@ -86,6 +86,58 @@ V8_UNITS = ("jxl/dec_group.cc", "jxl/render_pipeline/stage_gaborish.cc", "jxl/re
             "jxl/simd_util.cc")
 
 
+def relocate_prebuilt(paths):
+    """Prebuilt tools and libraries of oracle/_ref that travelled from another directory: an older build linked its
+    libraries by path (no SONAME), so their DT_NEEDED entries name files under the directory that built them.  Every such
+    entry whose file does not exist here is pointed at the bare file name -- the tail of the same string in .dynstr, so
+    only the entry's offset changes -- and the loader finds the library through the binary's $ORIGIN run paths, as it does
+    for a current build.  Returns the paths it changed."""
+    import struct
+    changed = []
+    for path in paths:
+        if not os.path.isfile(path):
+            continue
+        with open(path, "rb") as f:
+            b = bytearray(f.read())
+        if b[:4] != b"\x7fELF" or b[4] != 2 or b[5] != 1:  # ELF64 little-endian only (what g++ writes here)
+            continue
+        phoff, = struct.unpack_from("<Q", b, 0x20)
+        phentsize, phnum = struct.unpack_from("<HH", b, 0x36)
+        loads, dyn = [], None
+        for i in range(phnum):
+            p_type, _, p_offset, p_vaddr, _, p_filesz = struct.unpack_from("<IIQQQQ", b, phoff + i * phentsize)
+            if p_type == 1:  # PT_LOAD
+                loads.append((p_vaddr, p_offset, p_filesz))
+            elif p_type == 2:  # PT_DYNAMIC
+                dyn = (p_offset, p_filesz)
+        if dyn is None:
+            continue
+        entries = [(dyn[0] + k, *struct.unpack_from("<qQ", b, dyn[0] + k)) for k in range(0, dyn[1], 16)]
+        strtab = next((v for _, tag, v in entries if tag == 5), None)  # DT_STRTAB (a virtual address)
+        seg = [(va, off) for va, off, sz in loads if strtab is not None and va <= strtab < va + sz]
+        if not seg:
+            continue
+        stroff = strtab - seg[0][0] + seg[0][1]
+        dirty = False
+        for at, tag, val in entries:
+            if tag == 0:  # DT_NULL
+                break
+            if tag != 1:  # DT_NEEDED
+                continue
+            name = bytes(b[stroff + val:b.index(b"\0", stroff + val)]).decode()
+            if "/" in name and not os.path.exists(name):
+                struct.pack_into("<Q", b, at + 8, val + len(name) - len(os.path.basename(name)))
+                dirty = True
+        if dirty:
+            tmp = path + ".relocate"
+            with open(tmp, "wb") as f:
+                f.write(b)
+            os.chmod(tmp, os.stat(path).st_mode)
+            os.replace(tmp, path)
+            changed.append(path)
+    return changed
+
+
 def build(verbose=False, only_compile=False, variant=""):
     global FLAGS
     lib = os.path.join(OUT, "libjxl_ref%s.so" % ("_" + variant if variant else ""))

@@ -59,6 +59,7 @@ def build():
         missing = [p for p in out.values() if not os.path.exists(p)]
         if missing:
             raise RuntimeError("reference tree not present and no prebuilt " + missing[0])
+        B.relocate_prebuilt(list(out.values()))  # (built in another directory: see relocate_prebuilt)
         return out
     B.build()               # oracle/_ref/obj: the single-lane objects
     B.build(variant="v8")   # obj_fma + obj_v8
