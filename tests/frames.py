@@ -2,6 +2,7 @@
 import ctypes as C
 
 import numpy as np
+import torch
 
 from libjxl_amd import abi, synth
 
@@ -28,13 +29,202 @@ def make_case(xsize, ysize, dequant=None, **kw):
     params, t = synth.synth_frame(xsize, ysize, device="cpu", **kw)
     if dequant is None:
         dequant = oracle.default_dequant_tables()
+    return params, t, oracle_frame(params, t, dequant)
+
+
+def oracle_frame(params, t, dequant):
+    """oracle.Frame over CPU tensors t (dequant: the oracle's or the reference's own tables)."""
+    import oracle
     npy = dict(
         coeffs=[c.numpy() for c in t["coeffs"]],
         ac_strategy=t["ac_strategy"].numpy(), raw_quant=t["raw_quant"].numpy(),
         epf_sharpness=t["epf_sharpness"].numpy(), ytox_map=t["ytox_map"].numpy(),
         ytob_map=t["ytob_map"].numpy(), dc=[d.numpy() for d in t["dc"]])
-    fr = oracle.Frame(to_oracle_params(abi.make_params(params)), npy["coeffs"],
-                      npy["ac_strategy"], npy["raw_quant"], npy["epf_sharpness"],
-                      npy["ytox_map"], npy["ytob_map"], npy["dc"], dequant)
-    return params, t, fr
+    return oracle.Frame(to_oracle_params(abi.make_params(params)), npy["coeffs"],
+                        npy["ac_strategy"], npy["raw_quant"], npy["epf_sharpness"],
+                        npy["ytox_map"], npy["ytob_map"], npy["dc"], dequant)
 
+
+# ---- off-default frame parameters and side info ------------------------------
+# synth.synth_frame fixes most frame-level inputs (global_scale, quant_dc, the qm scales, CfL, opsin, the loop
+# filter fields) and keeps the side info in narrow ranges.  A PARAM_SET names a decoder state away from those
+# defaults; make_param_case applies it before the product inputs and the oracle / reference Frame are built.
+# Each entry of "knobs" is one independent input: a frame-header field (a params key, or intensity_target /
+# opsin_matrix, which together give inverse_opsin_matrix) or a side-info edit (cfl_map, quant_field, coeffs: see
+# _side_edit).  The stage list (gab, epf) is one where every knob of the set matters.
+F32 = np.float32
+K_MIN_SIGMA = F32(-3.90524291751269967465540850526868)  # epf.h:22
+K_INV_SIGMA_NUM = F32(-1.1715728752538099024)          # epf.h:18
+
+
+def qm_multiplier(qm_scale):
+    """x_dm_multiplier / b_dm_multiplier of a frame header's x_qm_scale / b_qm_scale: 0.8 ** (scale - 2) in f32."""
+    return float(F32(0.8 ** (qm_scale - 2)))
+
+
+def _unit_inverse_opsin():
+    p, _ = synth.synth_frame(8, 8, mix=synth.MIX_DCT8, intensity_target=255.0)
+    return [F32(v) for v in p["inverse_opsin_matrix"]]
+
+
+# every entry moved by its own relative amount (a colour-managed file's matrix is not the default one)
+OPSIN_MATRIX_PERTURB = [0.031, -0.024, 0.17, 0.043, -0.036, -0.21, 0.027, 0.052, -0.019]
+
+LF_FIELDS = dict(gab_weights=[0.135, 0.038, 0.095, 0.072, 0.128, 0.061],
+                 epf_channel_scale=[25.0, 9.0, 2.0], epf_quant_mul=0.7, epf_pass0_sigma_scale=1.3,
+                 epf_pass2_sigma_scale=4.0, epf_border_sad_mul=0.35,
+                 epf_sharp_lut=[0.0, 0.2, 0.35, 0.5, 0.65, 0.8, 0.9, 1.2])
+
+
+def _lf_set(gab, epf, seed):
+    names = ["epf_sharp_lut", "epf_channel_scale", "epf_quant_mul", "epf_border_sad_mul"]
+    names += ["gab_weights"] if gab else []
+    names += ["epf_pass2_sigma_scale"] if epf >= 2 else []  # EPF2 runs from two iterations on, EPF0 at three
+    names += ["epf_pass0_sigma_scale"] if epf == 3 else []
+    return dict(gab=gab, epf=epf, seed=seed, knobs={k: LF_FIELDS[k] for k in names})
+
+
+PARAM_SETS = {
+    "quant_hi": dict(gab=True, epf=1, seed=101, knobs=dict(
+        global_scale=9000, x_dm_multiplier=qm_multiplier(5), b_dm_multiplier=qm_multiplier(4), quant_dc=40)),
+    "quant_lo": dict(gab=False, epf=2, seed=102, knobs=dict(
+        global_scale=1200, x_dm_multiplier=qm_multiplier(5), b_dm_multiplier=qm_multiplier(4), quant_dc=40)),
+    "cfl": dict(gab=True, epf=1, seed=103, knobs=dict(
+        cfl_base_x=0.05, cfl_base_b=0.85, cfl_color_factor=100, cfl_map="full_int8")),
+    "opsin": dict(gab=False, epf=0, seed=104, knobs=dict(
+        opsin_biases=[-0.0037930732552754493, -0.0051, -0.0024], opsin_matrix=OPSIN_MATRIX_PERTURB,
+        intensity_target=1000.0)),
+    "lf_g1": _lf_set(True, 1, 105),
+    "lf_1": _lf_set(False, 1, 106),
+    "lf_g2": _lf_set(True, 2, 107),
+    "lf_2": _lf_set(False, 2, 108),
+    "lf_g3": _lf_set(True, 3, 109),
+    "lf_3": _lf_set(False, 3, 110),
+    "qfield_1": dict(gab=True, epf=1, seed=111, knobs=dict(quant_field="extremes", epf_sharp_lut="min_sigma")),
+    "qfield_3": dict(gab=True, epf=3, seed=112, knobs=dict(quant_field="extremes", epf_sharp_lut="min_sigma")),
+    "coeff_i16": dict(gab=True, epf=2, seed=113, knobs=dict(coeffs="i16_extremes")),
+    "coeff_i32": dict(gab=False, epf=0, seed=114, coeff_type=1, knobs=dict(coeffs="i32_beyond_2_24")),
+}
+# the frame-header fields that change the DC dequantisation (jxlhip_dequant_dc) but not the AC path
+DC_ONLY_KNOBS = ("quant_dc",)
+
+# sigma-boundary search: three (raw_quant, sharpness) pairs of the quant field's middle band whose LUT entries put
+# inv_sigma on kMinSigma and on the nearest values either side of it that 1 / sigma can take.  Near kMinSigma one
+# step of sigma moves 1 / sigma by about two floats, so not every float there is a quotient: the float just below
+# kMinSigma is one (1 / -0.256066), the float just above it is not, and its upper neighbour is two floats away.
+MIN_SIGMA_SHARPNESS = (5, 6, 7)
+
+
+def inv_sigma_f32(global_scale, epf_quant_mul, quant, lut):
+    """ComputeSigma (epf.cc:69-79, kernels_blocks.hip) in float32 for one cell."""
+    qs = F32(global_scale * (1.0 / 65536))
+    sigma_quant = F32(epf_quant_mul) / (qs * F32(quant) * K_INV_SIGMA_NUM)
+    sigma = np.minimum(sigma_quant * F32(lut), F32(-1e-4))
+    return F32(1.0) / sigma
+
+
+def _sigmas_near_min():
+    s0 = F32(1.0 / float(K_MIN_SIGMA))
+    sig = (s0.view(np.int32) + np.arange(-8, 9, dtype=np.int32)).view(np.float32)
+    return sig, F32(1.0) / sig
+
+
+def min_sigma_targets():
+    """[below, kMinSigma, above]: the quotients 1 / sigma nearest kMinSigma on either side, and kMinSigma."""
+    _, inv = _sigmas_near_min()
+    return [inv[inv < K_MIN_SIGMA].max(), K_MIN_SIGMA, inv[inv > K_MIN_SIGMA].min()]
+
+
+def min_sigma_cells(global_scale, epf_quant_mul):
+    """[(raw_quant, LUT value)] for the three targets: the largest raw_quant with a LUT value in [0.5, 1] for which
+    sigma is the target's sigma exactly, and of its LUT values the one nearest the ideal value."""
+    sig, inv = _sigmas_near_min()
+    qs = F32(global_scale * (1.0 / 65536))
+    out = []
+    for t in min_sigma_targets():
+        st = sig[inv == t][0]
+        for quant in range(256, 0, -1):
+            sigma_quant = F32(epf_quant_mul) / (qs * F32(quant) * K_INV_SIGMA_NUM)
+            ideal = F32(float(st) / float(sigma_quant))
+            if not 0.5 <= ideal <= 1.0:
+                continue
+            cand = (ideal.view(np.int32) + np.arange(-64, 65, dtype=np.int32)).view(np.float32)
+            hit = cand[inv_sigma_f32(global_scale, epf_quant_mul, quant, cand) == t]
+            if len(hit):
+                out.append((quant, float(hit[np.argmin(np.abs(hit - ideal))])))
+                break
+        else:
+            raise AssertionError("no (raw_quant, sharpness LUT value) gives inv_sigma %r" % t)
+    return out
+
+
+def _side_edit(kind, params, t, rng):
+    ysb, xsb = t["raw_quant"].shape
+    if kind == "full_int8":  # ytox / ytob over the whole int8 range, both ends present
+        for k in ("ytox_map", "ytob_map"):
+            m = rng.integers(-128, 128, size=t[k].shape).astype(np.int8)
+            m.flat[0], m.flat[-1] = -128, 127
+            if m.size > 2:
+                m.flat[1], m.flat[-2] = 127, -128
+            t[k] = torch.from_numpy(m)
+    elif kind == "extremes":  # raw_quant 1 and 256 under every sharpness value; the kMinSigma band
+        q = t["raw_quant"].numpy().copy()
+        sh = t["epf_sharpness"].numpy().copy()
+        yy, xx = np.mgrid[0:ysb, 0:xsb]
+        top = yy < max(1, ysb // 3)
+        q[top] = np.where((xx[top] // 2) % 2 == 0, 1, 256)
+        sh[top] = ((xx[top] + yy[top]) % 8).astype(np.uint8)
+        band = (yy >= ysb // 3) & (yy < 2 * ysb // 3)
+        cells = min_sigma_cells(params["global_scale"], params["epf_quant_mul"])
+        q[band] = np.array([qv for qv, _ in cells], np.int32)[xx[band] % 3]
+        sh[band] = np.array(MIN_SIGMA_SHARPNESS, np.uint8)[xx[band] % 3]
+        t["raw_quant"], t["epf_sharpness"] = torch.from_numpy(q), torch.from_numpy(sh)
+    elif kind in ("i16_extremes", "i32_beyond_2_24"):
+        vals = ([32767, -32768] if kind == "i16_extremes" else
+                [(1 << 24) + 1, -((1 << 24) + 1), (1 << 24) + 3, -((1 << 25) + 1)])
+        for c in range(3):
+            a = t["coeffs"][c].numpy().copy()
+            nz = np.flatnonzero(a)  # non-zero slots are never LLF slots (they hold 0 in the stream)
+            pick = rng.choice(nz, size=min(len(nz), 24), replace=False)
+            a[pick] = np.resize(np.array(vals, np.int64), len(pick)).astype(a.dtype)
+            t["coeffs"][c] = torch.from_numpy(a)
+    else:
+        raise KeyError(kind)
+
+
+def make_param_case(xsize, ysize, name, revert=(), dequant=None, mix=None, gab=None, epf_iters=None, **kw):
+    """make_case at PARAM_SETS[name]: returns (params_dict, torch tensors on CPU, oracle.Frame).  `revert`: knobs
+    of the set left at synth's defaults (the teeth checks).  gab / epf_iters default to the set's stage list.  A
+    tuple of names applies all their knobs (the first set gives the stage list and the seed)."""
+    import oracle
+    names = (name,) if isinstance(name, str) else tuple(name)
+    s = dict(PARAM_SETS[names[0]], knobs={k: v for n in names for k, v in PARAM_SETS[n]["knobs"].items()})
+    gab = s["gab"] if gab is None else gab
+    epf_iters = s["epf"] if epf_iters is None else epf_iters
+    kw.setdefault("coeff_type", s.get("coeff_type", 0))
+    kw.setdefault("seed", s["seed"])
+    it = kw.pop("intensity_target", 255.0)
+    params, t = synth.synth_frame(xsize, ysize, device="cpu", mix=synth.MIX_ALL if mix is None else mix, gab=gab,
+                                  epf_iters=epf_iters, intensity_target=it, **kw)
+    knobs = {k: v for k, v in s["knobs"].items() if k not in revert}
+    rng = np.random.default_rng(s["seed"])
+    derived = ("cfl_map", "quant_field", "coeffs", "opsin_matrix", "intensity_target")
+    for k, v in knobs.items():  # the header fields first: the kMinSigma cells depend on them
+        if k not in derived and not (k == "epf_sharp_lut" and v == "min_sigma"):
+            params[k] = v
+    if knobs.get("epf_sharp_lut") == "min_sigma":
+        lut = list(params["epf_sharp_lut"])
+        for sv, (_, x) in zip(MIN_SIGMA_SHARPNESS, min_sigma_cells(params["global_scale"], params["epf_quant_mul"])):
+            lut[sv] = x
+        params["epf_sharp_lut"] = lut
+    for k in sorted(set(knobs) & {"cfl_map", "quant_field", "coeffs"}):  # (sorted: one generator for all edits)
+        _side_edit(knobs[k], params, t, rng)
+    if "opsin_matrix" in knobs or "intensity_target" in knobs:
+        m = _unit_inverse_opsin()
+        if "opsin_matrix" in knobs:
+            m = [F32(v * F32(1.0 + d)) for v, d in zip(m, knobs["opsin_matrix"])]
+        mul = F32(255.0) / F32(knobs.get("intensity_target", it))
+        params["inverse_opsin_matrix"] = [float(F32(v * mul)) for v in m]
+    if dequant is None:
+        dequant = oracle.default_dequant_tables()
+    return params, t, oracle_frame(params, t, dequant)
