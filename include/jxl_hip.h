@@ -269,6 +269,25 @@ JXLHIP_EXPORT int jxlhip_upload_side_info(
  * (stage_write.cc:350-366); not un-premultiplied.  Without this call (jxlhip_frame_begin resets it) alpha is the
  * opaque 1.0 the reference substitutes (:355-360).  On a multi-device context every stripe takes its own rows. */
 JXLHIP_EXPORT int jxlhip_set_alpha(jxlhip_ctx* ctx, const float* host_plane, size_t stride_floats);
+/* Photon noise of the current frame (FrameHeader::kNoise, what cjxl --photon_noise_iso writes): lut = NoiseParams::lut,
+ * the 8 values DecodeNoise reads (lib/jxl/dec_noise.cc:155-165; jxlhip_noise_lut_decode), and the seed indices of
+ * the frame's generators, PassesDecoderState::visible_frame_index / nonvisible_frame_index (dec_cache.h:127-128) as
+ * FrameDecoder sets them BEFORE decoding the frame (dec_frame.cc:160-168): a file's only frame is (1, 0).
+ * jxlhip_decode_frame then renders what the reference's pipeline does between the loop filters and the XYB stage
+ * (dec_cache.cc:205-210): the random planes of PrepareNoiseInput (dec_noise.cc:58-151), ConvolveNoiseStage and
+ * AddNoiseStage (render_pipeline/stage_noise.cc:171-310) with the frame's base colour correlation (cfl_base_x /
+ * cfl_base_b); every output kind.  A LUT with no entry above 1e-3 adds nothing (noise.h:37-42): the frame then takes
+ * exactly the noise-free path.  jxlhip_frame_begin resets it (no noise); frames that never call this are untouched.
+ * JXLHIP_ERR_UNSUPPORTED on a multi-device context, for a stripe and with undo_orientation > 1; the split calls
+ * (jxlhip_decode_filters[_rows], jxlhip_stripe_finish) refuse a noise frame. */
+JXLHIP_EXPORT int jxlhip_set_noise(jxlhip_ctx* ctx, const float lut[8], uint32_t visible_frame_index,
+                                   uint32_t nonvisible_frame_index);
+/* Host-side check of the noise generator's jump: the state (s0_[i], s1_[i]) of the 8 lanes of
+ * Xorshift128Plus(visible_frame_index, nonvisible_frame_index, x0, y0) (lib/jxl/xorshift128plus-inl.h:46-57) after
+ * `fills` calls of Fill, computed as the kernel does (one jump-matrix product, then single steps) into state[2 * i],
+ * state[2 * i + 1].  No device needed. */
+JXLHIP_EXPORT int jxlhip_noise_rng_state(uint32_t visible_frame_index, uint32_t nonvisible_frame_index, uint32_t x0,
+                                         uint32_t y0, uint64_t fills, uint64_t state[16]);
 /* A pinned host plane of the current frame's size, owned by the context, for the caller to fill and hand to
  * jxlhip_set_alpha (the copy is then a true asynchronous DMA).  Valid until the next jxlhip_frame_begin of a larger
  * frame or jxlhip_destroy; the previous frame must have been synchronised before it is written again. */
@@ -387,6 +406,7 @@ enum {
                                  jxlhip_decode_frame); a frame has a FILTERS or a FUSED span, never both */
   JXLHIP_KERNEL_EPF0 = 4,     /* epf_iters == 3: [Gaborish] + EPF0 into the second plane set (k_epf0); the EPF1 +
                                  EPF2 + output march that follows is the FILTERS span */
+  JXLHIP_KERNEL_NOISE = 5,    /* photon noise (jxlhip_set_noise): k_noise_rng + k_noise_emit behind the frame's path */
   JXLHIP_KERNEL_COUNT = 8
 };
 /* A hint, not a contract: `frames_in_flight` = how many contexts the caller keeps busy on this device at the same time

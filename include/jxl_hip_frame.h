@@ -207,7 +207,8 @@ JXLHIP_EXPORT int jxlhip_frame_header_decode(const uint8_t* data, size_t size, s
  * (quant_weights.cc:513-528), Quantizer::Decode (quantizer.cc:125-149), DecodeBlockCtxMap
  * (entropy_coder.cc:25-61), ColorCorrelation::DecodeDC (chroma_from_luma.cc:24-44) -- the values
  * jxlhip_frame_params, jxlhip_dequant_dc and the AC decoder take.  frame_flags: the frame header's
- * flags; JXLHIP_ERR_UNSUPPORTED when patches, splines or noise precede these fields in the section. */
+ * flags; JXLHIP_ERR_UNSUPPORTED when patches or splines precede these fields in the section.  With
+ * JXLHIP_FLAG_NOISE the 8 noise LUT points in front of them are skipped (jxlhip_noise_lut_decode returns them). */
 typedef struct jxlhip_dc_global {
   float dc_quant[3];          /* DequantMatrices::DCQuant(c); default 1/4096, 1/512, 1/256 */
   int32_t global_scale;       /* Quantizer::global_scale_ */
@@ -219,6 +220,12 @@ typedef struct jxlhip_dc_global {
 } jxlhip_dc_global;
 JXLHIP_EXPORT int jxlhip_dc_global_decode(const uint8_t* data, size_t size, size_t* bit_pos, uint64_t frame_flags,
                                           jxlhip_dc_global* out);
+/* DecodeNoise (lib/jxl/dec_noise.cc:155-165): NoiseParams::lut, the 8 points of 10 bits (k / 1024 each) at bit *bit_pos
+ * of data -- the start of the DC-global section of a frame with JXLHIP_FLAG_NOISE (read there at
+ * dec_frame.cc:294-296, in front of what jxlhip_dc_global_decode reads from the same position).  *bit_pos advances by
+ * 80; JXLHIP_ERR_BAD_STREAM on truncation.  The values go to jxlhip_set_noise.  (A function of its own rather than a
+ * member of jxlhip_dc_global: callers allocate that struct, and compiled callers keep working with this library.) */
+JXLHIP_EXPORT int jxlhip_noise_lut_decode(const uint8_t* data, size_t size, size_t* bit_pos, float lut[8]);
 
 /* ---- The Modular-coded parts of a VarDCT frame: global MA tree and the DC groups ----
  * Replaces (libjxl tree, lib/jxl/): ModularFrameDecoder::DecodeGlobalInfo (dec_modular.cc:207-316),

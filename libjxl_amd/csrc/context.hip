@@ -164,6 +164,14 @@ struct jxlhip_ctx {
   void* alpha_host = nullptr;  // jxlhip_alpha_staging: pinned plane the caller fills
   size_t alpha_host_items = 0;
   int32_t* qdc_dev = nullptr;  // jxlhip_decode_codestream: the quantized DC planes on their way to jxlhip_dequant_dc_groups
+  // jxlhip_set_noise: photon noise of the current frame (frame_begin resets noise_on); noise_buf = the filtered frame as
+  // planar XYB + the random planes (kernels_noise.hip), noise_jump = the generator's jump matrices (uploaded once)
+  bool noise_on = false;
+  float noise_lut[8] = {0};
+  uint32_t noise_visible = 0, noise_nonvisible = 0;
+  float* noise_buf = nullptr;
+  size_t noise_floats = 0;
+  uint32_t* noise_jump = nullptr;
   size_t qdc_dev_items = 0;
   // transform-kernel fan-out (JXLHIP_BLOCK_STREAMS: 3 = one stream per family; default 1 = back to back on the
   // main stream, measured 15 % faster than letting the families compete for the CUs)
@@ -464,7 +472,7 @@ void jxlhip_destroy(jxlhip_ctx* c) {
                   c->error_flag, c->tables, c->up_coeffs[0], c->up_side,
                   c->dc_tmp,     c->quant_enc,  c->dc_prec,      c->cell_info,
                   c->qdc_dev,    c->host_frame_dev, c->planes2, c->orient_dev,
-                  c->alpha_dev};
+                  c->alpha_dev,  c->noise_buf,  c->noise_jump};
   for (void* b : bufs)
     if (b) (void)hipFree(b);
   if (c->own_stream) (void)hipStreamDestroy(c->own_stream);
@@ -668,6 +676,7 @@ int jxlhip_frame_begin(jxlhip_ctx* c, const jxlhip_frame_params* p) {
   c->have_frame = true;
   c->have_inputs = false;
   c->blocks_done = false;
+  c->noise_on = false;
   return JXLHIP_OK;
 }
 
@@ -819,6 +828,43 @@ int jxlhip_set_alpha(jxlhip_ctx* c, const float* host_plane, size_t stride_float
                              w * sizeof(float), rows, hipMemcpyHostToDevice, c->stream));
   c->fp.alpha = c->alpha_dev - y0 * w;
   c->fp.alpha_stride = (uint32_t)w;
+  return JXLHIP_OK;
+}
+
+// Photon noise of the current frame (FrameHeader::kNoise): NoiseParams::lut and the seed indices of
+// PassesDecoderState; frame_begin resets to "no noise".  A LUT without an entry above 1e-3 is recorded as no noise,
+// as AddNoiseStage skips it (noise.h:37-42).
+int jxlhip_set_noise(jxlhip_ctx* c, const float lut[8], uint32_t visible_frame_index, uint32_t nonvisible_frame_index) {
+  if (!c || !lut) return JXLHIP_ERR_INVALID_ARGUMENT;
+  if (!c->children.empty()) return Fail(c, JXLHIP_ERR_UNSUPPORTED, "noise on a multi-device context");
+  if (!c->have_frame) return Fail(c, JXLHIP_ERR_STATE, "set_noise before frame_begin");
+  if (c->f.group_y0 != 0 || c->f.group_rows != c->f.ysg) return Fail(c, JXLHIP_ERR_UNSUPPORTED, "noise with stripes");
+  if (c->p.undo_orientation > 1) return Fail(c, JXLHIP_ERR_UNSUPPORTED, "noise with undo_orientation %u", c->p.undo_orientation);
+  bool any = false;
+  for (int i = 0; i < 8; i++) any = any || fabsf(lut[i]) > 1e-3f;
+  c->noise_on = false;
+  if (!any) return JXLHIP_OK;
+  HIPCHK(c, hipSetDevice(c->device));
+  if (!c->noise_jump) {
+    static const std::vector<uint32_t> table = [] {
+      std::vector<uint32_t> t((size_t)kNoiseSegs * kNoiseJumpWords);
+      NoiseJumpTable(t.data());
+      return t;
+    }();
+    HIPCHK(c, hipMalloc((void**)&c->noise_jump, table.size() * sizeof(uint32_t)));
+    HIPCHK(c, hipMemcpyAsync(c->noise_jump, table.data(), table.size() * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
+  }
+  memcpy(c->noise_lut, lut, sizeof(c->noise_lut));
+  c->noise_visible = visible_frame_index;
+  c->noise_nonvisible = nonvisible_frame_index;
+  c->noise_on = true;
+  return JXLHIP_OK;
+}
+
+int jxlhip_noise_rng_state(uint32_t visible_frame_index, uint32_t nonvisible_frame_index, uint32_t x0, uint32_t y0,
+                           uint64_t fills, uint64_t state[16]) {
+  if (!state) return JXLHIP_ERR_INVALID_ARGUMENT;
+  NoiseStateAfter(visible_frame_index, nonvisible_frame_index, x0, y0, fills, state);
   return JXLHIP_OK;
 }
 
@@ -1709,6 +1755,7 @@ int jxlhip_decode_filters_rows(jxlhip_ctx* c, void* out, size_t out_stride, size
   JXLHIP_NO_MULTI(c);
   if (!c->blocks_done) return Fail(c, JXLHIP_ERR_STATE, "decode_filters before decode_blocks");
   if (c->p.undo_orientation > 1) return Fail(c, JXLHIP_ERR_UNSUPPORTED, "undo_orientation with the split calls");
+  if (c->noise_on) return Fail(c, JXLHIP_ERR_UNSUPPORTED, "noise with the split calls (jxlhip_decode_frame takes it)");
   int rc = CheckOutArgs(c, out, out_stride, out_plane_stride);
   if (rc) return rc;
   HIPCHK(c, hipSetDevice(c->device));
@@ -1761,6 +1808,7 @@ int jxlhip_stripe_finish(jxlhip_ctx* c, const float* recv_up, const float* recv_
 // XYB planes in the 256 MB Infinity Cache; measured on MI355X it only loses
 // time, so the default is one band = the whole stripe.
 static int DecodeFrameCoded(jxlhip_ctx* c, void* out, size_t out_stride, size_t out_plane_stride);
+static int DecodeFrameNoise(jxlhip_ctx* c, void* out, size_t out_stride, size_t out_plane_stride);
 
 // bytes of one interleaved output pixel (0: planar XYB)
 static size_t OutPixelBytes(const jxlhip_ctx* c) {
@@ -1774,6 +1822,7 @@ int jxlhip_decode_frame(jxlhip_ctx* c, void* out, size_t out_stride, size_t out_
   if (!c) return JXLHIP_ERR_INVALID_ARGUMENT;
   if (!c->children.empty()) return out ? MultiDecodeFrame(c, out, nullptr, out_stride, out_plane_stride) : JXLHIP_ERR_INVALID_ARGUMENT;
   if (!c->have_frame) return Fail(c, JXLHIP_ERR_STATE, "decode needs frame_begin + inputs");
+  if (c->noise_on) return DecodeFrameNoise(c, out, out_stride, out_plane_stride);
   if (c->p.undo_orientation <= 1) return DecodeFrameCoded(c, out, out_stride, out_plane_stride);
   // undo_orientation: coded orientation into a staging frame, k_orient into the caller's buffer
   const DevFrame& f = c->f;
@@ -1868,6 +1917,52 @@ static int DecodeFrameCoded(jxlhip_ctx* c, void* out, size_t out_stride, size_t 
   }
   c->blocks_done = true;
   return LaunchFiltersRows(c, fp, prev_y0, f.y1);
+}
+
+// A frame with photon noise (jxlhip_set_noise; whole frames, coded orientation): the frame's own path -- fused or
+// two-phase, whatever DecodeFrameCoded picks for it -- writes the filtered frame as planar XYB into context memory,
+// then k_noise_rng + k_noise_emit (kernels_noise.hip) add the noise between the loop filters and the XYB stage, where
+// the reference's pipeline has it (dec_cache.cc:205-210), and write the caller's output.
+static int DecodeFrameNoise(jxlhip_ctx* c, void* out, size_t out_stride, size_t out_plane_stride) {
+  int rc = CheckOutArgs(c, out, out_stride, out_plane_stride);
+  if (rc) return rc;
+  const DevFrame& f = c->f;
+  if (f.group_y0 != 0 || f.group_rows != f.ysg || c->p.undo_orientation > 1)
+    return Fail(c, JXLHIP_ERR_UNSUPPORTED, "noise needs a whole frame in coded orientation");
+  HIPCHK(c, hipSetDevice(c->device));
+  const uint32_t ns = (f.xsize + 63u) & ~63u;
+  const size_t nplane = (size_t)ns * f.ysize;
+  if ((rc = Grow(c, &c->noise_buf, &c->noise_floats, 6 * nplane))) return rc;
+  const uint32_t kind = c->p.output_kind;
+  c->p.output_kind = JXLHIP_OUT_XYB_PLANAR;
+  rc = DecodeFrameCoded(c, c->noise_buf, ns, nplane);
+  c->p.output_kind = kind;
+  if (rc) return rc;
+  NoiseArgs N{};
+  N.xsize = f.xsize;
+  N.ysize = f.ysize;
+  N.xsg = f.xsg;
+  N.ysg = f.ysg;
+  N.visible = c->noise_visible;
+  N.nonvisible = c->noise_nonvisible;
+  memcpy(N.lut, c->noise_lut, sizeof(N.lut));
+  N.ytox = c->p.cfl_base_x;  // ColorCorrelation::YtoXRatio(0) / YtoBRatio(0) (chroma_from_luma.h:51-57)
+  N.ytob = c->p.cfl_base_b;
+  N.xyb = c->noise_buf;
+  N.rnd = c->noise_buf + 3 * nplane;
+  N.ns = ns;
+  N.nplane = nplane;
+  N.jump = c->noise_jump;
+  FilterParams fp = c->fp;
+  fp.out = out;
+  fp.out_stride = out_stride;
+  fp.out_plane_stride = out_plane_stride;
+  ProfBegin(c);
+  if (!LaunchNoise(N, fp, (int)kind, c->stream)) return Fail(c, JXLHIP_ERR_INVALID_ARGUMENT, "noise output kind %u", kind);
+  ProfMark(c, JXLHIP_KERNEL_NOISE);
+  ProfEnd(c);
+  HIPCHK(c, hipGetLastError());
+  return JXLHIP_OK;
 }
 
 // The boundary handing over a HOST buffer (what JxlDecoderSetImageOutBuffer gives libjxl): both phases

@@ -2590,14 +2590,31 @@ int jxlhip_block_ctx_map_decode(const uint8_t* data, size_t size, size_t* bit_po
   return kOk;
 }
 
+// DecodeNoise (dec_noise.cc:155-165): 8 LUT points of 10 bits, k / kNoisePrecision (noise.h:20)
+int jxlhip_noise_lut_decode(const uint8_t* data, size_t size, size_t* bit_pos, float lut[8]) {
+  if (!data || !bit_pos || !lut) return JXLHIP_ERR_INVALID_ARGUMENT;
+  BitReader br(data, size, *bit_pos);
+  float v[8];
+  for (float& x : v) x = (float)br.Read(10) / 1024.0f;
+  if (!br.Healthy()) return kBad;
+  memcpy(lut, v, sizeof(v));
+  *bit_pos = br.BitsConsumed();
+  return kOk;
+}
+
 int jxlhip_dc_global_decode(const uint8_t* data, size_t size, size_t* bit_pos, uint64_t frame_flags,
                             jxlhip_dc_global* out) {
   if (!data || !bit_pos || !out) return JXLHIP_ERR_INVALID_ARGUMENT;
-  if (frame_flags & (JXLHIP_FLAG_PATCHES | JXLHIP_FLAG_SPLINES | JXLHIP_FLAG_NOISE)) return JXLHIP_ERR_UNSUPPORTED;
+  if (frame_flags & (JXLHIP_FLAG_PATCHES | JXLHIP_FLAG_SPLINES)) return JXLHIP_ERR_UNSUPPORTED;
   memset(out, 0, sizeof(*out));
-  size_t pos;
+  size_t pos = *bit_pos;
+  if (frame_flags & JXLHIP_FLAG_NOISE) {  // the noise LUT in front of the fields below: jxlhip_noise_lut_decode reads it
+    float lut[8];
+    const int rc = jxlhip_noise_lut_decode(data, size, &pos, lut);
+    if (rc) return rc;
+  }
   {
-    BitReader br(data, size, *bit_pos);
+    BitReader br(data, size, pos);
     // DequantMatrices::DecodeDC
     out->dc_quant[0] = 1.0f / 4096.0f;
     out->dc_quant[1] = 1.0f / 512.0f;

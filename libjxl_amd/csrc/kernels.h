@@ -100,6 +100,31 @@ bool LaunchFusedEpf0(const DevFrame& f, const FilterParams& p, int gab, float* c
 // generation-filling launch geometries are sized from (256 on a whole MI355X, fewer on a CPX / DPX partition)
 unsigned DeviceCus();
 
+// Photon noise (kernels_noise.hip).  The fill sequence of a group's generator is cut into segments of kNoiseSegFills
+// fills; kNoiseSegs segments cover the longest one (3 planes x 256 rows x 16 fills).
+constexpr uint32_t kNoiseSegFills = 128;
+constexpr uint32_t kNoiseSegs = (3u * 256u * 16u + kNoiseSegFills - 1) / kNoiseSegFills;
+constexpr uint32_t kNoiseJumpWords = 128 * 4;  // one 128x128-bit matrix: 128 columns of 4 words
+struct NoiseArgs {
+  uint32_t xsize, ysize, xsg, ysg;
+  uint32_t visible, nonvisible;  // PassesDecoderState::visible_frame_index / nonvisible_frame_index
+  float lut[8];                  // NoiseParams::lut
+  float ytox, ytob;              // ColorCorrelation::YtoXRatio(0) / YtoBRatio(0)
+  const float* xyb;              // the filtered frame: 3 planes, ns floats per row, nplane floats apart
+  float* rnd;                    // the random planes, same layout
+  uint32_t ns;                   // a multiple of 64
+  size_t nplane;                 // a multiple of 64
+  const uint32_t* jump;          // kNoiseSegs x kNoiseJumpWords (NoiseJumpTable)
+};
+// host: the jump matrices M^(j * kNoiseSegFills) of one Xorshift128+ lane, columns of (s0 lo, s0 hi, s1 lo, s1 hi)
+void NoiseJumpTable(uint32_t* host /* kNoiseSegs * kNoiseJumpWords */);
+// host: the 8 lanes' (s0, s1) of Xorshift128Plus(visible, nonvisible, x0, y0) after `fills` fills, through the same
+// jump matrices the kernel uses
+void NoiseStateAfter(uint32_t visible, uint32_t nonvisible, uint32_t x0, uint32_t y0, uint64_t fills, uint64_t state[16]);
+// k_noise_rng + k_noise_emit: random planes, ConvolveNoise, AddNoise on N.xyb, then the output tail of `output_kind`
+// into p.out (whole frames only); false for a bad output kind
+bool LaunchNoise(const NoiseArgs& N, const FilterParams& p, int output_kind, hipStream_t st);
+
 // block-major plane rows <-> dense row-major staging
 void LaunchZeroU32(uint32_t* p, uint32_t n, hipStream_t st);  // (kernels_tables.hip: a kernel, for captured graphs)
 void LaunchRowsCopy(const DevFrame& f, float* dense, int y_first, int nrows, int ncols,

@@ -126,6 +126,14 @@ class VarDctDecoder:
         _check(self.L, self.ctx, self.L.jxlhip_set_alpha(self.ctx, a.ctypes.data, a.shape[1]), "set_alpha")
         self.sync()  # (the array may go away as soon as this returns)
 
+    def set_noise(self, lut, visible_frame_index=1, nonvisible_frame_index=0):
+        """Photon noise of the current frame (FrameHeader::kNoise): NoiseParams::lut (8 floats) and the generators'
+        seed indices (a file's only frame: 1, 0), jxlhip_set_noise; begin_frame resets to no noise."""
+        vals = [float(v) for v in lut]
+        assert len(vals) == 8, len(vals)
+        _check(self.L, self.ctx, self.L.jxlhip_set_noise(self.ctx, (C.c_float * 8)(*vals), int(visible_frame_index),
+                                                         int(nonvisible_frame_index)), "set_noise")
+
     # -- decode ----------------------------------------------------------------
     def decode_blocks(self):
         _check(self.L, self.ctx, self.L.jxlhip_decode_blocks(self.ctx), "decode_blocks")
