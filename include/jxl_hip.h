@@ -282,6 +282,16 @@ JXLHIP_EXPORT int jxlhip_set_alpha(jxlhip_ctx* ctx, const float* host_plane, siz
  * (jxlhip_decode_filters[_rows], jxlhip_stripe_finish) refuse a noise frame. */
 JXLHIP_EXPORT int jxlhip_set_noise(jxlhip_ctx* ctx, const float lut[8], uint32_t visible_frame_index,
                                    uint32_t nonvisible_frame_index);
+/* Splines of the current frame (FrameHeader::kSplines; jxlhip_splines_decode / jxlhip_splines_from_quantized,
+ * jxl_hip_frame.h): computes the draw list of Splines::InitializeDrawCache (lib/jxl/splines.cc:657-758) for the
+ * frame's size and base colour correlation (cfl_base_x / cfl_base_b) and uploads it into context memory; the object
+ * may be destroyed when this returns.  jxlhip_decode_frame then draws the splines where the reference's pipeline has
+ * its spline stage, between the loop filters and noise (dec_cache.cc:198-201; DrawSegment, splines.cc:82-127), with
+ * every output kind.  NULL or a list without segments: no splines.  jxlhip_frame_begin resets it; frames that never
+ * call this are untouched.  JXLHIP_ERR_BAD_STREAM where the reference's draw cache fails (jxlhip_splines_segments);
+ * JXLHIP_ERR_UNSUPPORTED on a multi-device context, for a stripe and with undo_orientation > 1; the split calls refuse
+ * a spline frame. */
+JXLHIP_EXPORT int jxlhip_set_splines(jxlhip_ctx* ctx, const struct jxlhip_splines* splines);
 /* Host-side check of the noise generator's jump: the state (s0_[i], s1_[i]) of the 8 lanes of
  * Xorshift128Plus(visible_frame_index, nonvisible_frame_index, x0, y0) (lib/jxl/xorshift128plus-inl.h:46-57) after
  * `fills` calls of Fill, computed as the kernel does (one jump-matrix product, then single steps) into state[2 * i],
@@ -407,6 +417,7 @@ enum {
   JXLHIP_KERNEL_EPF0 = 4,     /* epf_iters == 3: [Gaborish] + EPF0 into the second plane set (k_epf0); the EPF1 +
                                  EPF2 + output march that follows is the FILTERS span */
   JXLHIP_KERNEL_NOISE = 5,    /* photon noise (jxlhip_set_noise): k_noise_rng + k_noise_emit behind the frame's path */
+  JXLHIP_KERNEL_SPLINES = 6,  /* splines (jxlhip_set_splines): k_splines behind the frame's path, in front of noise */
   JXLHIP_KERNEL_COUNT = 8
 };
 /* A hint, not a contract: `frames_in_flight` = how many contexts the caller keeps busy on this device at the same time

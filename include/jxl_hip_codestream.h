@@ -16,9 +16,10 @@
  *   the render pipeline                                 dec_cache.cc:117-371 -> jxlhip_decode_frame (device)
  * Taken: any enumerated colour encoding and ICC originals (pixels then linear sRGB, like JxlDecoder without a CMS),
  * grey images, up to four full-resolution integer extra channels (alpha into a 4-channel output, all of them as host
- * planes) incl. the squeeze `cjxl -p` puts on them and palettes without deltas, progressive passes, orientation.
+ * planes) incl. the squeeze `cjxl -p` puts on them and palettes without deltas, progressive passes, orientation,
+ * photon noise and splines (drawn on the device, jxlhip_set_noise / jxlhip_set_splines).
  * Everything this front-end does not decode is refused with JXLHIP_ERR_UNSUPPORTED so that the caller can hand the
- * file to libjxl's CPU decoder: Modular-mode frames, animation / multiple frames, previews, patches / splines / noise,
+ * file to libjxl's CPU decoder: Modular-mode frames, animation / multiple frames, previews, patches,
  * chroma subsampling and YCbCr (JPEG recompression), upsampling, cropped frames, DC frames, RAW dequant tables, RCT /
  * delta palettes in the extra channels' Modular streams.
  */

@@ -208,7 +208,9 @@ JXLHIP_EXPORT int jxlhip_frame_header_decode(const uint8_t* data, size_t size, s
  * (entropy_coder.cc:25-61), ColorCorrelation::DecodeDC (chroma_from_luma.cc:24-44) -- the values
  * jxlhip_frame_params, jxlhip_dequant_dc and the AC decoder take.  frame_flags: the frame header's
  * flags; JXLHIP_ERR_UNSUPPORTED when patches or splines precede these fields in the section.  With
- * JXLHIP_FLAG_NOISE the 8 noise LUT points in front of them are skipped (jxlhip_noise_lut_decode returns them). */
+ * JXLHIP_FLAG_NOISE the 8 noise LUT points in front of them are skipped (jxlhip_noise_lut_decode returns them).
+ * A spline frame's bundle is read with jxlhip_splines_decode; pass the flags without JXLHIP_FLAG_SPLINES and the
+ * position behind the bundle. */
 typedef struct jxlhip_dc_global {
   float dc_quant[3];          /* DequantMatrices::DCQuant(c); default 1/4096, 1/512, 1/256 */
   int32_t global_scale;       /* Quantizer::global_scale_ */
@@ -226,6 +228,48 @@ JXLHIP_EXPORT int jxlhip_dc_global_decode(const uint8_t* data, size_t size, size
  * 80; JXLHIP_ERR_BAD_STREAM on truncation.  The values go to jxlhip_set_noise.  (A function of its own rather than a
  * member of jxlhip_dc_global: callers allocate that struct, and compiled callers keep working with this library.) */
 JXLHIP_EXPORT int jxlhip_noise_lut_decode(const uint8_t* data, size_t size, size_t* bit_pos, float lut[8]);
+
+/* ---- Splines (FrameHeader::kSplines) ----
+ * jxlhip_splines: the quantized splines of one frame (Splines after Splines::Decode, lib/jxl/splines.cc:600-642), an
+ * opaque object.  jxlhip_splines_decode reads the bundle at bit *bit_pos of data -- the start of the DC-global section
+ * of a frame with JXLHIP_FLAG_SPLINES (dec_frame.cc:289-293), in front of the noise LUT and of what
+ * jxlhip_dc_global_decode reads; *bit_pos advances to the end of the bundle.  num_pixels = xsize * ysize of the frame
+ * (the control-point cap min(2^20, num_pixels / 2)).  JXLHIP_ERR_BAD_STREAM on every condition the reference
+ * rejects (too many splines or control points, delta-deltas beyond 2^30, INT_MIN in a DCT value, starting points at or
+ * beyond +-2^23, a bad final ANS state) and on truncation. */
+typedef struct jxlhip_splines jxlhip_splines;
+JXLHIP_EXPORT int jxlhip_splines_decode(const uint8_t* data, size_t size, size_t* bit_pos, uint64_t num_pixels,
+                                        jxlhip_splines** out);
+/* The same object from caller-given quantized splines (what QuantizedSpline::Create writes): spline i starts at
+ * (starts[2i], starts[2i+1]) and has num_deltas[i] control-point delta-deltas, read in order from deltas (x, y pairs,
+ * concatenated over the splines); dcts holds 128 values per spline: 3 x 32 colour DCT (X, Y, B), then 32 sigma DCT.
+ * The decoder's per-value checks apply (JXLHIP_ERR_BAD_STREAM). */
+JXLHIP_EXPORT int jxlhip_splines_from_quantized(uint32_t num_splines, const int32_t* starts, const uint32_t* num_deltas,
+                                                const int32_t* deltas, const int32_t* dcts,
+                                                int32_t quantization_adjustment, jxlhip_splines** out);
+JXLHIP_EXPORT void jxlhip_splines_destroy(jxlhip_splines* s);
+/* Read-out of the quantized splines in the layout jxlhip_splines_from_quantized takes: *num_splines and *num_deltas
+ * (the total over all splines) are always written; each array is filled when it is not NULL and must then hold
+ * 2 * num_splines (starts), num_splines (counts), 2 * num_deltas (deltas) and 128 * num_splines (dcts) values. */
+JXLHIP_EXPORT int jxlhip_splines_quantized(const jxlhip_splines* s, uint32_t* num_splines, size_t* num_deltas,
+                                           int32_t* quantization_adjustment, int32_t* starts, uint32_t* counts,
+                                           int32_t* deltas, int32_t* dcts);
+/* One drawable unit of a spline (SplineSegment, splines.h:95-101) and its row span [y0, y1) (SplineSegmentSpan). */
+typedef struct jxlhip_spline_segment {
+  float center_x, center_y;
+  float inv_sigma;
+  float sigma_over_4_times_intensity;
+  float color[3];
+  float maximum_distance;
+  int32_t y0, y1;
+} jxlhip_spline_segment;
+/* The draw list of Splines::InitializeDrawCache (splines.cc:657-758) for a frame of xsize x ysize with the frame's
+ * base colour correlation y_to_x / y_to_b (ColorCorrelation::YtoXRatio(0) / YtoBRatio(0)): the segments in the order
+ * DrawSegments adds them.  *count = their number; up to `cap` of them are written to out (out may be NULL with cap 0).
+ * JXLHIP_ERR_BAD_STREAM where the reference fails: manhattan-distance or estimated-area limit, a control point at or
+ * beyond +-2^23, identical successive control points. */
+JXLHIP_EXPORT int jxlhip_splines_segments(const jxlhip_splines* s, uint32_t xsize, uint32_t ysize, float y_to_x,
+                                          float y_to_b, jxlhip_spline_segment* out, size_t cap, size_t* count);
 
 /* ---- The Modular-coded parts of a VarDCT frame: global MA tree and the DC groups ----
  * Replaces (libjxl tree, lib/jxl/): ModularFrameDecoder::DecodeGlobalInfo (dec_modular.cc:207-316),

@@ -8,7 +8,7 @@ _SO = os.environ.get("JXLHIP_SO") or os.path.join(_HERE, "csrc", "libjxl_hip.so"
 _RUNNER_SO = os.path.join(_HERE, "csrc", "libjxl_threads_hip.so")
 
 KERNEL_COUNT = 8
-KERNEL_NAMES = ["prepare", "blocks", "filters", "fused", "epf0", "noise", "k6", "k7"]
+KERNEL_NAMES = ["prepare", "blocks", "filters", "fused", "epf0", "noise", "splines", "k7"]
 
 
 class JxlHipError(RuntimeError):
@@ -65,6 +65,13 @@ class DcGlobal(C.Structure):
     _fields_ = [("dc_quant", C.c_float * 3), ("global_scale", C.c_int32), ("quant_dc", C.c_int32),
                 ("cfl_color_factor", C.c_uint32), ("cfl_base_x", C.c_float), ("cfl_base_b", C.c_float),
                 ("ytox_dc", C.c_int32), ("ytob_dc", C.c_int32), ("block_ctx_map", BlockCtxMap)]
+
+
+class SplineSegment(C.Structure):
+    """jxlhip_spline_segment (include/jxl_hip_frame.h)."""
+    _fields_ = [("center_x", C.c_float), ("center_y", C.c_float), ("inv_sigma", C.c_float),
+                ("sigma_over_4_times_intensity", C.c_float), ("color", C.c_float * 3), ("maximum_distance", C.c_float),
+                ("y0", C.c_int32), ("y1", C.c_int32)]
 
 
 class ImageInfo(C.Structure):
@@ -224,7 +231,7 @@ EXPORTS = [
     "jxlhip_dequant_table_offset", "jxlhip_status_string", "jxlhip_create", "jxlhip_create_ex", "jxlhip_create_multi",
     "jxlhip_destroy", "jxlhip_last_error", "jxlhip_debug_reload_env", "jxlhip_set_stream",
     "jxlhip_frame_begin", "jxlhip_frame_set_inputs", "jxlhip_upload_side_info",
-    "jxlhip_submit_group", "jxlhip_set_alpha", "jxlhip_set_noise", "jxlhip_noise_rng_state", "jxlhip_alpha_staging", "jxlhip_decode_blocks", "jxlhip_halo_rows",
+    "jxlhip_submit_group", "jxlhip_set_alpha", "jxlhip_set_noise", "jxlhip_noise_rng_state", "jxlhip_set_splines", "jxlhip_alpha_staging", "jxlhip_decode_blocks", "jxlhip_halo_rows",
     "jxlhip_halo_export", "jxlhip_halo_import", "jxlhip_decode_filters", "jxlhip_decode_filters_rows", "jxlhip_stripe_begin",
     "jxlhip_stripe_finish", "jxlhip_decode_frame",
     "jxlhip_decode_frame_host", "jxlhip_decode_frame_pinned",
@@ -239,7 +246,8 @@ EXPORTS = [
     "jxlhip_dequant_encodings_decode", "jxlhip_ac_global_decode", "jxlhip_ac_group_decode_submit_passes",
     "jxlhip_ac_groups_decode_submit", "jxlhip_ac_groups_decode_submit_ex", "jxlhip_num_toc_entries", "jxlhip_toc_decode", "jxlhip_ac_global_decode_at",
     # include/jxl_hip_frame.h
-    "jxlhip_frame_header_decode", "jxlhip_dc_global_decode", "jxlhip_noise_lut_decode", "jxlhip_image_header_decode", "jxlhip_icc_decode", "jxlhip_output_opsin_matrix",
+    "jxlhip_frame_header_decode", "jxlhip_dc_global_decode", "jxlhip_noise_lut_decode", "jxlhip_splines_decode",
+    "jxlhip_splines_from_quantized", "jxlhip_splines_destroy", "jxlhip_splines_quantized", "jxlhip_splines_segments", "jxlhip_image_header_decode", "jxlhip_icc_decode", "jxlhip_output_opsin_matrix",
     "jxlhip_modular_global_decode", "jxlhip_modular_tree_destroy", "jxlhip_dc_group_decode", "jxlhip_dc_group_decode_staged",
     "jxlhip_modular_ac_group_decode", "jxlhip_modular_ac_group_decode_f32", "jxlhip_modular_extra_channel_f32",
     "jxlhip_modular_groups_are_final", "jxlhip_modular_uses_dc_groups", "jxlhip_modular_finalize",
@@ -297,6 +305,13 @@ def load_library():
     L.jxlhip_frame_header_decode.argtypes = [vp, sz, C.POINTER(sz), C.POINTER(ImageInfo), C.POINTER(FrameHeader)]
     L.jxlhip_dc_global_decode.argtypes = [vp, sz, C.POINTER(sz), C.c_uint64, C.POINTER(DcGlobal)]
     L.jxlhip_noise_lut_decode.argtypes = [vp, sz, C.POINTER(sz), C.POINTER(C.c_float)]
+    L.jxlhip_splines_decode.argtypes = [vp, sz, C.POINTER(sz), C.c_uint64, C.POINTER(vp)]
+    L.jxlhip_splines_from_quantized.argtypes = [u32, vp, vp, vp, vp, i32, C.POINTER(vp)]
+    L.jxlhip_splines_destroy.argtypes = [vp]
+    L.jxlhip_splines_destroy.restype = None
+    L.jxlhip_splines_segments.argtypes = [vp, u32, u32, C.c_float, C.c_float, vp, sz, C.POINTER(sz)]
+    L.jxlhip_set_splines.argtypes = [vp, vp]
+    L.jxlhip_splines_quantized.argtypes = [vp, C.POINTER(u32), C.POINTER(sz), C.POINTER(i32), vp, vp, vp, vp]
     L.jxlhip_modular_global_decode.argtypes = [vp, sz, C.POINTER(sz), C.POINTER(FrameHeader), C.POINTER(vp)]
     L.jxlhip_modular_tree_destroy.argtypes = [vp]
     L.jxlhip_modular_tree_destroy.restype = None
@@ -360,3 +375,60 @@ def load_library():
     L.jxlhip_ac_global_decode_at.argtypes = [vp, sz, C.POINTER(sz), u32, u32, u32, vp, vp, C.POINTER(u32), C.POINTER(vp)]
     _lib = L
     return L
+
+
+def splines_from_quantized(splines, quantization_adjustment=0, L=None):
+    """jxlhip_splines_from_quantized: an owned jxlhip_splines* (c_void_p) from quantized splines, each a dict with
+    "start" (x, y), "deltas" [(ddx, ddy), ...] (the control-point delta-deltas), "color" (3 x 32 ints) and "sigma" (32
+    ints).  Returns (rc, handle); free the handle with splines_destroy."""
+    import numpy as np
+    L = L or load_library()
+    n = len(splines)
+    starts = np.array([sp["start"] for sp in splines], np.int32).reshape(-1)
+    counts = np.array([len(sp["deltas"]) for sp in splines], np.uint32)
+    deltas = np.array([d for sp in splines for d in sp["deltas"]] or [(0, 0)], np.int64).astype(np.int32).reshape(-1)
+    dcts = np.array([np.concatenate([np.asarray(sp["color"], np.int64).reshape(96), np.asarray(sp["sigma"], np.int64)])
+                     for sp in splines], np.int64).astype(np.int32).reshape(-1)
+    h = C.c_void_p()
+    rc = L.jxlhip_splines_from_quantized(n, starts.ctypes.data, counts.ctypes.data, deltas.ctypes.data,
+                                         dcts.ctypes.data, int(quantization_adjustment), C.byref(h))
+    return rc, h
+
+
+def splines_destroy(handle, L=None):
+    (L or load_library()).jxlhip_splines_destroy(handle)
+
+
+def splines_segments(handle, xsize, ysize, y_to_x=0.0, y_to_b=1.0, L=None):
+    """jxlhip_splines_segments: (rc, array of SplineSegment) -- the draw list of the frame."""
+    L = L or load_library()
+    n = C.c_size_t(0)
+    rc = L.jxlhip_splines_segments(handle, xsize, ysize, y_to_x, y_to_b, None, 0, C.byref(n))
+    if rc:
+        return rc, (SplineSegment * 0)()
+    out = (SplineSegment * n.value)()
+    rc = L.jxlhip_splines_segments(handle, xsize, ysize, y_to_x, y_to_b, out, n.value, C.byref(n))
+    return rc, out
+
+
+def splines_quantized(handle, L=None):
+    """jxlhip_splines_quantized: (quantization_adjustment, [dict(start, deltas, color, sigma), ...])."""
+    import numpy as np
+    L = L or load_library()
+    n, nd, adj = C.c_uint32(0), C.c_size_t(0), C.c_int32(0)
+    assert L.jxlhip_splines_quantized(handle, C.byref(n), C.byref(nd), C.byref(adj), None, None, None, None) == 0
+    starts = np.zeros(2 * n.value, np.int32)
+    counts = np.zeros(n.value, np.uint32)
+    deltas = np.zeros(max(1, 2 * nd.value), np.int32)
+    dcts = np.zeros(128 * n.value, np.int32)
+    assert L.jxlhip_splines_quantized(handle, C.byref(n), C.byref(nd), C.byref(adj), starts.ctypes.data,
+                                      counts.ctypes.data, deltas.ctypes.data, dcts.ctypes.data) == 0
+    out, k = [], 0
+    for i in range(n.value):
+        m = int(counts[i])
+        out.append(dict(start=(int(starts[2 * i]), int(starts[2 * i + 1])),
+                        deltas=[(int(deltas[2 * j]), int(deltas[2 * j + 1])) for j in range(k, k + m)],
+                        color=dcts[128 * i:128 * i + 96].reshape(3, 32).tolist(),
+                        sigma=dcts[128 * i + 96:128 * i + 128].tolist()))
+        k += m
+    return adj.value, out

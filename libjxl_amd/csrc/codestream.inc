@@ -132,7 +132,7 @@ int ParseHeaders(const uint8_t* cs, size_t n, ParsedHeaders* h) {
   if (rc) return rc;
   const jxlhip_frame_header& fh = h->fh;
   if (fh.is_modular || fh.color_transform != JXLHIP_CT_XYB || fh.frame_type != JXLHIP_FRAME_REGULAR ||
-      (fh.flags & (JXLHIP_FLAG_PATCHES | JXLHIP_FLAG_SPLINES | JXLHIP_FLAG_USE_DC_FRAME)) ||
+      (fh.flags & (JXLHIP_FLAG_PATCHES | JXLHIP_FLAG_USE_DC_FRAME)) ||
       fh.chroma_mode[0] || fh.chroma_mode[1] || fh.chroma_mode[2] || fh.upsampling != 1 || fh.dc_level != 0 ||
       fh.custom_size_or_origin || !fh.is_last || fh.xsize != ih.xsize || fh.ysize != ih.ysize)
     return JXLHIP_ERR_UNSUPPORTED;
@@ -563,12 +563,21 @@ static int DecodeCodestreamImpl(jxlhip_ctx* c, jxlhip_parallel_runner runner, vo
   // ---- DC global: quantizer, block context map, colour correlation; the global modular tree
   jxlhip_dc_global dcg;
   size_t spos = 0;  // bit position inside section 0 (the only section of a single-section frame)
+  // the splines bundle leads the section (dec_frame.cc:289-293); jxlhip_dc_global_decode reads on from behind it
+  std::unique_ptr<jxlhip_splines, void (*)(jxlhip_splines*)> splines(nullptr, jxlhip_splines_destroy);
+  if (fh.flags & JXLHIP_FLAG_SPLINES) {
+    jxlhip_splines* sp = nullptr;
+    if ((rc = jxlhip_splines_decode(sec(0), sz[0], &spos, (uint64_t)fh.xsize * fh.ysize, &sp)))
+      return Fail(c, rc, "invalid splines");
+    splines.reset(sp);
+  }
   float noise_lut[8] = {0};
   if (fh.flags & JXLHIP_FLAG_NOISE) {
     size_t npos = spos;
     if ((rc = jxlhip_noise_lut_decode(sec(0), sz[0], &npos, noise_lut))) return Fail(c, rc, "invalid noise parameters");
   }
-  if ((rc = jxlhip_dc_global_decode(sec(0), sz[0], &spos, fh.flags, &dcg))) return Fail(c, rc, "invalid DC global section");
+  if ((rc = jxlhip_dc_global_decode(sec(0), sz[0], &spos, fh.flags & ~(uint64_t)JXLHIP_FLAG_SPLINES, &dcg)))
+    return Fail(c, rc, "invalid DC global section");
   jxlhip_modular_tree* tree_raw = nullptr;
   if ((rc = jxlhip_modular_global_decode(sec(0), sz[0], &spos, &fh, &tree_raw)))
     return Fail(c, rc, "invalid modular global section");
@@ -922,6 +931,7 @@ static int DecodeCodestreamImpl(jxlhip_ctx* c, jxlhip_parallel_runner runner, vo
   // photon noise: the stream's only frame is visible frame 1 (FrameDecoder::InitFrame counts it before decoding,
   // dec_frame.cc:160-168)
   if ((fh.flags & JXLHIP_FLAG_NOISE) && (rc = jxlhip_set_noise(c, noise_lut, 1, 0))) return rc;
+  if (splines && (rc = jxlhip_set_splines(c, splines.get()))) return rc;
   if ((rc = jxlhip_decode_frame(c, out, out_stride, out_plane_stride))) return rc;
   if ((rc = jxlhip_sync(c))) return rc;
   clock.Mark(JXLHIP_PHASE_KERNELS);

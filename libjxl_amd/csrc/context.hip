@@ -14,6 +14,7 @@
 #include <functional>
 #include <condition_variable>
 #include <atomic>
+#include <memory>
 #include <mutex>
 #include <vector>
 
@@ -172,6 +173,20 @@ struct jxlhip_ctx {
   float* noise_buf = nullptr;
   size_t noise_floats = 0;
   uint32_t* noise_jump = nullptr;
+  // jxlhip_set_splines: the draw list of the current frame (frame_begin resets splines_on), binned by 64 x 16 tile
+  // (kernels_splines.hip); spl_tiles = tile_start (tiles + 1), tile_idx, active tiles.  The host copies stay alive
+  // until spl_ev says their upload is done.
+  bool splines_on = false;
+  SplineSeg* spl_segs = nullptr;
+  size_t spl_segs_items = 0;
+  uint32_t* spl_tiles = nullptr;
+  size_t spl_tiles_items = 0;
+  uint32_t spl_tiles_x = 0, spl_num_tiles = 0, spl_num_active = 0;
+  size_t spl_entries = 0;
+  std::vector<SplineSeg> spl_host_segs;
+  std::vector<uint32_t> spl_host_tiles;
+  hipEvent_t spl_ev = nullptr;
+  bool spl_ev_pending = false;
   size_t qdc_dev_items = 0;
   // transform-kernel fan-out (JXLHIP_BLOCK_STREAMS: 3 = one stream per family; default 1 = back to back on the
   // main stream, measured 15 % faster than letting the families compete for the CUs)
@@ -472,9 +487,10 @@ void jxlhip_destroy(jxlhip_ctx* c) {
                   c->error_flag, c->tables, c->up_coeffs[0], c->up_side,
                   c->dc_tmp,     c->quant_enc,  c->dc_prec,      c->cell_info,
                   c->qdc_dev,    c->host_frame_dev, c->planes2, c->orient_dev,
-                  c->alpha_dev,  c->noise_buf,  c->noise_jump};
+                  c->alpha_dev,  c->noise_buf,  c->noise_jump, c->spl_segs, c->spl_tiles};
   for (void* b : bufs)
     if (b) (void)hipFree(b);
+  if (c->spl_ev) (void)hipEventDestroy(c->spl_ev);
   if (c->own_stream) (void)hipStreamDestroy(c->own_stream);
   DeleteCtx(c);
 }
@@ -677,6 +693,7 @@ int jxlhip_frame_begin(jxlhip_ctx* c, const jxlhip_frame_params* p) {
   c->have_inputs = false;
   c->blocks_done = false;
   c->noise_on = false;
+  c->splines_on = false;
   return JXLHIP_OK;
 }
 
@@ -858,6 +875,91 @@ int jxlhip_set_noise(jxlhip_ctx* c, const float lut[8], uint32_t visible_frame_i
   c->noise_visible = visible_frame_index;
   c->noise_nonvisible = nonvisible_frame_index;
   c->noise_on = true;
+  return JXLHIP_OK;
+}
+
+// std::llround of a float as the reference's x86-64 build evaluates it: out-of-range and NaN arguments give INT64_MIN
+static int64_t SplineRound(float v) { return fabsf(v) < 9.0e18f ? (int64_t)llroundf(v) : INT64_MIN; }
+
+// Splines of the current frame (FrameHeader::kSplines): the draw list of Splines::InitializeDrawCache for the frame's
+// size and base colour correlation, binned by 64 x 16 tile for k_splines; frame_begin resets to "no splines".
+int jxlhip_set_splines(jxlhip_ctx* c, const jxlhip_splines* s) {
+  if (!c) return JXLHIP_ERR_INVALID_ARGUMENT;
+  if (!c->children.empty()) return Fail(c, JXLHIP_ERR_UNSUPPORTED, "splines on a multi-device context");
+  if (!c->have_frame) return Fail(c, JXLHIP_ERR_STATE, "set_splines before frame_begin");
+  if (c->f.group_y0 != 0 || c->f.group_rows != c->f.ysg) return Fail(c, JXLHIP_ERR_UNSUPPORTED, "splines with stripes");
+  if (c->p.undo_orientation > 1)
+    return Fail(c, JXLHIP_ERR_UNSUPPORTED, "splines with undo_orientation %u", c->p.undo_orientation);
+  c->splines_on = false;
+  if (!s) return JXLHIP_OK;
+  const uint32_t W = c->f.xsize, H = c->f.ysize;
+  HIPCHK(c, hipSetDevice(c->device));
+  if (c->spl_ev_pending) {  // the previous frame's upload still reads the host copies
+    HIPCHK(c, hipEventSynchronize(c->spl_ev));
+    c->spl_ev_pending = false;
+  }
+  size_t n = 0;
+  int rc = jxlhip_splines_segments(s, W, H, c->p.cfl_base_x, c->p.cfl_base_b, nullptr, 0, &n);
+  if (rc) return Fail(c, rc, "invalid splines");
+  std::vector<jxlhip_spline_segment> segs(n);
+  if (n && (rc = jxlhip_splines_segments(s, W, H, c->p.cfl_base_x, c->p.cfl_base_b, segs.data(), n, &n)))
+    return Fail(c, rc, "invalid splines");
+  // bin by tile: the column span of DrawSegment (splines.cc:116-125) clipped to the frame, the row span as computed
+  const uint32_t tx = (W + 63) / 64, ty = (H + 15) / 16, tiles = tx * ty;
+  std::vector<SplineSeg>& hs = c->spl_host_segs;
+  hs.clear();
+  std::vector<uint32_t> count(tiles + 1, 0);
+  for (const jxlhip_spline_segment& g : segs) {
+    const int64_t start = SplineRound(g.center_x - g.maximum_distance);
+    const int64_t end = SplineRound(g.center_x + g.maximum_distance);
+    if (end < 0 || start >= (int64_t)W || g.y1 <= g.y0) continue;
+    SplineSeg d;
+    d.cx = g.center_x;
+    d.cy = g.center_y;
+    d.inv_sigma = g.inv_sigma;
+    d.s4i = g.sigma_over_4_times_intensity;
+    for (int k = 0; k < 3; k++) d.color[k] = g.color[k];
+    d.y0 = g.y0;
+    d.y1 = g.y1;
+    d.x0 = (int32_t)std::max<int64_t>(start, 0);
+    d.x1 = (int32_t)std::min<int64_t>(end, (int64_t)W - 1);
+    d.pad = 0.0f;
+    hs.push_back(d);
+    for (uint32_t y = (uint32_t)d.y0 / 16; y <= (uint32_t)(d.y1 - 1) / 16; y++)
+      for (uint32_t x = (uint32_t)d.x0 / 64; x <= (uint32_t)d.x1 / 64; x++) count[y * tx + x + 1]++;
+  }
+  std::vector<uint32_t>& ht = c->spl_host_tiles;
+  ht.assign(tiles + 1, 0);
+  uint32_t active = 0;
+  for (uint32_t t = 0; t < tiles; t++) {
+    active += count[t + 1] != 0;
+    ht[t + 1] = ht[t] + count[t + 1];
+  }
+  const size_t entries = ht[tiles];
+  if (entries == 0) return JXLHIP_OK;  // nothing reaches the frame: the spline-free path
+  if (entries > 0xFFFFFFFFu - tiles) return Fail(c, JXLHIP_ERR_OUT_OF_MEMORY, "spline draw list too long");
+  ht.resize(tiles + 1 + entries + active);
+  uint32_t* fill = count.data();  // write cursor per tile
+  for (uint32_t t = 0; t < tiles; t++) fill[t] = ht[t];
+  for (uint32_t i = 0; i < (uint32_t)hs.size(); i++) {
+    const SplineSeg& d = hs[i];
+    for (uint32_t y = (uint32_t)d.y0 / 16; y <= (uint32_t)(d.y1 - 1) / 16; y++)
+      for (uint32_t x = (uint32_t)d.x0 / 64; x <= (uint32_t)d.x1 / 64; x++) ht[tiles + 1 + fill[y * tx + x]++] = i;
+  }
+  for (uint32_t t = 0, a = 0; t < tiles; t++)
+    if (ht[t + 1] != ht[t]) ht[tiles + 1 + entries + a++] = t;
+  if ((rc = Grow(c, &c->spl_segs, &c->spl_segs_items, hs.size()))) return rc;
+  if ((rc = Grow(c, &c->spl_tiles, &c->spl_tiles_items, ht.size()))) return rc;
+  HIPCHK(c, hipMemcpyAsync(c->spl_segs, hs.data(), hs.size() * sizeof(SplineSeg), hipMemcpyHostToDevice, c->stream));
+  HIPCHK(c, hipMemcpyAsync(c->spl_tiles, ht.data(), ht.size() * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
+  if (!c->spl_ev) HIPCHK(c, hipEventCreateWithFlags(&c->spl_ev, hipEventDisableTiming));
+  HIPCHK(c, hipEventRecord(c->spl_ev, c->stream));
+  c->spl_ev_pending = true;
+  c->spl_tiles_x = tx;
+  c->spl_num_tiles = tiles;
+  c->spl_num_active = active;
+  c->spl_entries = entries;
+  c->splines_on = true;
   return JXLHIP_OK;
 }
 
@@ -1756,6 +1858,8 @@ int jxlhip_decode_filters_rows(jxlhip_ctx* c, void* out, size_t out_stride, size
   if (!c->blocks_done) return Fail(c, JXLHIP_ERR_STATE, "decode_filters before decode_blocks");
   if (c->p.undo_orientation > 1) return Fail(c, JXLHIP_ERR_UNSUPPORTED, "undo_orientation with the split calls");
   if (c->noise_on) return Fail(c, JXLHIP_ERR_UNSUPPORTED, "noise with the split calls (jxlhip_decode_frame takes it)");
+  if (c->splines_on)
+    return Fail(c, JXLHIP_ERR_UNSUPPORTED, "splines with the split calls (jxlhip_decode_frame takes them)");
   int rc = CheckOutArgs(c, out, out_stride, out_plane_stride);
   if (rc) return rc;
   HIPCHK(c, hipSetDevice(c->device));
@@ -1808,7 +1912,7 @@ int jxlhip_stripe_finish(jxlhip_ctx* c, const float* recv_up, const float* recv_
 // XYB planes in the 256 MB Infinity Cache; measured on MI355X it only loses
 // time, so the default is one band = the whole stripe.
 static int DecodeFrameCoded(jxlhip_ctx* c, void* out, size_t out_stride, size_t out_plane_stride);
-static int DecodeFrameNoise(jxlhip_ctx* c, void* out, size_t out_stride, size_t out_plane_stride);
+static int DecodeFrameFeatures(jxlhip_ctx* c, void* out, size_t out_stride, size_t out_plane_stride);
 
 // bytes of one interleaved output pixel (0: planar XYB)
 static size_t OutPixelBytes(const jxlhip_ctx* c) {
@@ -1822,7 +1926,7 @@ int jxlhip_decode_frame(jxlhip_ctx* c, void* out, size_t out_stride, size_t out_
   if (!c) return JXLHIP_ERR_INVALID_ARGUMENT;
   if (!c->children.empty()) return out ? MultiDecodeFrame(c, out, nullptr, out_stride, out_plane_stride) : JXLHIP_ERR_INVALID_ARGUMENT;
   if (!c->have_frame) return Fail(c, JXLHIP_ERR_STATE, "decode needs frame_begin + inputs");
-  if (c->noise_on) return DecodeFrameNoise(c, out, out_stride, out_plane_stride);
+  if (c->noise_on || c->splines_on) return DecodeFrameFeatures(c, out, out_stride, out_plane_stride);
   if (c->p.undo_orientation <= 1) return DecodeFrameCoded(c, out, out_stride, out_plane_stride);
   // undo_orientation: coded orientation into a staging frame, k_orient into the caller's buffer
   const DevFrame& f = c->f;
@@ -1919,47 +2023,70 @@ static int DecodeFrameCoded(jxlhip_ctx* c, void* out, size_t out_stride, size_t 
   return LaunchFiltersRows(c, fp, prev_y0, f.y1);
 }
 
-// A frame with photon noise (jxlhip_set_noise; whole frames, coded orientation): the frame's own path -- fused or
-// two-phase, whatever DecodeFrameCoded picks for it -- writes the filtered frame as planar XYB into context memory,
-// then k_noise_rng + k_noise_emit (kernels_noise.hip) add the noise between the loop filters and the XYB stage, where
-// the reference's pipeline has it (dec_cache.cc:205-210), and write the caller's output.
-static int DecodeFrameNoise(jxlhip_ctx* c, void* out, size_t out_stride, size_t out_plane_stride) {
+// A frame with splines and / or photon noise (jxlhip_set_splines, jxlhip_set_noise; whole frames, coded orientation):
+// the frame's own path -- fused or two-phase, whatever DecodeFrameCoded picks for it -- writes the filtered frame as
+// planar XYB into context memory; the render stages the reference's pipeline has between the loop filters and the
+// XYB stage follow (dec_cache.cc:194-210), splines first, then noise, and the last launch writes the caller's output:
+//   splines only  k_splines draws every tile and emits;
+//   noise only    k_noise_rng + k_noise_emit (kernels_noise.hip);
+//   both          k_splines draws the tiles with segments back into the planes, then the noise launches.
+static int DecodeFrameFeatures(jxlhip_ctx* c, void* out, size_t out_stride, size_t out_plane_stride) {
   int rc = CheckOutArgs(c, out, out_stride, out_plane_stride);
   if (rc) return rc;
   const DevFrame& f = c->f;
   if (f.group_y0 != 0 || f.group_rows != f.ysg || c->p.undo_orientation > 1)
-    return Fail(c, JXLHIP_ERR_UNSUPPORTED, "noise needs a whole frame in coded orientation");
+    return Fail(c, JXLHIP_ERR_UNSUPPORTED, "noise / splines need a whole frame in coded orientation");
   HIPCHK(c, hipSetDevice(c->device));
   const uint32_t ns = (f.xsize + 63u) & ~63u;
   const size_t nplane = (size_t)ns * f.ysize;
-  if ((rc = Grow(c, &c->noise_buf, &c->noise_floats, 6 * nplane))) return rc;
+  if ((rc = Grow(c, &c->noise_buf, &c->noise_floats, (c->noise_on ? 6 : 3) * nplane))) return rc;
   const uint32_t kind = c->p.output_kind;
   c->p.output_kind = JXLHIP_OUT_XYB_PLANAR;
   rc = DecodeFrameCoded(c, c->noise_buf, ns, nplane);
   c->p.output_kind = kind;
   if (rc) return rc;
-  NoiseArgs N{};
-  N.xsize = f.xsize;
-  N.ysize = f.ysize;
-  N.xsg = f.xsg;
-  N.ysg = f.ysg;
-  N.visible = c->noise_visible;
-  N.nonvisible = c->noise_nonvisible;
-  memcpy(N.lut, c->noise_lut, sizeof(N.lut));
-  N.ytox = c->p.cfl_base_x;  // ColorCorrelation::YtoXRatio(0) / YtoBRatio(0) (chroma_from_luma.h:51-57)
-  N.ytob = c->p.cfl_base_b;
-  N.xyb = c->noise_buf;
-  N.rnd = c->noise_buf + 3 * nplane;
-  N.ns = ns;
-  N.nplane = nplane;
-  N.jump = c->noise_jump;
   FilterParams fp = c->fp;
   fp.out = out;
   fp.out_stride = out_stride;
   fp.out_plane_stride = out_plane_stride;
   ProfBegin(c);
-  if (!LaunchNoise(N, fp, (int)kind, c->stream)) return Fail(c, JXLHIP_ERR_INVALID_ARGUMENT, "noise output kind %u", kind);
-  ProfMark(c, JXLHIP_KERNEL_NOISE);
+  if (c->splines_on) {
+    SplineArgs S{};
+    S.xsize = f.xsize;
+    S.ysize = f.ysize;
+    S.tiles_x = c->spl_tiles_x;
+    S.num_active = c->spl_num_active;
+    S.xyb = c->noise_buf;
+    S.xyb_out = c->noise_buf;
+    S.ns = ns;
+    S.nplane = nplane;
+    S.segs = c->spl_segs;
+    S.tile_start = c->spl_tiles;
+    S.tile_idx = c->spl_tiles + c->spl_num_tiles + 1;
+    S.active = c->spl_tiles + c->spl_num_tiles + 1 + c->spl_entries;
+    if (!LaunchSplines(S, fp, (int)kind, /*in_place=*/c->noise_on, c->stream))
+      return Fail(c, JXLHIP_ERR_INVALID_ARGUMENT, "splines output kind %u", kind);
+    ProfMark(c, JXLHIP_KERNEL_SPLINES);
+  }
+  if (c->noise_on) {
+    NoiseArgs N{};
+    N.xsize = f.xsize;
+    N.ysize = f.ysize;
+    N.xsg = f.xsg;
+    N.ysg = f.ysg;
+    N.visible = c->noise_visible;
+    N.nonvisible = c->noise_nonvisible;
+    memcpy(N.lut, c->noise_lut, sizeof(N.lut));
+    N.ytox = c->p.cfl_base_x;  // ColorCorrelation::YtoXRatio(0) / YtoBRatio(0) (chroma_from_luma.h:51-57)
+    N.ytob = c->p.cfl_base_b;
+    N.xyb = c->noise_buf;
+    N.rnd = c->noise_buf + 3 * nplane;
+    N.ns = ns;
+    N.nplane = nplane;
+    N.jump = c->noise_jump;
+    if (!LaunchNoise(N, fp, (int)kind, c->stream)) return Fail(c, JXLHIP_ERR_INVALID_ARGUMENT, "noise output kind %u", kind);
+    ProfMark(c, JXLHIP_KERNEL_NOISE);
+  }
   ProfEnd(c);
   HIPCHK(c, hipGetLastError());
   return JXLHIP_OK;

@@ -2717,3 +2717,5 @@ int jxlhip_ac_group_decode_sparse(const jxlhip_ac_pass* pass, uint32_t xsb, uint
 }
 
 }  // extern "C"
+
+#include "splines.inc"

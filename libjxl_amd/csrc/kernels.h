@@ -125,6 +125,31 @@ void NoiseStateAfter(uint32_t visible, uint32_t nonvisible, uint32_t x0, uint32_
 // into p.out (whole frames only); false for a bad output kind
 bool LaunchNoise(const NoiseArgs& N, const FilterParams& p, int output_kind, hipStream_t st);
 
+// Splines (kernels_splines.hip).  The frame is cut into 64 x 16 tiles; tile t draws the segments
+// segs[tile_idx[tile_start[t] .. tile_start[t + 1])] in that (increasing) order.
+struct SplineSeg {       // SplineSegment (splines.h:95-101) with its spans; 48 bytes
+  float cx, cy, inv_sigma, s4i;
+  float color[3];
+  int32_t y0, y1;        // rows [y0, y1), inside the frame
+  int32_t x0, x1;        // columns [x0, x1] = [llround(cx - maximum_distance), llround(cx + maximum_distance)] clipped
+  float pad;
+};
+struct SplineArgs {
+  uint32_t xsize, ysize, tiles_x;
+  uint32_t num_active;     // tiles with segments (draw-in-place covers only these)
+  const float* xyb;        // the filtered frame: 3 planes, ns floats per row, nplane floats apart
+  float* xyb_out;          // draw-in-place: where the drawn planes go (same layout; may be xyb)
+  uint32_t ns;
+  size_t nplane;
+  const SplineSeg* segs;
+  const uint32_t* tile_start;  // tiles + 1 entries
+  const uint32_t* tile_idx;
+  const uint32_t* active;      // num_active tile indices
+};
+// k_splines: in_place = false: draw every tile and write the output tail of `output_kind` into p.out; true: draw the
+// active tiles back into S.xyb_out (planar XYB, for the noise launches).  False for a bad output kind.
+bool LaunchSplines(const SplineArgs& S, const FilterParams& p, int output_kind, bool in_place, hipStream_t st);
+
 // block-major plane rows <-> dense row-major staging
 void LaunchZeroU32(uint32_t* p, uint32_t n, hipStream_t st);  // (kernels_tables.hip: a kernel, for captured graphs)
 void LaunchRowsCopy(const DevFrame& f, float* dense, int y_first, int nrows, int ncols,

@@ -134,6 +134,20 @@ class VarDctDecoder:
         _check(self.L, self.ctx, self.L.jxlhip_set_noise(self.ctx, (C.c_float * 8)(*vals), int(visible_frame_index),
                                                          int(nonvisible_frame_index)), "set_noise")
 
+    def set_splines(self, splines, quantization_adjustment=0):
+        """Splines of the current frame (FrameHeader::kSplines), jxlhip_set_splines: a jxlhip_splines* handle
+        (abi.splines_from_quantized, jxlhip_splines_decode) or a list of quantized splines in the form
+        abi.splines_from_quantized takes; None = no splines.  begin_frame resets to no splines."""
+        if splines is None or isinstance(splines, (int, C.c_void_p)):
+            _check(self.L, self.ctx, self.L.jxlhip_set_splines(self.ctx, splines), "set_splines")
+            return
+        rc, h = abi.splines_from_quantized(splines, quantization_adjustment, self.L)
+        _check(self.L, self.ctx, rc, "splines_from_quantized")
+        try:
+            _check(self.L, self.ctx, self.L.jxlhip_set_splines(self.ctx, h), "set_splines")
+        finally:
+            abi.splines_destroy(h, self.L)
+
     # -- decode ----------------------------------------------------------------
     def decode_blocks(self):
         _check(self.L, self.ctx, self.L.jxlhip_decode_blocks(self.ctx), "decode_blocks")
