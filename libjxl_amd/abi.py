@@ -3,7 +3,7 @@ import ctypes as C
 import os
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
-# JXLHIP_SO: an experiment build of the library (tools/build_variant.py); default = the product
+# JXLHIP_SO: another build of the library (an experiment); default = the product
 _SO = os.environ.get("JXLHIP_SO") or os.path.join(_HERE, "csrc", "libjxl_hip.so")
 _RUNNER_SO = os.path.join(_HERE, "csrc", "libjxl_threads_hip.so")
 

@@ -34,15 +34,12 @@ using namespace jxlhip;
 namespace {
 
 constexpr int kPoolStreams = 8;
-constexpr int kMaxBlockStreams = 8;
-constexpr int kMaxBands = 64;
-// Counter blocks (kCountStride u32 each): [0, kMaxBands) the bands of a direct decode (one-band frames alternate between
-// blocks 0 and 1, each frame's k_prepare zeroing the next one's); a frame recorded into a hipGraph uses the same indices
-// + kCaptureBase, blocks no direct call ever touches -- a replay dirties its blocks behind the host's back, and the
-// host's "clean" flags describe blocks 0 / 1 only (round 5 put captured frames on block 0: a replay between two direct
-// calls left k_prepare starting on non-zero counters).
-constexpr int kCaptureBase = kMaxBands;
-constexpr int kCountBlocks = 2 * kMaxBands;
+// Counter blocks (kCountStride u32 each) of phase 1 (LaunchPhase1): direct calls alternate between blocks 0 and 1; a
+// phase 1 recorded into a hipGraph uses kCaptureBlock, a block no direct call ever touches -- a replay dirties its block
+// behind the host's back, and the host's "clean" flags describe blocks 0 / 1 only (round 5 put captured frames on
+// block 0, round 6 still the split calls: a replay between two direct calls left k_prepare starting on non-zero counters).
+constexpr int kCaptureBlock = 2;
+constexpr int kCountBlocks = 3;
 // pinned staging buffers of jxlhip_ac_group_decode_submit (0.4 / 0.8 MB each): kStageSlotsFirst at first use, one more
 // whenever a thread would otherwise have to wait for an upload to finish, up to kStageSlots.  (An upload is microseconds
 // of PCIe, but the runtime now and then sits on a queued copy for 10-30 ms -- profiles/r04_e2e_waits.txt -- and with 32
@@ -80,8 +77,8 @@ struct jxlhip_ctx {
   bool have_frame = false;
   bool have_inputs = false;
   bool blocks_done = false;
-  // One-band decodes of whole frames alternate between counter blocks 0 and 1: k_prepare of frame N zeroes the block
-  // frame N + 1 will use (DevFrame::zero_counts) -- no memset launch per frame.  clean[b]: block b is all zero.
+  // Direct phase-1 launches alternate between counter blocks 0 and 1: k_prepare of frame N zeroes the block frame N + 1
+  // will use (DevFrame::zero_counts) -- no memset launch per frame.  clean[b]: block b is all zero.
   int counts_slot = 0;
   bool counts_clean[2] = {false, false};
   double cs_phase_ms[8] = {};  // jxlhip_codestream_phase_ms
@@ -188,17 +185,9 @@ struct jxlhip_ctx {
   hipEvent_t spl_ev = nullptr;
   bool spl_ev_pending = false;
   size_t qdc_dev_items = 0;
-  // transform-kernel fan-out (JXLHIP_BLOCK_STREAMS: 3 = one stream per family; default 1 = back to back on the
-  // main stream, measured 15 % faster than letting the families compete for the CUs)
-  int nblock_streams = 1;
-  hipStream_t bstreams[kMaxBlockStreams] = {nullptr};
-  hipEvent_t bev[kMaxBlockStreams] = {nullptr};
-  hipEvent_t fork_ev = nullptr;
-  int band_rows = 0;  // JXLHIP_BAND_ROWS: group rows per band of decode_frame (0 = whole stripe, the default:
-                      // measured on MI355X, bands of 1-9 group rows under-fill the chip and lose 10-70 %)
   bool generic_filters = false;  // JXLHIP_FILTERS=generic: LDS kernel for every stage list
   int mfma = -1;                 // DCT32X32 / DCT16X16 on the matrix cores (kernels_mfma.hip; the 16x16 rule is in
-                                 // LaunchBlocksBand).  -1 (default): when the caller's
+                                 // LaunchPhase1).  -1 (default): when the caller's
                                  // used_acs says DCT32X32 is the only class of the row-per-lane 32-point family in
                                  // the frame (the class kernel then is a launch of its own anyway; measured on c5:
                                  // 219 -> 193 us); on mixed frames the butterflies inside the merged launch win
@@ -376,27 +365,16 @@ int jxlhip_create_ex(int device, const JxlMemoryManagerHip* memory_manager, jxlh
   {  // the debug / test switches follow the environment as it is when a context is created (and at no other time)
     std::lock_guard<std::mutex> lock(jxlhip_env::g.mu);
     jxlhip_env::LoadLocked();
-  }
-  {
-    const char* e = getenv("JXLHIP_FILTERS");
-    c->generic_filters = e && !strcmp(e, "generic");
-    const char* b = getenv("JXLHIP_BLOCK_STREAMS");
-    if (b) c->nblock_streams = atoi(b);
-    const char* su = getenv("JXLHIP_SPARSE_UPLOAD");
-    if (su) c->sparse_upload = atoi(su) != 0;
-    const char* fu = getenv("JXLHIP_FUSE");
-    if (fu) c->fuse = atoi(fu) != 0 ? 1 : 0;
-    const char* mf = getenv("JXLHIP_MFMA");
-    if (mf) c->mfma = atoi(mf) != 0 ? 1 : 0;
-    if (const char* ss = getenv("JXLHIP_STAGE_SLOTS")) {  // whole chunks, at least the first allocation
-      const int v = (atoi(ss) + kStageChunk - 1) / kStageChunk * kStageChunk;
+    const jxlhip_env::Switches& s = jxlhip_env::g;
+    c->generic_filters = s.generic_filters.load();
+    c->sparse_upload = s.sparse_upload.load();
+    c->fuse = s.fuse.load();
+    c->mfma = s.mfma.load();
+    const int ss = s.stage_slots.load();
+    if (ss != jxlhip_env::Switches::kUnset) {  // whole chunks, at least the first allocation
+      const int v = (ss + kStageChunk - 1) / kStageChunk * kStageChunk;
       c->stage_cap = v < kStageSlotsFirst ? kStageSlotsFirst : (v > kStageSlots ? kStageSlots : v);
     }
-    const char* br = getenv("JXLHIP_BAND_ROWS");
-    if (br) c->band_rows = atoi(br);
-    if (c->band_rows < 0) c->band_rows = 0;
-    if (c->nblock_streams < 1) c->nblock_streams = 1;
-    if (c->nblock_streams > kMaxBlockStreams) c->nblock_streams = kMaxBlockStreams;
   }
   auto fail = [&](int code) {
     jxlhip_destroy(c);
@@ -411,14 +389,7 @@ int jxlhip_create_ex(int device, const JxlMemoryManagerHip* memory_manager, jxlh
         hipEventCreateWithFlags(&c->pool_ev[i], hipEventDisableTiming) != hipSuccess)
       return fail(JXLHIP_ERR_HIP);
   }
-  for (int i = 0; i < c->nblock_streams; i++) {
-    if (hipStreamCreateWithFlags(&c->bstreams[i], hipStreamNonBlocking) != hipSuccess ||
-        hipEventCreateWithFlags(&c->bev[i], hipEventDisableTiming) != hipSuccess)
-      return fail(JXLHIP_ERR_HIP);
-  }
-  if (hipEventCreateWithFlags(&c->fork_ev, hipEventDisableTiming) != hipSuccess ||
-      hipEventCreateWithFlags(&c->frame_ev, hipEventDisableTiming) != hipSuccess)
-    return fail(JXLHIP_ERR_HIP);
+  if (hipEventCreateWithFlags(&c->frame_ev, hipEventDisableTiming) != hipSuccess) return fail(JXLHIP_ERR_HIP);
   if (hipMalloc((void**)&c->counts, sizeof(uint32_t) * kCountStride * kCountBlocks) != hipSuccess ||
       hipMalloc((void**)&c->error_flag, sizeof(int32_t) * 2) != hipSuccess ||
       hipMalloc((void**)&c->tables, sizeof(float) * (512 + 64 + 1024 + 2048 + 256)) != hipSuccess ||
@@ -456,14 +427,6 @@ void jxlhip_destroy(jxlhip_ctx* c) {
     }
     if (c->pool_ev[i]) (void)hipEventDestroy(c->pool_ev[i]);
   }
-  for (int i = 0; i < kMaxBlockStreams; i++) {
-    if (c->bstreams[i]) {
-      (void)hipStreamSynchronize(c->bstreams[i]);
-      (void)hipStreamDestroy(c->bstreams[i]);
-    }
-    if (c->bev[i]) (void)hipEventDestroy(c->bev[i]);
-  }
-  if (c->fork_ev) (void)hipEventDestroy(c->fork_ev);
   if (c->frame_ev) (void)hipEventDestroy(c->frame_ev);
   for (int i = 0; i < kStageSlots; i++) {
     if (c->stage_ev[i]) {
@@ -1581,16 +1544,33 @@ int jxlhip_ac_group_decode_submit(jxlhip_ctx* c, const jxlhip_ac_pass* pass, uin
 // ---- decode -------------------------------------------------------------------
 namespace {
 
-// k_prepare + the transform kernels for group rows [g0, g1) of the stripe,
-// using counter slot `band`.
+// Phase 1 over the context's whole stripe (DevFrame::band_g0 / band_g1 = its group rows, set by jxlhip_frame_begin):
+// k_prepare + the transform kernels.  Every phase 1 takes its work-list counter block here.  Direct calls alternate
+// between blocks 0 and 1: a block gets a memset only when it is not marked clean, and the k_prepare of one call zeroes
+// the block the next call will use (DevFrame::zero_counts) -- no memset launch per frame.  Under stream capture -- the
+// caller records the frame's launches into a hipGraph and replays it (bench.py's `graph_replay`: the command
+// processor's ~5-8 us per dependent launch are paid once per graph instead) -- every replay must find the SAME block
+// zeroed by a node of the graph itself, and must not touch a block the direct calls keep a "clean" flag for:
+// kCaptureBlock, zeroed by a kernel (see LaunchZeroU32: no memset node at the root of a frame graph).
 // fused: 0 = two-phase, 1 = the whole frame through the fused kernel, 2 = a STRIPE through it (the DCT8 cells of
 // the stripe's first / last block row are decoded into the planes as well: they are the halo rows its neighbours pull)
-int LaunchBlocksBand(jxlhip_ctx* c, uint32_t g0, uint32_t g1, int band, int fused = 0,
-                     const FilterParams* emit = nullptr, int zero_band = -1) {
+int LaunchPhase1(jxlhip_ctx* c, int fused = 0, const FilterParams* emit = nullptr) {
   hipStream_t st = c->stream;
+  hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
+  (void)hipStreamIsCapturing(st, &cap);
+  const bool capturing = cap == hipStreamCaptureStatusActive;
+  const int block = capturing ? kCaptureBlock : c->counts_slot;
+  uint32_t* counts = c->counts + (size_t)block * kCountStride;
+  if (capturing) {
+    LaunchZeroU32(counts, (uint32_t)kCountStride, st);
+    HIPCHK(c, hipGetLastError());
+  } else {
+    if (!c->counts_clean[block]) HIPCHK(c, hipMemsetAsync(counts, 0, sizeof(uint32_t) * kCountStride, st));
+    // From here on the block is in use: whatever happens below (a failed launch after k_prepare ran), it must not be
+    // taken for clean by the next frame.  Block ^ 1 becomes clean only when the launches that zero it succeeded.
+    c->counts_clean[block] = false;
+  }
   DevFrame f = c->f;
-  f.band_g0 = g0;
-  f.band_g1 = g1;
   f.fused = (uint32_t)fused;
   f.cell_info = c->cell_info;
   {
@@ -1606,32 +1586,42 @@ int LaunchBlocksBand(jxlhip_ctx* c, uint32_t g0, uint32_t g1, int band, int fuse
                         (!(f.used_acs & (1u << 5)) || f.mfma32) && (uint64_t)f.xsize * f.ysize >= (16u << 20);
     f.mfma16 = (c->mfma > 0 || (c->mfma < 0 && lone16)) ? c->tables + 1600 + 2048 : nullptr;
   }
-  f.zero_counts = zero_band >= 0 ? c->counts + (size_t)zero_band * kCountStride : nullptr;
+  f.zero_counts = capturing ? nullptr : c->counts + (size_t)(block ^ 1) * kCountStride;
   if (fused == 2)  // a stripe: every cell "from the planes" until k_prepare says otherwise (whole frames: k_prepare writes every cell)
     HIPCHK(c, hipMemsetAsync(c->cell_info, 0xFF, sizeof(uint2) * (size_t)f.xsb * f.ysb, st));
   WorkLists wl = c->wl;
-  wl.count = c->counts + (size_t)band * kCountStride;
-  const uint32_t cells = f.xsg * (g1 - g0) * 1024u;
+  wl.count = counts;
+  const uint32_t cells = f.xsg * f.group_rows * 1024u;
   ProfBegin(c);
   LaunchPrepare(f, wl, c->p.lf.epf_iters > 0, c->p.lf.epf_quant_mul, c->lut, st);
   ProfMark(c, JXLHIP_KERNEL_PREPARE);
-  if (c->nblock_streams > 1) {
-    // fork: the class kernels wait for k_prepare, run side by side, and the
-    // main stream joins them all before anything that reads the planes
-    HIPCHK(c, hipEventRecord(c->fork_ev, st));
-    for (int i = 0; i < c->nblock_streams; i++)
-      HIPCHK(c, hipStreamWaitEvent(c->bstreams[i], c->fork_ev, 0));
-    LaunchBlocks(f, wl, cells, c->tables, c->tables + 512, c->bstreams, c->nblock_streams, emit);
-    for (int i = 0; i < c->nblock_streams; i++) {
-      HIPCHK(c, hipEventRecord(c->bev[i], c->bstreams[i]));
-      HIPCHK(c, hipStreamWaitEvent(st, c->bev[i], 0));
-    }
-  } else {
-    LaunchBlocks(f, wl, cells, c->tables, c->tables + 512, &st, 1, emit);
-  }
+  LaunchBlocks(f, wl, cells, c->tables, c->tables + 512, st, emit);
   ProfMark(c, JXLHIP_KERNEL_BLOCKS);
   ProfEnd(c);
   HIPCHK(c, hipGetLastError());
+  if (!capturing) {
+    c->counts_clean[block ^ 1] = true;
+    c->counts_slot = block ^ 1;
+  }
+  return JXLHIP_OK;
+}
+
+// epf_iters = 3: [Gaborish] + EPF0 into the second plane set -- from the fused producer's slab (k_fused_pc0) or from
+// the planes (k_epf0) -- then EPF1 + EPF2 + output from there.  *declined: the EPF0 march does not take the geometry,
+// nothing was launched.
+int LaunchEpf0Then12(jxlhip_ctx* c, const DevFrame& f, const FilterParams& fp, bool fused, bool* declined) {
+  float* dst[3];
+  const size_t plane_floats = (size_t)f.plane_tile_rows * f.tile_stride * 64;
+  for (int ch = 0; ch < 3; ch++) dst[ch] = c->planes2 + ch * plane_floats;
+  const int gab = (int)c->p.lf.gab;
+  *declined = !(fused ? LaunchFusedEpf0(f, fp, gab, dst, c->stream) : LaunchEpf0(f, fp, gab, dst, c->stream));
+  if (*declined) return JXLHIP_OK;
+  ProfMark(c, JXLHIP_KERNEL_EPF0);
+  DevFrame f2 = f;
+  for (int ch = 0; ch < 3; ch++) f2.xyb[ch] = dst[ch];
+  f2.linear_stride = f.tile_stride * 32u;
+  if (!LaunchFiltersFast(f2, fp, 0, 2, (int)c->p.output_kind, c->stream))
+    return Fail(c, JXLHIP_ERR_STATE, "EPF1 + EPF2 march refused a frame the EPF0 march accepted");
   return JXLHIP_OK;
 }
 
@@ -1644,18 +1634,10 @@ int LaunchFiltersRows(jxlhip_ctx* c, const FilterParams& fp, uint32_t fy0, uint3
   f.cell_info = c->cell_info;
   ProfBegin(c);
   if (fused && c->p.lf.epf_iters == 3) {
-    // EPF0 from the producer's slab into the second plane set (k_fused_pc0), EPF1 + EPF2 + output from there
-    float* dst[3];
-    const size_t plane_floats = (size_t)f.plane_tile_rows * f.tile_stride * 64;
-    for (int ch = 0; ch < 3; ch++) dst[ch] = c->planes2 + ch * plane_floats;
-    if (!LaunchFusedEpf0(f, fp, (int)c->p.lf.gab, dst, c->stream))
-      return Fail(c, JXLHIP_ERR_STATE, "fused EPF0 kernel refused a frame FusedEpf0Supported accepted");
-    ProfMark(c, JXLHIP_KERNEL_EPF0);
-    DevFrame f2 = f;
-    for (int ch = 0; ch < 3; ch++) f2.xyb[ch] = dst[ch];
-    f2.linear_stride = f.tile_stride * 32u;
-    if (!LaunchFiltersFast(f2, fp, 0, 2, (int)c->p.output_kind, c->stream))
-      return Fail(c, JXLHIP_ERR_STATE, "EPF1 + EPF2 march refused a frame the fused EPF0 march accepted");
+    bool declined;
+    const int rc = LaunchEpf0Then12(c, f, fp, true, &declined);
+    if (rc) return rc;
+    if (declined) return Fail(c, JXLHIP_ERR_STATE, "fused EPF0 kernel refused a frame FusedEpf0Supported accepted");
     ProfMark(c, JXLHIP_KERNEL_FILTERS);
     ProfEnd(c);
     HIPCHK(c, hipGetLastError());
@@ -1671,18 +1653,10 @@ int LaunchFiltersRows(jxlhip_ctx* c, const FilterParams& fp, uint32_t fy0, uint3
   }
   bool fast = false;
   if (!c->generic_filters && fy1 > fy0 && c->p.lf.epf_iters == 3 && c->planes2) {
-    // EPF0 into the second plane set, EPF1 + EPF2 + output from there
-    float* dst[3];
-    const size_t plane_floats = (size_t)f.plane_tile_rows * f.tile_stride * 64;
-    for (int ch = 0; ch < 3; ch++) dst[ch] = c->planes2 + ch * plane_floats;
-    if (LaunchEpf0(f, fp, (int)c->p.lf.gab, dst, c->stream)) {
-      ProfMark(c, JXLHIP_KERNEL_EPF0);
-      DevFrame f2 = f;
-      for (int ch = 0; ch < 3; ch++) f2.xyb[ch] = dst[ch];
-      f2.linear_stride = f.tile_stride * 32u;
-      fast = LaunchFiltersFast(f2, fp, 0, 2, (int)c->p.output_kind, c->stream);
-      if (!fast) return Fail(c, JXLHIP_ERR_STATE, "EPF1 + EPF2 march refused a frame the EPF0 march accepted");
-    }
+    bool declined;  // (then the generic kernel below)
+    const int rc = LaunchEpf0Then12(c, f, fp, false, &declined);
+    if (rc) return rc;
+    fast = !declined;
   } else if (!c->generic_filters && fy1 > fy0) {
     fast = LaunchFiltersFast(f, fp, (int)c->p.lf.gab, (int)c->p.lf.epf_iters, (int)c->p.output_kind, c->stream);
   }
@@ -1722,14 +1696,14 @@ bool WantFused(const jxlhip_ctx* c) {
     // device kept busy by other frames is bound by traffic: 64.8 -> 67.0 Gpx/s with three in flight
     // (profiles/r04_epf3_fused.txt)
     const bool many = c->concurrency > 1 && (uint64_t)f.xsize * f.ysize >= (6ull << 20);
-    return (c->fuse > 0 || (c->fuse < 0 && many && has_dct8)) && !c->generic_filters && c->band_rows == 0 && c->planes2 &&
+    return (c->fuse > 0 || (c->fuse < 0 && many && has_dct8)) && !c->generic_filters && c->planes2 &&
            f.group_y0 == 0 && f.group_rows == f.ysg && FusedEpf0Supported(f, (int)c->p.lf.gab);
   }
-  return (c->fuse > 0 || (c->fuse < 0 && big && has_dct8 && !packed_fixed)) && !c->generic_filters && c->band_rows == 0 &&
+  return (c->fuse > 0 || (c->fuse < 0 && big && has_dct8 && !packed_fixed)) && !c->generic_filters &&
          FusedSupported(f, (int)c->p.lf.gab, (int)c->p.lf.epf_iters, (int)c->p.output_kind);
 }
 
-int BeginDecode(jxlhip_ctx* c, uint32_t nbands, uint32_t first_block = 0) {
+int BeginDecode(jxlhip_ctx* c) {
   if (!c->have_frame || !c->have_inputs)
     return Fail(c, JXLHIP_ERR_STATE, "decode needs frame_begin + inputs");
   HIPCHK(c, hipSetDevice(c->device));
@@ -1754,19 +1728,6 @@ int BeginDecode(jxlhip_ctx* c, uint32_t nbands, uint32_t first_block = 0) {
     HIPCHK(c, hipEventRecord(c->sp_off_ev[par], st));
     c->sp_off_pending[par] = true;
     LaunchExpandSparse(c->sp_dev, c->sp_off_dev, (int16_t*)c->up_coeffs[0], c->f.group_y0 * c->f.xsg, c->f.group_rows * c->f.xsg, st);
-  }
-  if (nbands > (uint32_t)kMaxBands) nbands = kMaxBands;
-  if (nbands) {
-    hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
-    (void)hipStreamIsCapturing(st, &cap);
-    uint32_t* blocks = c->counts + (size_t)first_block * kCountStride;
-    if (cap == hipStreamCaptureStatusActive) {  // (see LaunchZeroU32: no memset node at the root of a frame graph)
-      LaunchZeroU32(blocks, (uint32_t)(kCountStride * nbands), st);
-      HIPCHK(c, hipGetLastError());
-    } else {
-      HIPCHK(c, hipMemsetAsync(blocks, 0, sizeof(uint32_t) * kCountStride * nbands, st));
-    }
-    if (first_block == 0) c->counts_clean[0] = c->counts_clean[1] = false;  // used by the bands that follow
   }
   return JXLHIP_OK;
 }
@@ -1795,7 +1756,7 @@ int CheckOutArgs(jxlhip_ctx* c, void* out, size_t out_stride, size_t out_plane_s
 int jxlhip_decode_blocks(jxlhip_ctx* c) {
   if (!c) return JXLHIP_ERR_INVALID_ARGUMENT;
   JXLHIP_NO_MULTI(c);
-  int rc = BeginDecode(c, 1);
+  int rc = BeginDecode(c);
   if (rc) return rc;
   // A STRIPE of a frame (what jxlhip_create_multi / libjxl_amd.stripes run per device) takes the fused kernel
   // by the whole-frame rule: its DCT8 blocks are decoded inside the filter march, except that those of its
@@ -1804,7 +1765,7 @@ int jxlhip_decode_blocks(jxlhip_ctx* c) {
   const bool stripe = c->f.group_y0 != 0 || c->f.group_rows != c->f.ysg;
   c->blocks_fused = stripe && WantFused(c);
   if (c->blocks_fused && (rc = Grow(c, &c->cell_info, &c->cell_info_items, (size_t)c->f.xsb * c->f.ysb))) return rc;
-  rc = LaunchBlocksBand(c, c->f.group_y0, c->f.group_y0 + c->f.group_rows, 0, c->blocks_fused ? 2 : 0);
+  rc = LaunchPhase1(c, c->blocks_fused ? 2 : 0);
   if (rc) return rc;
   c->blocks_done = true;
   return JXLHIP_OK;
@@ -1907,10 +1868,7 @@ int jxlhip_stripe_finish(jxlhip_ctx* c, const float* recv_up, const float* recv_
   return jxlhip_decode_filters_rows(c, out, out_stride, out_plane_stride, y_interior_end, c->f.y1);
 }
 
-// Both phases.  With JXLHIP_BAND_ROWS = n > 0 the stripe is walked in bands of n
-// group rows -- blocks(b) then filters(b-1) -- which was meant to keep a band's
-// XYB planes in the 256 MB Infinity Cache; measured on MI355X it only loses
-// time, so the default is one band = the whole stripe.
+// Both phases, each over the whole stripe.
 static int DecodeFrameCoded(jxlhip_ctx* c, void* out, size_t out_stride, size_t out_plane_stride);
 static int DecodeFrameFeatures(jxlhip_ctx* c, void* out, size_t out_stride, size_t out_plane_stride);
 
@@ -1950,31 +1908,8 @@ int jxlhip_decode_frame(jxlhip_ctx* c, void* out, size_t out_stride, size_t out_
 static int DecodeFrameCoded(jxlhip_ctx* c, void* out, size_t out_stride, size_t out_plane_stride) {
   const DevFrame& f = c->f;
   c->blocks_fused = false;
-  uint32_t br = c->band_rows ? (uint32_t)c->band_rows : f.group_rows;
-  while ((f.group_rows + br - 1) / br > (uint32_t)kMaxBands) br++;
-  // one band (the default): the counter blocks 0 / 1 alternate and k_prepare zeroes the next frame's -- no memset launch
-  const uint32_t nbands = (f.group_rows + br - 1) / br;
-  // Under stream capture -- the caller records the frame's launches into a hipGraph and replays it (bench.py's
-  // `graph_replay`: the command processor's ~5-8 us per dependent launch are paid once per graph instead) -- every
-  // replay must find the SAME counter blocks zeroed by a node of the graph itself, and must not touch a block the direct
-  // calls keep a "clean" flag for: captured frames use the blocks from kCaptureBase on (see there).
-  hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
-  (void)hipStreamIsCapturing(c->stream, &cap);
-  const bool capturing = cap == hipStreamCaptureStatusActive;
-  const bool one_band = nbands == 1 && !capturing;
-  const int block0 = capturing ? kCaptureBase : 0;
-  const int slot = one_band ? c->counts_slot : block0;
-  int rc = BeginDecode(c, one_band ? 0 : nbands, (uint32_t)block0);
+  int rc = BeginDecode(c);
   if (rc) return rc;
-  if (one_band && !c->counts_clean[slot])
-    HIPCHK(c, hipMemsetAsync(c->counts + (size_t)slot * kCountStride, 0, sizeof(uint32_t) * kCountStride, c->stream));
-  // From here on block `slot` is in use: whatever happens below (a failed launch after k_prepare ran), it must not be
-  // taken for clean by the next frame.  Block slot ^ 1 becomes clean only when the launches that zero it succeeded.
-  if (one_band) c->counts_clean[slot] = false;
-  auto rotate = [&]() {  // after a successful LaunchBlocksBand(.., slot, .., slot ^ 1)
-    c->counts_clean[slot ^ 1] = true;
-    c->counts_slot = slot ^ 1;
-  };
   rc = CheckOutArgs(c, out, out_stride, out_plane_stride);
   if (rc) return rc;
   FilterParams fp = c->fp;
@@ -1985,13 +1920,12 @@ static int DecodeFrameCoded(jxlhip_ctx* c, void* out, size_t out_stride, size_t 
   // class kernel applies the opsin inverse and writes the pixels itself (kernels_mfma.hip, EMIT) -- no XYB planes,
   // no second kernel.  used_acs is the caller's promise; k_prepare reports any other strategy it meets.
   if (c->mfma != 0 && f.used_acs == (1u << 5) && c->p.lf.gab == 0 && c->p.lf.epf_iters == 0 &&
-      c->p.output_kind == JXLHIP_OUT_LINEAR_RGB_F32 && !c->generic_filters && c->band_rows == 0) {
-    rc = LaunchBlocksBand(c, f.group_y0, f.group_y0 + f.group_rows, slot, 0, &fp, one_band ? slot ^ 1 : -1);
-    if (!rc && one_band) rotate();
+      c->p.output_kind == JXLHIP_OUT_LINEAR_RGB_F32 && !c->generic_filters) {
+    rc = LaunchPhase1(c, 0, &fp);
     c->blocks_done = false;  // nothing in the planes
     return rc;
   }
-  // Whole frame on this context, one band: the fused kernel decodes the DCT8 blocks inside the filter
+  // Whole frame on this context: the fused kernel decodes the DCT8 blocks inside the filter
   // march (kernels_fused.hip).  The split calls (jxlhip_decode_blocks / _filters) stay two-phase: a
   // stripe's halo rows must exist in the planes for its neighbours.
   // auto: with a filter, frames of 12 Mpx and more (see jxlhip_ctx::fuse); without one the fused wave has no
@@ -1999,28 +1933,13 @@ static int DecodeFrameCoded(jxlhip_ctx* c, void* out, size_t out_stride, size_t 
   // frame has no DCT8 block -- then the slab is only a detour (configs[4]: 76.1 vs 79.6 Gpx/s)
   if (WantFused(c) && f.group_y0 == 0 && f.group_rows == f.ysg) {
     if ((rc = Grow(c, &c->cell_info, &c->cell_info_items, (size_t)f.xsb * f.ysb))) return rc;
-    rc = LaunchBlocksBand(c, f.group_y0, f.group_y0 + f.group_rows, slot, 1, nullptr, one_band ? slot ^ 1 : -1);
-    if (rc) return rc;
-    if (one_band) rotate();
+    if ((rc = LaunchPhase1(c, 1))) return rc;
     c->blocks_done = false;  // the planes do not hold the whole frame
     return LaunchFiltersRows(c, fp, f.y0, f.y1, true);
   }
-  const uint32_t g_end = f.group_y0 + f.group_rows;
-  uint32_t prev_y0 = f.y0;
-  int band = 0;
-  for (uint32_t g0 = f.group_y0; g0 < g_end; g0 += br, band++) {
-    const uint32_t g1 = g0 + br < g_end ? g0 + br : g_end;
-    rc = one_band ? LaunchBlocksBand(c, g0, g1, slot, 0, nullptr, slot ^ 1) : LaunchBlocksBand(c, g0, g1, block0 + band);
-    if (rc) return rc;
-    if (one_band) rotate();
-    if (g0 > f.group_y0) {  // rows of the previous band: its lower halo now exists
-      rc = LaunchFiltersRows(c, fp, prev_y0, g0 * 256);
-      if (rc) return rc;
-      prev_y0 = g0 * 256;
-    }
-  }
+  if ((rc = LaunchPhase1(c))) return rc;
   c->blocks_done = true;
-  return LaunchFiltersRows(c, fp, prev_y0, f.y1);
+  return LaunchFiltersRows(c, fp, f.y0, f.y1);
 }
 
 // A frame with splines and / or photon noise (jxlhip_set_splines, jxlhip_set_noise; whole frames, coded orientation):

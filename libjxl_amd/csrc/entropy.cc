@@ -9,8 +9,10 @@
 // I.3.5-I.3.7, as implemented by the reference at the lines cited per function.
 #include "env_switches.h"
 #include <stdlib.h>
+#include <string.h>
 namespace jxlhip_env {
 Switches g;
+// (every switch is read by a getenv call that names it: tests/test_abi.py checks the list in include/jxl_hip.h)
 void LoadLocked() {
   g.wp_general.store(getenv("JXLHIP_WP_GENERAL") != nullptr);
   g.codestream_verbose.store(getenv("JXLHIP_CODESTREAM_VERBOSE") != nullptr);
@@ -19,14 +21,18 @@ void LoadLocked() {
   g.test_range_group.store(e ? atoll(e) : -1);
   const char* ife = getenv("JXLHIP_MULTI_INTERIOR_FIRST");
   g.multi_interior_first.store(!ife || atoi(ife) != 0 ? 1 : 0);
-  auto num = [](const char* name, int unset) {
-    const char* v = getenv(name);
-    return v ? atoi(v) : unset;
-  };
-  g.fused_pc_rh.store(num("JXLHIP_FUSED_PC_RH", 0));
-  g.filter_rh.store(num("JXLHIP_FILTER_RH", 0));
-  g.big_wgs.store(num("JXLHIP_BIG_WGS", Switches::kUnset));
+  auto num = [](const char* v, int unset) { return v ? atoi(v) : unset; };
+  auto force = [](const char* v) { return v ? (atoi(v) != 0 ? 1 : 0) : -1; };  // 0 / 1 forces, -1 = auto
+  g.fused_pc_rh.store(num(getenv("JXLHIP_FUSED_PC_RH"), 0));
+  g.filter_rh.store(num(getenv("JXLHIP_FILTER_RH"), 0));
+  g.big_wgs.store(num(getenv("JXLHIP_BIG_WGS"), Switches::kUnset));
   g.multi_force_gather.store(getenv("JXLHIP_MULTI_FORCE_GATHER") != nullptr);
+  const char* filters = getenv("JXLHIP_FILTERS");
+  g.generic_filters.store(filters && !strcmp(filters, "generic"));
+  g.sparse_upload.store(num(getenv("JXLHIP_SPARSE_UPLOAD"), 1) != 0);
+  g.fuse.store(force(getenv("JXLHIP_FUSE")));
+  g.mfma.store(force(getenv("JXLHIP_MFMA")));
+  g.stage_slots.store(num(getenv("JXLHIP_STAGE_SLOTS"), Switches::kUnset));
   {
     // unparsable / empty / 0: the default (2^30 pixels = four 16K frames' worth), not "refuse every frame"
     const char* mp = getenv("JXLHIP_MAX_PIXELS");

@@ -24,6 +24,12 @@ struct Switches {
   std::atomic<int> big_wgs{kUnset};         // JXLHIP_BIG_WGS: workgroups of the 64-point family in k_transform_r
   std::atomic<bool> multi_force_gather{false};  // JXLHIP_MULTI_FORCE_GATHER: one-device boxes exercise the gather copies
   std::atomic<unsigned long long> max_pixels{1ull << 30};  // JXLHIP_MAX_PIXELS: what jxlhip_decode_codestream allocates for at most
+  // path switches of a context (jxlhip_create_ex copies them into it; see the jxlhip_ctx members of the same names)
+  std::atomic<bool> generic_filters{false};  // JXLHIP_FILTERS=generic
+  std::atomic<bool> sparse_upload{true};     // JXLHIP_SPARSE_UPLOAD=0 turns it off
+  std::atomic<int> fuse{-1};                 // JXLHIP_FUSE=0 / 1 forces (-1: auto)
+  std::atomic<int> mfma{-1};                 // JXLHIP_MFMA=0 / 1 forces (-1: auto)
+  std::atomic<int> stage_slots{kUnset};      // JXLHIP_STAGE_SLOTS: pinned staging slots per context
   std::mutex mu;
 };
 extern Switches g;  // defined in entropy.cc

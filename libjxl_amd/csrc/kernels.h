@@ -46,11 +46,11 @@ struct FilterParams {
 
 void LaunchPrepare(const DevFrame& f, const WorkLists& wl, int with_sigma, float epf_quant_mul,
                    const SharpLut& lut, hipStream_t st);
-// Five launches (k_dct8, the row-per-lane families R16 / R32, family A, the large kinds) on
-// streams[0] / streams[1 % nstreams]; `cells` = block cells of the band (bounds the unit count).
-// emit: see LaunchMfma32 (nullptr: every class writes the XYB planes).
+// The transform kernels (k_transform_8, the row-per-lane families R16 / R32 or their merged k_transform_r, family A,
+// the matrix-core classes, the large kinds), back to back on `st`; `cells` = block cells of the stripe (bounds the
+// unit count).  emit: see LaunchMfma32 (nullptr: every class writes the XYB planes).
 void LaunchBlocks(const DevFrame& f, const WorkLists& wl, uint32_t cells, const float* wc,
-                  const float* resample, hipStream_t* streams, int nstreams, const FilterParams* emit = nullptr);
+                  const float* resample, hipStream_t st, const FilterParams* emit = nullptr);
 // Returns 0, or -1 when the (gab, epf_iters, output_kind) combination is invalid.
 int LaunchFilters(const DevFrame& f, const FilterParams& p, int gab, int epf_iters,
                   int output_kind, hipStream_t st);

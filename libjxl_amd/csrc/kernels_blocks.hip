@@ -1739,7 +1739,7 @@ __global__ __launch_bounds__(256, sizeof(CT) == 2 ? 3 : 2) void k_transform_r(De
 // --------------------------------------------------------------- launchers
 template <typename CT>
 static void LaunchBlocksT(const DevFrame& f, const WorkLists& wl, uint32_t cells, const float* wc,
-                          const float* resample, hipStream_t* streams, int nstreams, const FilterParams* emit) {
+                          const float* resample, hipStream_t st, const FilterParams* emit) {
   const uint32_t units = cells / 64;
   const uint32_t grid_l = cells / 128 < 512u ? (cells / 128 ? cells / 128 : 1) : 512u;
   constexpr uint32_t kDct8PerWg = Dct8Geom<CT>::kPerWg;
@@ -1747,14 +1747,11 @@ static void LaunchBlocksT(const DevFrame& f, const WorkLists& wl, uint32_t cells
   const uint32_t grid_a = units + 3 < 1536u ? units + 3 : 1536u;
   const uint32_t grid_r16 = units + 3 < 4096u ? units + 3 : 4096u;
   const uint32_t grid_r32 = units / 2 + 5 < 3072u ? units / 2 + 5 : 3072u;  // units of 128 blocks
-  // With two streams the latency-bound family A (a few hundred long 64x64 / 64x32 units and the
-  // special 8x8 kinds, LDS-heavy, low occupancy) runs beside the LDS-free bandwidth-bound k_dct8.
-  hipStream_t s0 = streams[0], s1 = streams[1 % nstreams];
   // used_acs (when the caller knows it) says which families have work at all
   auto any = [&](std::initializer_list<int> strategies) {
     if (f.used_acs == 0) return true;
-    for (int st : strategies)
-      if (f.used_acs & (1u << st)) return true;
+    for (int s : strategies)
+      if (f.used_acs & (1u << s)) return true;
     return false;
   };
   const bool need_r16 = any({6, 7}) || (!f.mfma16 && any({4}));
@@ -1764,7 +1761,7 @@ static void LaunchBlocksT(const DevFrame& f, const WorkLists& wl, uint32_t cells
   bool specials_in_r = false, dct8_in_r = false;
   uint32_t grid_specials = 0, grid_dct8 = 0;
   if (have_big && !merged_r)
-    hipLaunchKernelGGL((k_transform_a<CT>), dim3(grid_a), dim3(192), 0, s1, f, wl);
+    hipLaunchKernelGGL((k_transform_a<CT>), dim3(grid_a), dim3(192), 0, st, f, wl);
   {
     // worst cases: all cells special (3 tasks per 64 blocks, 4 tasks per workgroup) or all DCT8
     const bool specials = any({1, 2, 3, 12, 13, 14, 15, 16, 17});
@@ -1779,7 +1776,7 @@ static void LaunchBlocksT(const DevFrame& f, const WorkLists& wl, uint32_t cells
     dct8_in_r = merged_r && bound_8 != 0;
     grid_specials = bound_s + kNumSpecial;
     grid_dct8 = bound_8;
-    if (grid_8 && !merged_r) hipLaunchKernelGGL((k_transform_8<CT>), dim3(grid_8), dim3(256), 0, s0, f, wl);
+    if (grid_8 && !merged_r) hipLaunchKernelGGL((k_transform_8<CT>), dim3(grid_8), dim3(256), 0, st, f, wl);
   }
   if (merged_r) {  // -10 us per 8K d1.0 frame against two launches, -15 us more with family A inside
     uint32_t big_cap = 512u;
@@ -1791,40 +1788,38 @@ static void LaunchBlocksT(const DevFrame& f, const WorkLists& wl, uint32_t cells
     // (round 6, again: the 16-point classes in a launch of their own -- 93 VGPRs, no LDS, five waves per SIMD, where inside
     // this launch they run at three: all-DCT16X16 frames 159 against 115 us -- cost 9 us more per frame on both the d1 mix
     // and genuine-content shares, profiles/r06_transform_overread.txt; the single launch stays)
-    hipLaunchKernelGGL((k_transform_r<CT>), dim3(special_wgs + big_wgs + grid_r16 + dct8_wgs), dim3(256), 0, s0, f, wl,
+    hipLaunchKernelGGL((k_transform_r<CT>), dim3(special_wgs + big_wgs + grid_r16 + dct8_wgs), dim3(256), 0, st, f, wl,
                        big_wgs, special_wgs, grid_r16, dct8_wgs);
   } else {
-    if (need_r16) hipLaunchKernelGGL((k_transform_r16<CT>), dim3(grid_r16), dim3(256), 0, s0, f, wl);
-    if (need_r32) hipLaunchKernelGGL((k_transform_r32<CT>), dim3(grid_r32), dim3(256), 0, s0, f, wl);
+    if (need_r16) hipLaunchKernelGGL((k_transform_r16<CT>), dim3(grid_r16), dim3(256), 0, st, f, wl);
+    if (need_r32) hipLaunchKernelGGL((k_transform_r32<CT>), dim3(grid_r32), dim3(256), 0, st, f, wl);
   }
-  if (f.mfma32 && any({5})) LaunchMfma32(f, wl, cells, s1, emit);
-  if (f.mfma16 && any({4})) LaunchMfma16(f, wl, cells, s1);
+  if (f.mfma32 && any({5})) LaunchMfma32(f, wl, cells, st, emit);
+  if (f.mfma16 && any({4})) LaunchMfma16(f, wl, cells, st);
   if (cells >= 256 && any({21, 22, 23, 24, 25, 26}))
-    hipLaunchKernelGGL(k_large<CT>, dim3(grid_l), dim3(256), 0, s1, f, wl.list[kClsLarge],
+    hipLaunchKernelGGL(k_large<CT>, dim3(grid_l), dim3(256), 0, st, f, wl.list[kClsLarge],
                        wl.count + kClsLarge * kCounterPad, wc, resample);
 }
 
 void LaunchPrepare(const DevFrame& f, const WorkLists& wl, int with_sigma, float epf_quant_mul,
                    const SharpLut& lut, hipStream_t st) {
-  // lists for the band's group rows; sigma additionally for the group row just
-  // outside the STRIPE when the band touches its first / last row (the EPF
-  // stages evaluate halo rows there; inside the stripe the neighbouring bands
-  // provide their own sigma before any filter launch needs it)
+  // lists for the stripe's group rows [band_g0, band_g1); sigma additionally for the group row just outside the
+  // stripe on either side, where the frame has one (the EPF stages evaluate halo rows there)
   uint32_t lo = f.band_g0, hi = f.band_g1;
   if (with_sigma) {
-    if (lo == f.group_y0 && lo > 0) lo--;
-    if (hi == f.group_y0 + f.group_rows && hi < f.ysg) hi++;
+    if (lo > 0) lo--;
+    if (hi < f.ysg) hi++;
   }
   hipLaunchKernelGGL(k_prepare, dim3(f.xsg * (hi - lo)), dim3(1024), 0, st, f, wl, lo,
                      with_sigma, epf_quant_mul, lut);
 }
 
 void LaunchBlocks(const DevFrame& f, const WorkLists& wl, uint32_t cells, const float* wc,
-                  const float* resample, hipStream_t* streams, int nstreams, const FilterParams* emit) {
+                  const float* resample, hipStream_t st, const FilterParams* emit) {
   if (f.coeff_type == JXLHIP_COEFF_I16)
-    LaunchBlocksT<int16_t>(f, wl, cells, wc, resample, streams, nstreams, emit);
+    LaunchBlocksT<int16_t>(f, wl, cells, wc, resample, st, emit);
   else
-    LaunchBlocksT<int32_t>(f, wl, cells, wc, resample, streams, nstreams, emit);
+    LaunchBlocksT<int32_t>(f, wl, cells, wc, resample, st, emit);
 }
 
 }  // namespace jxlhip

@@ -79,3 +79,19 @@ def test_product_never_imports_oracle():
                 text = open(os.path.join(dirpath, f)).read()
                 assert not re.search(r"^\s*(import|from)\s+oracle\b", text, re.M), f
                 assert "jxl_oracle.h" not in text and "libjxl_oracle" not in text, f
+
+
+def test_header_lists_every_environment_switch():
+    """jxlhip_debug_reload_env's comment in include/jxl_hip.h names exactly the switches the library reads: the
+    getenv("JXLHIP_...") calls under libjxl_amd/csrc/ (all of them in env_switches.h's LoadLocked)."""
+    csrc = os.path.join(ROOT, "libjxl_amd", "csrc")
+    read = set()
+    for f in os.listdir(csrc):
+        if f.endswith((".hip", ".h", ".cc", ".inc")):
+            read |= set(re.findall(r'getenv\(\s*"(JXLHIP_\w+)"', open(os.path.join(csrc, f)).read()))
+    header = open(os.path.join(ROOT, "include", "jxl_hip.h")).read()
+    m = re.search(r"/\*((?:(?!/\*).)*?)\*/\s*JXLHIP_EXPORT void jxlhip_debug_reload_env\b", header, re.S)
+    assert m, "no comment in front of jxlhip_debug_reload_env"
+    listed = set(re.findall(r"\bJXLHIP_[A-Z0-9_]+\b", m.group(1)))
+    assert len(read) >= 10
+    assert listed == read, (sorted(listed - read), sorted(read - listed))

@@ -353,6 +353,56 @@ def test_graph_replays_interleaved_with_direct_calls_on_one_stream(dq, oracle, f
 
 
 @pytest.mark.parametrize("fuse", ["1", "0"])
+def test_split_call_graph_replays_interleaved_with_direct_calls(dq, oracle, fuse, monkeypatch):
+    """The same for the split calls: jxlhip_decode_blocks + jxlhip_decode_filters of a whole frame captured into a graph,
+    its replays interleaved with direct decode_frame calls and direct split calls on the SAME stream.  Every phase 1
+    takes its counter block from one rule (context.hip: LaunchPhase1): a captured jxlhip_decode_blocks uses the capture
+    block too, so a replay never dirties the blocks the direct calls keep "clean" flags for (round 6 captured it on
+    block 0).  Every frame must be the same pixels, and the stream must report no fault."""
+    monkeypatch.setenv("JXLHIP_FUSE", fuse)
+    params, t, fr = frames.make_case(1000, 520, mix=synth.MIX_D1, gab=True, epf_iters=1, seed=63)
+    cs = torch.cuda.Stream()
+    cs.wait_stream(torch.cuda.current_stream())
+    with torch.cuda.stream(cs):
+        d = VarDctDecoder(0)  # bound to cs for its whole life
+        d.begin_frame(params)
+        d.set_inputs(to_dev(t), dq)
+        out = d.alloc_output()
+        want = d.decode_frame().clone()
+        d.decode_blocks()
+        d.decode_filters(out)
+        d.sync()
+    assert torch.equal(out, want)
+    assert rel_err(want.cpu().numpy(), fr.decode(threads=4)) <= TIGHT
+    g = torch.cuda.CUDAGraph()
+    with torch.cuda.graph(g, stream=cs):
+        d.decode_blocks()
+        d.decode_filters(out)
+
+    def split(o):
+        d.decode_blocks()
+        d.decode_filters(o)
+
+    with torch.cuda.stream(cs):
+        for round_ in range(3):
+            for i in range(2 + round_):  # both alternating blocks used and re-zeroed, by both kinds of direct call
+                out.zero_()
+                (d.decode_frame if (i + round_) % 2 == 0 else split)(out)
+                d.sync()
+                assert torch.equal(out, want), ("direct", round_, i)
+            out.zero_()
+            g.replay()
+            d.sync()
+            assert torch.equal(out, want), ("replay", round_)
+        for call in (split, d.decode_frame):
+            out.zero_()
+            call(out)
+            d.sync()
+            assert torch.equal(out, want), call
+    d.close()
+
+
+@pytest.mark.parametrize("fuse", ["1", "0"])
 @pytest.mark.parametrize("gab,epf,interior", [(1, 1, True), (1, 2, False), (1, 3, False), (0, 0, True)])
 def test_stripe_step_in_three_calls_equals_whole_frame(dq, oracle, gab, epf, interior, fuse, monkeypatch):
     """jxlhip_stripe_begin (phase 1 + both exports) / jxlhip_decode_filters_rows (the interior) / jxlhip_stripe_finish
