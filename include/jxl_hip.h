@@ -232,8 +232,8 @@ JXLHIP_EXPORT void jxlhip_destroy(jxlhip_ctx* ctx);
 JXLHIP_EXPORT const char* jxlhip_last_error(const jxlhip_ctx* ctx);
 /* The library samples its debug / test switches (JXLHIP_WP_GENERAL, JXLHIP_CODESTREAM_VERBOSE, JXLHIP_NO_PIPELINE,
  * JXLHIP_TEST_RANGE_GROUP, JXLHIP_MULTI_INTERIOR_FIRST, JXLHIP_MULTI_FORCE_GATHER, JXLHIP_MAX_PIXELS, the kernels'
- * launch-geometry knobs JXLHIP_FUSED_PC_RH, JXLHIP_FILTER_RH, JXLHIP_BIG_WGS, and the path switches JXLHIP_FILTERS,
- * JXLHIP_SPARSE_UPLOAD, JXLHIP_FUSE, JXLHIP_MFMA, JXLHIP_STAGE_SLOTS) from the environment when a context is created
+ * launch-geometry knobs JXLHIP_FUSED_PC_RH, JXLHIP_FILTER_RH, JXLHIP_BIG_WGS, JXLHIP_R_WGS, and the path switches
+ * JXLHIP_FILTERS, JXLHIP_SPARSE_UPLOAD, JXLHIP_FUSE, JXLHIP_MFMA, JXLHIP_STAGE_SLOTS) from the environment when a context is created
  * (jxlhip_create / _ex / _multi) and at their first use before that; a test that changes one of them under a live
  * context calls this to have them read again (the path switches stay as a context was created with them).  Decoding
  * and kernel launches never call getenv (no reference counterpart: libjxl has no run-time switches on this path). */

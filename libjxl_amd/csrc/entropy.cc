@@ -26,6 +26,7 @@ void LoadLocked() {
   g.fused_pc_rh.store(num(getenv("JXLHIP_FUSED_PC_RH"), 0));
   g.filter_rh.store(num(getenv("JXLHIP_FILTER_RH"), 0));
   g.big_wgs.store(num(getenv("JXLHIP_BIG_WGS"), Switches::kUnset));
+  g.r_wgs.store(num(getenv("JXLHIP_R_WGS"), Switches::kUnset));
   g.multi_force_gather.store(getenv("JXLHIP_MULTI_FORCE_GATHER") != nullptr);
   const char* filters = getenv("JXLHIP_FILTERS");
   g.generic_filters.store(filters && !strcmp(filters, "generic"));

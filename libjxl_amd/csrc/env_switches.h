@@ -21,7 +21,8 @@ struct Switches {
   static constexpr int kUnset = -2147483647 - 1;
   std::atomic<int> fused_pc_rh{0};          // JXLHIP_FUSED_PC_RH: rows per window chunk (0 = fill the device)
   std::atomic<int> filter_rh{0};            // JXLHIP_FILTER_RH: rows per wave of the two-phase filter march (0 = fill the device)
-  std::atomic<int> big_wgs{kUnset};         // JXLHIP_BIG_WGS: workgroups of the 64-point family in k_transform_r
+  std::atomic<int> big_wgs{kUnset};         // JXLHIP_BIG_WGS: workgroups of the 64-point family (k_transform_r, k_transform_a)
+  std::atomic<int> r_wgs{kUnset};           // JXLHIP_R_WGS: workgroups of the row-per-lane families (k_transform_r, _r16, _r32)
   std::atomic<bool> multi_force_gather{false};  // JXLHIP_MULTI_FORCE_GATHER: one-device boxes exercise the gather copies
   std::atomic<unsigned long long> max_pixels{1ull << 30};  // JXLHIP_MAX_PIXELS: what jxlhip_decode_codestream allocates for at most
   // path switches of a context (jxlhip_create_ex copies them into it; see the jxlhip_ctx members of the same names)

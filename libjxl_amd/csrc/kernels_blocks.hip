@@ -1128,9 +1128,9 @@ __device__ __forceinline__ void MediumUnit(const DevFrame& f, const WorkItem* __
 // profiles/r06_medium_timing.txt) the two IDCT passes are 3 % of a varblock's time, the load phase 52 % and the store
 // phase 39 % -- a wave's vmcnt counter retires loads AND stores in issue order, so the loads of varblock k + 1, issued
 // behind the 16 KB of stores of varblock k, are only "there" when those stores have drained.  Here a workgroup walks its
-// varblocks itself (one varblock per task, whatever the class) and requests varblock k + 1's coefficient rows, dequant
-// table vectors and DC column -- 116 registers that nothing else needs at that point -- BETWEEN varblock k's second pass
-// and its stores: they travel during the store phase, and waiting for them does not wait for the stores behind them.
+// varblocks itself (one varblock per task, whatever the class) and requests varblock k + 1's coefficient rows and DC
+// column (APrefetch: 44 registers; the dequant table vectors are read when AHead dequantises) BETWEEN varblock k's second
+// pass and its stores: they travel during the store phase, and waiting for them does not wait for the stores behind them.
 // 16-bit coefficients only (32-bit rows would be 72 registers more: MediumUnit keeps those frames).
 struct APrefetch {
   uint2 x[6], y[6], b[6];     // the thread's 4 coefficients per step and channel (6 steps of 768 for 64x64, 3 for the halves)
@@ -1744,9 +1744,19 @@ static void LaunchBlocksT(const DevFrame& f, const WorkLists& wl, uint32_t cells
   const uint32_t grid_l = cells / 128 < 512u ? (cells / 128 ? cells / 128 : 1) : 512u;
   constexpr uint32_t kDct8PerWg = Dct8Geom<CT>::kPerWg;
   // caps: residency of the kernel (workgroups per CU by LDS / registers) x 256 CUs x 2 generations
-  const uint32_t grid_a = units + 3 < 1536u ? units + 3 : 1536u;
-  const uint32_t grid_r16 = units + 3 < 4096u ? units + 3 : 4096u;
-  const uint32_t grid_r32 = units / 2 + 5 < 3072u ? units / 2 + 5 : 3072u;  // units of 128 blocks
+  uint32_t grid_a = units + 3 < 1536u ? units + 3 : 1536u;
+  uint32_t grid_r16 = units + 3 < 4096u ? units + 3 : 4096u;
+  uint32_t grid_r32 = units / 2 + 5 < 3072u ? units / 2 + 5 : 3072u;  // units of 128 blocks
+  // experiments and tests/test_gpu_phase1_loops.py: fewer workgroups for the 64-point family (JXLHIP_BIG_WGS) or the
+  // row-per-lane families (JXLHIP_R_WGS), so that each one walks many units (anything outside [1, 4096]: the built-in caps)
+  const int big_env = jxlhip_env::Get().big_wgs.load(std::memory_order_relaxed);
+  const int r_env = jxlhip_env::Get().r_wgs.load(std::memory_order_relaxed);
+  const bool big_set = big_env >= 1 && big_env <= 4096;
+  if (big_set && (uint32_t)big_env < grid_a) grid_a = (uint32_t)big_env;
+  if (r_env >= 1 && r_env <= 4096) {
+    if ((uint32_t)r_env < grid_r16) grid_r16 = (uint32_t)r_env;
+    if ((uint32_t)r_env < grid_r32) grid_r32 = (uint32_t)r_env;
+  }
   // used_acs (when the caller knows it) says which families have work at all
   auto any = [&](std::initializer_list<int> strategies) {
     if (f.used_acs == 0) return true;
@@ -1779,9 +1789,7 @@ static void LaunchBlocksT(const DevFrame& f, const WorkLists& wl, uint32_t cells
     if (grid_8 && !merged_r) hipLaunchKernelGGL((k_transform_8<CT>), dim3(grid_8), dim3(256), 0, st, f, wl);
   }
   if (merged_r) {  // -10 us per 8K d1.0 frame against two launches, -15 us more with family A inside
-    uint32_t big_cap = 512u;
-    const int big_env = jxlhip_env::Get().big_wgs.load(std::memory_order_relaxed);  // experiments: workgroups of the 64-point family
-    if (big_env >= 1 && big_env <= 4096) big_cap = (uint32_t)big_env;  // (anything else: the built-in cap)
+    const uint32_t big_cap = big_set ? (uint32_t)big_env : 512u;
     const uint32_t big_wgs = have_big ? (grid_a < big_cap ? grid_a : big_cap) : 0u;
     const uint32_t special_wgs = specials_in_r ? grid_specials : 0u;
     const uint32_t dct8_wgs = dct8_in_r ? grid_dct8 : 0u;
