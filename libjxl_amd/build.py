@@ -14,10 +14,12 @@ FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=o
          # the gfx950 code objects travel zstd-compressed inside the fat binary (the HIP runtime unpacks them when the
          # library is loaded: measured on the GPU box, profiles/r06_library_size.txt): 12.1 -> ~4 MB
          "--offload-compress"]
-LIB_SOURCES = ["context.hip", "kernels_blocks.hip", "kernels_filters.hip", "kernels_filters_fast.hip", "kernels_filters_fast_b.hip", "kernels_filters_fast_c.hip",
-               "kernels_filters_fast_d.hip",
-               "kernels_fused.hip", "kernels_fused_epf0.hip", "kernels_mfma.hip", "kernels_epf0.hip", "kernels_tables.hip", "kernels_noise.hip", "kernels_splines.hip",
-               "entropy.cc"]
+# (the units that compile longest come first: the pool starts them in this order)
+LIB_SOURCES = ["kernels_fused.hip", "kernels_filters_fast_general.hip", "kernels_filters_fast_general_epf2.hip",
+               "kernels_filters_fast_fp.hip", "kernels_filters_fast_be16.hip", "kernels_filters_fast_int.hip",
+               "kernels_blocks.hip", "kernels_filters_fast.hip", "kernels_fused_epf0.hip", "entropy.cc", "context.hip",
+               "kernels_filters.hip", "kernels_mfma.hip", "kernels_epf0.hip", "kernels_tables.hip", "kernels_noise.hip",
+               "kernels_splines.hip"]
 RUNNER_SOURCES = ["runner.cc"]
 # Per-file flags.  kernels_blocks.hip: the SLP vectoriser pairs the butterflies of the in-register IDCTs into packed
 # fp32 operations (v_pk_fma / v_pk_add / v_pk_mul on aligned register PAIRS, stitched together with v_mov): the pairs
@@ -26,8 +28,6 @@ RUNNER_SOURCES = ["runner.cc"]
 # 113 to 93 (five waves per SIMD), and a packed instruction holds the SIMD ~1.6x as long as a plain one anyway
 # (tools/probes/valu_issue.hip).  Explicit vector types (filters_march.h) are not affected.
 EXTRA_FLAGS = {"kernels_blocks.hip": ["-fno-slp-vectorize"]}
-if os.environ.get("JXLHIP_BUILD_NO_SLP_ALL"):  # experiment builds
-    EXTRA_FLAGS = {k: ["-fno-slp-vectorize"] for k in LIB_SOURCES if k.endswith(".hip")}
 
 
 def _deps():
@@ -49,10 +49,7 @@ def _stale(target, sources):
 def _compile(src):
     obj = os.path.join(BUILD, os.path.splitext(src)[0] + ".o")
     path = os.path.join(CSRC, src)
-    extra = [os.path.join(CSRC, "kernels_fused.hip")] if src == "kernels_fused_epf0.hip" else []  # it #includes it
-    if src.startswith("kernels_filters_fast_"):
-        extra = [os.path.join(CSRC, "kernels_filters_fast.hip")]
-    if _stale(obj, [path] + extra + _deps() + [os.path.abspath(__file__)]):
+    if _stale(obj, [path] + _deps() + [os.path.abspath(__file__)]):
         lang = ["-x", "hip"] if src.endswith(".hip") else []
         cmd = [HIPCC] + FLAGS + EXTRA_FLAGS.get(src, []) + lang + ["-c", path, "-o", obj]
         r = subprocess.run(cmd, capture_output=True, text=True)
@@ -176,7 +173,7 @@ def build(verbose=False):
     have_runner = all(os.path.exists(os.path.join(CSRC, s)) for s in RUNNER_SOURCES)
     if have_runner:
         srcs += RUNNER_SOURCES
-    with ThreadPoolExecutor(max_workers=6) as ex:
+    with ThreadPoolExecutor(max_workers=min(16, os.cpu_count() or 6)) as ex:
         objs = dict(zip(srcs, ex.map(_compile, srcs)))
     lib = _link(os.path.join(CSRC, "libjxl_hip.so"), [objs[s] for s in LIB_SOURCES])
     check_no_scratch(lib)

@@ -1,5 +1,5 @@
 // epf0_march.h -- [Gaborish] + EPF0 as a register row march (stage_epf.cc:54-193): the per-row step shared by
-// k_epf0 (kernels_epf0.hip: rows from the XYB planes) and k_fused_pc0 (kernels_fused.hip, part 3: rows from the LDS
+// k_epf0 (kernels_epf0.hip: rows from the XYB planes) and k_fused_pc0 (kernels_fused_epf0.hip: rows from the LDS
 // slab a producing wave fills, DCT8 cells decoded in the wave).  See kernels_epf0.hip for the regrouping of the
 // reference's twelve 15-term SADs into six plus-sums per pixel.
 #ifndef JXLHIP_EPF0_MARCH_H_

@@ -1,7 +1,7 @@
-// filters_march.h -- the register row march shared by the phase-2 kernel (kernels_filters_fast.hip:
-// rows come from the block-major XYB planes) and the fused kernel (kernels_fused.hip: rows come from a
-// per-wave LDS slab that the wave fills from the coefficient stream).  See kernels_filters_fast.hip
-// for the design notes.
+// filters_march.h -- the register row march shared by the phase-2 kernel (filters_fast.h: rows come
+// from the block-major XYB planes) and the fused kernel (kernels_fused.hip: rows come from a per-wave
+// LDS slab that a producing wave fills from the coefficient stream).  See filters_fast.h for the
+// design notes.
 #ifndef JXLHIP_FILTERS_MARCH_H_
 #define JXLHIP_FILTERS_MARCH_H_
 
@@ -365,8 +365,6 @@ __device__ __forceinline__ void EmitPair(const v2f* v, Lane& L, int gy, char* ou
 // One row step.  PH = (r - r_first) & 3 is the ring slot of input row r.
 // Row bookkeeping: q = row leaving Gaborish (r-1 with GAB, r without),
 // p = q-1 = row whose plus-sums are completed, o = q-2 = EPF output row.
-// DBG: JXLHIP_DEBUG ablation bits of this kernel, compiled in only for the launch that asks for
-// them (4: no output stores, 8: input rows stay in L1).
 //
 // KNOWN (fused kernel's marching wave, SRC_LDS, kernels_fused.hip MarchPC): what the caller knows about this step at
 // COMPILE time.  A wave issues one instruction of any kind per ~5 cycles (tools/probes/valu_issue.hip), and the
@@ -379,7 +377,7 @@ __device__ __forceinline__ void EmitPair(const v2f* v, Lane& L, int gy, char* ou
 //   kStepFirst      (with kStepInterior) the first whole group of the chunk: EPF == 2 picks up the inv_sigma of the
 //                   block row above for the one row of it that the third stage reads
 enum StepKnown : int { kStepGeneric = 0, kStepInterior = 1, kStepEmit = 2, kStepFirst = 4 };
-template <int GAB, int EPF, int OUTK, int FMT, int PH, bool EDGE, int DBG, int SRC = SRC_PLANES, int KNOWN = kStepGeneric>
+template <int GAB, int EPF, int OUTK, int FMT, int PH, bool EDGE, int SRC = SRC_PLANES, int KNOWN = kStepGeneric>
 __device__ __forceinline__ void Step(State& s, int r, const DevFrame& f, const FilterParams& P,
                                      Lane& L, int prefetch_last_row, int y_begin, int y_end,
                                      float& inv_sigma_blk, float& inv_sigma_blk2, char* out_row, const XybConsts& K,
@@ -405,7 +403,6 @@ __device__ __forceinline__ void Step(State& s, int r, const DevFrame& f, const F
     for (int b = 0; b < kBurst; b++) {
       int pr = r + kAhead + b;
       pr = pr > prefetch_last_row ? prefetch_last_row : pr;
-      if constexpr (DBG & 8) pr = y_begin + (pr & 7);  // ablation: reads stay in L1
       const uint32_t off = SrcRowOffset<SRC>(f, Mirror1(pr, H));
 #pragma unroll
       for (int c = 0; c < 3; c++) s.x[c][(PH + kAhead + b) & 7] = LoadPair<EDGE>((const char*)f.xyb[c] + off, L);
@@ -572,7 +569,7 @@ __device__ __forceinline__ void Step(State& s, int r, const DevFrame& f, const F
     for (int c = 0; c < 3; c++) outv[c] = gq[c];
   }
   // 4. emit
-  if (((KNOWN & kStepInterior) ? (KNOWN & kStepEmit) != 0 : (o >= y_begin && o < y_end)) && !((DBG & 4) && outv[0].x != 12345.678f)) {
+  if ((KNOWN & kStepInterior) ? (KNOWN & kStepEmit) != 0 : (o >= y_begin && o < y_end)) {
     EmitPair<OUTK, FMT, EDGE>(outv, L, o, out_row, P, K);
   }
 }

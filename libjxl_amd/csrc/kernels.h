@@ -24,8 +24,8 @@ struct FilterParams {
   float opsin_bias[3];   // OpsinParams::opsin_biases
   float cbrt_bias[3];    // cbrt(opsin_biases)
   float minv[9];         // inverse opsin matrix * 255/intensity_target
-  float xyb_bias[6];     // -cbrt_bias[0..2], opsin_bias[0..2] (kernels_filters_fast.hip)
-  float mcol[3][4];      // its columns, wrapped: (m[j], m[3+j], m[6+j], m[j]) (kernels_filters_fast.hip)
+  float xyb_bias[6];     // -cbrt_bias[0..2], opsin_bias[0..2] (filters_march.h)
+  float mcol[3][4];      // its columns, wrapped: (m[j], m[3+j], m[6+j], m[j]) (filters_march.h)
   void* out;
   size_t out_stride;        // RGB / packed: bytes per row; XYB: floats per row
   size_t out_plane_stride;  // XYB only
@@ -99,6 +99,24 @@ bool LaunchFusedEpf0(const DevFrame& f, const FilterParams& p, int gab, float* c
 // compute units of the device the calling thread has current (hipDeviceAttributeMultiprocessorCount, cached): what the
 // generation-filling launch geometries are sized from (256 on a whole MI355X, fewer on a CPX / DPX partition)
 unsigned DeviceCus();
+// Rows per chunk of a row march whose launch is `wgx` columns of workgroups over `rows` rows, `resident` of them on
+// the device at a time.  Every workgroup costs its chunk height plus `overhead` row steps and all of a launch take
+// the same time, so the launch runs in ceil(workgroups / resident) generations: the height among first, first + step,
+// .. last that minimises generations * cost instead of leaving a mostly empty last generation (the lowest on a tie).
+inline int ChunkRows(unsigned wgx, unsigned rows, unsigned resident, int first, int last, int step, int overhead) {
+  int best = 64;
+  double best_cost = 1e30;
+  for (int rh = first; rh <= last; rh += step) {
+    const unsigned wgs = wgx * ((rows + rh - 1) / rh);
+    const unsigned gens = (wgs + resident - 1) / resident;
+    const double cost = (double)gens * (rh + overhead);
+    if (cost < best_cost) {
+      best_cost = cost;
+      best = rh;
+    }
+  }
+  return best;
+}
 
 // Photon noise (kernels_noise.hip).  The fill sequence of a group's generator is cut into segments of kNoiseSegFills
 // fills; kNoiseSegs segments cover the longest one (3 planes x 256 rows x 16 fills).

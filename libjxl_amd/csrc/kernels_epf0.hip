@@ -11,7 +11,7 @@
 // exactly the reference's border rule for the stage after EPF0 (simple_render_pipeline.cc:129-164).
 //
 // EPF0 (stage_epf.cc:54-193): 12 neighbours (the 5x5 "plus": |dy| + |dx| <= 2), each weighted by a
-// 5-pixel plus-shaped SAD over the three channels.  As in the EPF1 march (kernels_filters_fast.hip) the
+// 5-pixel plus-shaped SAD over the three channels.  As in the EPF1 march (filters_fast.h) the
 // sums are regrouped: with the six channel-summed difference images
 //     V1(y,x) = S |p(y,x) - p(y-1,x)|     V2: (y-2,x)     H1: (y,x-1)     H2: (y,x-2)
 //     A (y,x) = S |p(y,x) - p(y-1,x-1)|   B : (y-1,x+1)           S = sum_c scale_c
@@ -122,23 +122,6 @@ __global__ __launch_bounds__(256, 2) void k_epf0(DevFrame f, FilterParams P, int
   else March0<GAB, false>(f, P, L, y_begin, y_end, dst);
 }
 
-// see FilterRowsPerWave (kernels_filters_fast.hip); two workgroups per CU
-int Epf0RowsPerWave(unsigned wgx, unsigned rows, int hx) {
-  const unsigned resident = DeviceCus() * 2u;
-  int best = 64;
-  double best_cost = 1e30;
-  for (int rh = 16; rh <= 512; rh++) {
-    const unsigned wgs = wgx * ((rows + rh - 1) / rh);
-    const unsigned gens = (wgs + resident - 1) / resident;
-    const double cost = (double)gens * (rh + 2 * hx + 6);
-    if (cost < best_cost) {
-      best_cost = cost;
-      best = rh;
-    }
-  }
-  return best;
-}
-
 }  // namespace
 
 // [Gaborish] + EPF0 for the rows the following EPF1 + EPF2 march of rows [f.fy0, f.fy1) reads
@@ -152,7 +135,7 @@ bool LaunchEpf0(const DevFrame& f, const FilterParams& p, int gab, float* const 
   constexpr int USE = Geom0<1>::USE;
   const unsigned strips = (f.xsize + USE - 1) / USE;
   const unsigned wgx = (strips + 3) / 4;
-  const int RH = Epf0RowsPerWave(wgx, oy1 - oy0, 3 + gab);
+  const int RH = ChunkRows(wgx, oy1 - oy0, DeviceCus() * 2u, 16, 512, 1, 2 * (3 + gab) + 6);  // two workgroups per CU
   const dim3 grid(wgx, (oy1 - oy0 + RH - 1) / RH);
   if (gab) hipLaunchKernelGGL((k_epf0<1>), grid, dim3(256), 0, st, f, p, RH, oy0, oy1, dst[0], dst[1], dst[2]);
   else hipLaunchKernelGGL((k_epf0<0>), grid, dim3(256), 0, st, f, p, RH, oy0, oy1, dst[0], dst[1], dst[2]);

@@ -669,7 +669,7 @@ def test_three_epf_iterations_through_the_fused_producer_match_oracle(dq, oracle
     """epf_iters = 3 with the frame in fused mode (forced here; automatic from the whole-frame size rule): k_fused_pc0
     marches [Gaborish] + EPF0 from the slab its producing wave fills -- the DCT8 cells decoded in the wave, never written
     to the first plane set -- into the second plane set; EPF1 + EPF2 + output from there as in the two-phase path
-    (kernels_fused.hip part 3, epf0_march.h).  Against the oracle at the bar of every other path, and bit-equal to the
+    (kernels_fused_epf0.hip, epf0_march.h).  Against the oracle at the bar of every other path, and bit-equal to the
     two-phase path (k_epf0): the same arithmetic on the same values, whichever kernel decoded the DCT8 blocks.  Sizes:
     windows cut by the frame's edges, ragged bottoms, several row chunks per window, int32 coefficients; float RGB and
     planar XYB outputs."""

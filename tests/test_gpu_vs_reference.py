@@ -256,7 +256,7 @@ def test_packed_float_srgb(dec, ref, st, sw):
 @pytest.mark.parametrize("tf,st,bits,nc,sw", [(1, 2, 16, 4, 0), (1, 2, 16, 3, 1), (1, 2, 10, 4, 1), (1, 0, 0, 3, 0), (1, 0, 0, 4, 0),
                                               (0, 0, 0, 4, 0), (1, 3, 0, 4, 0), (0, 3, 0, 4, 0), (2, 2, 16, 3, 1), (2, 2, 16, 4, 1)])
 def test_packed_formats_with_a_kernel_of_their_own(dec, ref, tf, st, bits, nc, sw, gab, epf):
-    """Round 3's fixed-format instantiations of the row march (kernels_filters_fast_{b,c,d}.hip: 16-bit sRGB RGBA and
+    """Round 3's fixed-format instantiations of the row march (kernels_filters_fast_{int,be16,fp}.hip: 16-bit sRGB RGBA and
     the big-endian 16-bit forms, float sRGB / linear, half-float RGBA, big-endian 16-bit PQ) against the reference's
     FromLinearStage + WriteToOutputStage, over the stage lists."""
     hdr = tf == 2

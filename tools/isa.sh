@@ -1,5 +1,6 @@
 #!/bin/bash
-# Device ISA + resource usage of one HIP source (no GPU needed): tools/isa.sh kernels_filters_fast.hip [out.s]
+# Device ISA + resource usage of one translation unit of libjxl_amd/csrc (no GPU needed):
+# tools/isa.sh kernels_filters_fast_int.hip [out.s]
 src=$1; out=${2:-/tmp/dis/$(basename $src .hip).s}
 mkdir -p $(dirname $out)
 cd $(dirname $0)/../libjxl_amd/csrc
