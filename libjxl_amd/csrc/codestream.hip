@@ -1,7 +1,9 @@
-// codestream.inc -- jxlhip_codestream_basic_info / jxlhip_decode_codestream (include/jxl_hip_codestream.h):
+// codestream.hip -- jxlhip_codestream_basic_info / jxlhip_decode_codestream (include/jxl_hip_codestream.h):
 // the host front-end pieces (entropy.cc, modular.inc) and the device back-end glued into the order of
 // operations of FrameDecoder (lib/jxl/dec_frame.cc:96-189, 268-416, 573-760) for ONE plain VarDCT still frame.
-// Included by context.hip inside extern "C".
+#include <functional>
+
+#include "context.h"
 
 namespace {
 
@@ -481,7 +483,7 @@ int jxlhip_decode_codestream_extra(jxlhip_ctx* c, jxlhip_parallel_runner runner,
                                         out_plane_stride, extra_planes, num_extra_planes, extra_stride, info_out);
     // an early return may leave uploads of this frame queued: nothing of it may still be in flight when the
     // caller frees its buffers
-    if (rc != JXLHIP_OK && c && c->children.empty() && c->stream) (void)hipStreamSynchronize(c->stream);
+    if (rc != JXLHIP_OK && c && !c->multi && c->stream) (void)hipStreamSynchronize(c->stream);
     return rc;
   } catch (const std::bad_alloc&) {
     return c ? Fail(c, JXLHIP_ERR_OUT_OF_MEMORY, "host allocation failed while decoding the codestream") : JXLHIP_ERR_OUT_OF_MEMORY;
@@ -820,7 +822,7 @@ static int DecodeCodestreamImpl(jxlhip_ctx* c, jxlhip_parallel_runner runner, vo
     HIPCHK(c, hipMemcpyAsync((void*)in.epf_sharpness, sharp.data(), nb, hipMemcpyHostToDevice, st));
     HIPCHK(c, hipMemcpyAsync((void*)in.ytox_map, ytox.data(), nt, hipMemcpyHostToDevice, st));
     HIPCHK(c, hipMemcpyAsync((void*)in.ytob_map, ytob.data(), nt, hipMemcpyHostToDevice, st));
-    if ((rc = Grow(c, &c->qdc_dev, &c->qdc_dev_items, 3 * nb))) return rc;
+    if ((rc = c->qdc_dev.Reserve(c, 3 * nb))) return rc;
     HIPCHK(c, hipMemcpyAsync(c->qdc_dev, qdc.data(), 3 * nb * sizeof(int32_t), hipMemcpyHostToDevice, st));
     {
       const int32_t* q3[3] = {c->qdc_dev, c->qdc_dev + nb, c->qdc_dev + 2 * nb};

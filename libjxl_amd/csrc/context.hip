@@ -1,213 +1,22 @@
-// context.hip -- the C ABI of include/jxl_hip.h: context, frame set-up, input
-// hand-off, the two decode phases, halo regions, profiling.  Host code only;
+// context.hip -- the C ABI of include/jxl_hip.h: context, frame set-up, the
+// two decode phases, halo regions, profiling.  Host code only;
 // kernels live in kernels_*.hip.  No CPU fallback: every entry point that needs
 // a device fails with JXLHIP_ERR_NO_DEVICE / JXLHIP_ERR_HIP when there is none.
+// The input hand-off is handover.hip, the multi-device parent multi.hip, the whole-file decoder codestream.hip.
 #include <math.h>
 #include <stdarg.h>
-#include <stdio.h>
 #include <stdlib.h>
 #include <new>
-#include <string.h>
 
-#include <algorithm>
-#include <chrono>
-#include <functional>
-#include <condition_variable>
-#include <atomic>
-#include <memory>
-#include <mutex>
-#include <vector>
-
-#include "../../include/jxl_hip_codestream.h"
-#include "../../include/jxl_hip_entropy.h"
-#include "kernels.h"
+#include "context.h"
 #include "dither_pattern.inc"
 
-#include "env_switches.h"  // (the switches themselves live in entropy.cc: that file is also built alone, by the fuzz harnesses)
 extern "C" __attribute__((visibility("default"))) void jxlhip_debug_reload_env(void) {
   std::lock_guard<std::mutex> lock(jxlhip_env::g.mu);
   jxlhip_env::LoadLocked();
 }
 
-using namespace jxlhip;
-
-namespace {
-
-constexpr int kPoolStreams = 8;
-// Counter blocks (kCountStride u32 each) of phase 1 (LaunchPhase1): direct calls alternate between blocks 0 and 1; a
-// phase 1 recorded into a hipGraph uses kCaptureBlock, a block no direct call ever touches -- a replay dirties its block
-// behind the host's back, and the host's "clean" flags describe blocks 0 / 1 only (round 5 put captured frames on
-// block 0, round 6 still the split calls: a replay between two direct calls left k_prepare starting on non-zero counters).
-constexpr int kCaptureBlock = 2;
-constexpr int kCountBlocks = 3;
-// pinned staging buffers of jxlhip_ac_group_decode_submit (0.4 / 0.8 MB each): kStageSlotsFirst at first use, one more
-// whenever a thread would otherwise have to wait for an upload to finish, up to kStageSlots.  (An upload is microseconds
-// of PCIe, but the runtime now and then sits on a queued copy for 10-30 ms -- profiles/r04_e2e_waits.txt -- and with 32
-// slots for 64 decoding threads that stall became every thread's.)
-constexpr int kStageSlots = 128, kStageSlotsFirst = 32;
-// (slots are pinned kStageChunk at a time: one hipHostMalloc of 12 MB takes a tenth of the time of 32 of 0.4 MB, and a
-// context's first frame -- all a one-shot tool ever decodes -- waited for them)
-constexpr int kStageChunk = 32;
-
-// jxlhip_profile_enable: ONE event between consecutive launches (it ends the span of the launch before it and starts
-// the span of the one after: rounds 1-5 recorded two, and the pass inflated every launch by ~9 %)
-struct ProfMarkRec {
-  hipEvent_t ev;
-  int slot_after;  // kernel slot of the span that STARTS at this event; < 0: none (the end of a group of launches)
-};
-
-}  // namespace
-
-struct jxlhip_ctx {
-  // jxlhip_create_multi: the context is a PARENT over one child context per device (a device may be
-  // listed more than once); frame-level calls fan out to the children, each of which decodes a stripe
-  // of group rows.  A parent owns no device memory of its own except the halo staging below.
-  std::vector<jxlhip_ctx*> children;
-  std::vector<std::pair<uint32_t, uint32_t>> stripes;  // (group_y0, group_rows) per child of the current frame
-  std::vector<float*> halo_send[2], halo_recv[2];      // per child: dense [3][halo][xsize] staging (0: up, 1: down)
-  std::vector<size_t> halo_floats;
-  std::vector<uint8_t*> stripe_out;                    // per child: its output stripe when the frame goes to another device / the host
-  std::vector<size_t> stripe_out_bytes;
-  std::vector<hipEvent_t> ev_halo[2], ev_pull[2], ev_done;
-  JxlMemoryManagerHip mm{};                            // jxlhip_create_ex / _multi: who allocated this object
-  int device = 0;
-  hipStream_t own_stream = nullptr;
-  hipStream_t stream = nullptr;  // the one launches go to
-  char err[512] = {0};
-  bool have_frame = false;
-  bool have_inputs = false;
-  bool blocks_done = false;
-  // Direct phase-1 launches alternate between counter blocks 0 and 1: k_prepare of frame N zeroes the block frame N + 1
-  // will use (DevFrame::zero_counts) -- no memset launch per frame.  clean[b]: block b is all zero.
-  int counts_slot = 0;
-  bool counts_clean[2] = {false, false};
-  double cs_phase_ms[8] = {};  // jxlhip_codestream_phase_ms
-  int concurrency = 1;  // jxlhip_set_concurrency_hint: contexts the caller keeps busy on this device at a time
-  bool handover_fresh = false;  // frame_begin started the hand-over and upload_side_info has not been called since
-  bool blocks_fused = false;  // jxlhip_decode_blocks ran in fused-stripe mode: the planes lack the inner DCT8 blocks
-  jxlhip_frame_params p{};
-  DevFrame f{};
-  FilterParams fp{};
-  SharpLut lut{};
-  // context-owned device memory
-  float* planes = nullptr;  // 3 planes
-  size_t planes_floats = 0;
-  unsigned char* orient_dev = nullptr;  // undo_orientation: the frame in coded orientation (jxlhip_decode_frame)
-  size_t orient_bytes = 0;
-  float* planes2 = nullptr;  // epf_iters == 3: EPF0 output, the EPF1 + EPF2 march's input (kernels_epf0.hip)
-  size_t planes2_floats = 0;
-  float* inv_sigma = nullptr;
-  size_t sigma_floats = 0;
-  WorkItem* lists = nullptr;
-  size_t lists_items = 0;
-  uint32_t* counts = nullptr;    // kNumClasses
-  int32_t* error_flag = nullptr; // [0] stream error, [1] table status
-  float* tables = nullptr;       // wc[512] + resample[64]
-  jxlhip_quant_encoding* quant_enc = nullptr;  // device: the 17 resolved encodings of the last table build
-  jxlhip_quant_encoding quant_enc_host[JXLHIP_NUM_QUANT_TABLES];
-  WorkLists wl{};
-  uint32_t max_items[kNumClasses] = {0};
-  // upload path
-  void* up_coeffs[3] = {nullptr, nullptr, nullptr};
-  size_t up_coeff_bytes = 0;
-  uint32_t up_groups = 0;  // geometry the upload buffers were laid out for
-  size_t up_esz = 0;
-  uint8_t* up_side = nullptr;  // one slab: acs, quant, sharp, ytox, ytob, dc*3, dequant
-  size_t up_side_bytes = 0;
-  jxlhip_frame_inputs up_inputs{};
-  // sparse coefficient hand-off (jxlhip_ac_group_decode_submit, single-pass 16-bit frames): a group's non-zero
-  // coefficients go up as (position << 16 | value) words into sp_dev + group * kSparseStride; BeginDecode expands the
-  // groups whose sp_mode byte is set into the dense upload buffer (k_expand_sparse)
-  bool sparse_upload = true;  // JXLHIP_SPARSE_UPLOAD=0 turns it off
-  uint8_t* sp_dev = nullptr;
-  size_t sp_bytes = 0;
-  uint32_t frame_serial = 0;
-  std::atomic<bool> sp_any{false};
-  std::atomic<size_t> sp_arena_used{0};   // sp_dev is a per-frame bump arena: a staging slot's worth of groups per copy
-  uint32_t* sp_off_host[2] = {nullptr, nullptr};  // pinned, per frame parity: arena offset / 16 of every group's header,
-  size_t sp_off_items = 0;                        // 0xFFFFFFFF = the group was handed over densely
-  hipEvent_t sp_off_ev[2] = {nullptr, nullptr};   // "the copy of sp_off_host[parity] has executed"
-  bool sp_off_pending[2] = {false, false};
-  uint32_t* sp_off_dev = nullptr;
-  size_t sp_off_dev_items = 0;
-  hipStream_t pool[kPoolStreams] = {nullptr};
-  hipEvent_t pool_ev[kPoolStreams] = {nullptr};
-  hipEvent_t frame_ev = nullptr;  // jxlhip_frame_begin: "everything queued for the previous frame", see there
-  bool pool_dirty[kPoolStreams] = {false};
-  std::mutex pool_mu;
-  uint32_t pool_next = 0;
-  // entropy-decode staging: pinned host buffers (3 channels x 65536 coefficients
-  // each), reused round-robin; stage_ev[i] fires when slot i's upload is done
-  void* stage[kStageSlots] = {nullptr};
-  hipEvent_t stage_ev[kStageSlots] = {nullptr};
-  int stage_state[kStageSlots] = {0};  // 0 free, 1 owned by a decoding thread, 2 upload queued (stage_ev)
-  int stage_count = 0;                 // slots allocated so far (<= stage_cap), kStageChunk at a time
-  int stage_cap = kStageSlots;         // JXLHIP_STAGE_SLOTS (read at jxlhip_create): pinned host memory per context is at
-                                       // most stage_cap x 0.8 MB -- several contexts per device share the host's lockable memory
-  void* stage_chunk[kStageSlots / kStageChunk] = {nullptr};  // the allocations the slots are carved from
-  size_t stage_bytes = 0;
-  std::mutex stage_mu;
-  std::condition_variable stage_cv;
-  // dc scratch
-  float* dc_tmp = nullptr;
-  size_t dc_tmp_floats = 0;
-  uint8_t* dc_prec = nullptr;  // per-DC-group extra_precision of jxlhip_dequant_dc_groups
-  size_t dc_prec_bytes = 0;
-  uint8_t* host_frame_dev = nullptr;  // jxlhip_decode_frame_host: the device frame in front of the D2H copy
-  size_t host_frame_bytes = 0;
-  void* pinned_frame = nullptr;  // jxlhip_decode_frame_pinned: context-owned pinned host frame (StageAlloc)
-  size_t pinned_frame_bytes = 0;
-  float* alpha_dev = nullptr;  // jxlhip_set_alpha: the frame's alpha plane (xsize floats per row)
-  size_t alpha_items = 0;
-  void* alpha_host = nullptr;  // jxlhip_alpha_staging: pinned plane the caller fills
-  size_t alpha_host_items = 0;
-  int32_t* qdc_dev = nullptr;  // jxlhip_decode_codestream: the quantized DC planes on their way to jxlhip_dequant_dc_groups
-  // jxlhip_set_noise: photon noise of the current frame (frame_begin resets noise_on); noise_buf = the filtered frame as
-  // planar XYB + the random planes (kernels_noise.hip), noise_jump = the generator's jump matrices (uploaded once)
-  bool noise_on = false;
-  float noise_lut[8] = {0};
-  uint32_t noise_visible = 0, noise_nonvisible = 0;
-  float* noise_buf = nullptr;
-  size_t noise_floats = 0;
-  uint32_t* noise_jump = nullptr;
-  // jxlhip_set_splines: the draw list of the current frame (frame_begin resets splines_on), binned by 64 x 16 tile
-  // (kernels_splines.hip); spl_tiles = tile_start (tiles + 1), tile_idx, active tiles.  The host copies stay alive
-  // until spl_ev says their upload is done.
-  bool splines_on = false;
-  SplineSeg* spl_segs = nullptr;
-  size_t spl_segs_items = 0;
-  uint32_t* spl_tiles = nullptr;
-  size_t spl_tiles_items = 0;
-  uint32_t spl_tiles_x = 0, spl_num_tiles = 0, spl_num_active = 0;
-  size_t spl_entries = 0;
-  std::vector<SplineSeg> spl_host_segs;
-  std::vector<uint32_t> spl_host_tiles;
-  hipEvent_t spl_ev = nullptr;
-  bool spl_ev_pending = false;
-  size_t qdc_dev_items = 0;
-  bool generic_filters = false;  // JXLHIP_FILTERS=generic: LDS kernel for every stage list
-  int mfma = -1;                 // DCT32X32 / DCT16X16 on the matrix cores (kernels_mfma.hip; the 16x16 rule is in
-                                 // LaunchPhase1).  -1 (default): when the caller's
-                                 // used_acs says DCT32X32 is the only class of the row-per-lane 32-point family in
-                                 // the frame (the class kernel then is a launch of its own anyway; measured on c5:
-                                 // 219 -> 193 us); on mixed frames the butterflies inside the merged launch win
-                                 // (c3: blocks 95 -> 105 us with a separate MFMA launch).  JXLHIP_MFMA=0 / 1 forces.
-  int fuse = -1;                 // the fused kernel (kernels_fused.hip) in jxlhip_decode_frame.  -1 (default): for
-                                 // frames of 12 Mpx and more -- a fused wave pays its halo rows and a fill per 8 rows,
-                                 // which only amortises when the frame gives every resident wave enough rows (8K d1.0:
-                                 // fused 89.9 vs 80 Gpx/s two-phase; 6144x3456: 88.5 vs 77.4; 5120x2880: 87.5 vs 82.2;
-                                 // 4K: 71.2 vs 80.3; 1024^2: 16.9 vs 18.3; profiles/r02_fused_rows_sweep*.txt,
-                                 // r02_fused_size_threshold.txt).  JXLHIP_FUSE=0 / 1 forces.
-  uint2* cell_info = nullptr;    // fused mode: per-cell coefficient offset + quant / CfL word (k_prepare)
-  size_t cell_info_items = 0;
-  // profiling
-  bool profiling = false;
-  std::vector<ProfMarkRec> marks;
-};
-
-namespace {
-
-int Fail(jxlhip_ctx* c, int code, const char* fmt, ...) {
+int jxlhip::Fail(jxlhip_ctx* c, int code, const char* fmt, ...) {
   if (c) {
     va_list ap;
     va_start(ap, fmt);
@@ -217,83 +26,32 @@ int Fail(jxlhip_ctx* c, int code, const char* fmt, ...) {
   return code;
 }
 
-#define HIPCHK(c, call)                                                              \
-  do {                                                                               \
-    hipError_t e_ = (call);                                                          \
-    if (e_ != hipSuccess)                                                            \
-      return Fail(c, e_ == hipErrorOutOfMemory ? JXLHIP_ERR_OUT_OF_MEMORY           \
-                                               : JXLHIP_ERR_HIP,                     \
-                  "%s: %s", #call, hipGetErrorString(e_));                           \
-  } while (0)
+namespace {
 
-template <typename T>
-int Grow(jxlhip_ctx* c, T** ptr, size_t* have, size_t need) {
-  if (need <= *have && *ptr) return JXLHIP_OK;
-  if (*ptr) HIPCHK(c, hipFree(*ptr));
-  *ptr = nullptr;
-  *have = 0;
-  HIPCHK(c, hipMalloc((void**)ptr, need * sizeof(T)));
-  *have = need;
-  return JXLHIP_OK;
+// Counter blocks (kCountStride u32 each) of phase 1 (LaunchPhase1): direct calls alternate between blocks 0 and 1; a
+// phase 1 recorded into a hipGraph uses kCaptureBlock, a block no direct call ever touches -- a replay dirties its block
+// behind the host's back, and the host's "clean" flags describe blocks 0 / 1 only (round 5 put captured frames on
+// block 0, round 6 still the split calls: a replay between two direct calls left k_prepare starting on non-zero counters).
+constexpr int kCaptureBlock = 2;
+constexpr int kCountBlocks = 3;
+
+void ProfPush(jxlhip_ctx* c) {
+  c->marks.emplace_back();
+  (void)c->marks.back().ev.Create(hipEventDefault);
+  (void)hipEventRecord(c->marks.back().ev, c->stream);
 }
-
 void ProfBegin(jxlhip_ctx* c) {
-  if (!c->profiling) return;
-  hipEvent_t e;
-  (void)hipEventCreate(&e);
-  (void)hipEventRecord(e, c->stream);
-  c->marks.push_back({e, -1});
+  if (c->profiling) ProfPush(c);
 }
-// closes the span [previous mark, now) for `slot` and opens the next one
+// closes the span [previous mark, now) for `slot` and opens the next one (the last mark's slot_after stays -1: nothing
+// starts there)
 void ProfMark(jxlhip_ctx* c, int slot) {
   if (!c->profiling || c->marks.empty()) return;
   c->marks.back().slot_after = slot;
-  hipEvent_t e;
-  (void)hipEventCreate(&e);
-  (void)hipEventRecord(e, c->stream);
-  c->marks.push_back({e, -1});
+  ProfPush(c);
 }
-void ProfEnd(jxlhip_ctx* c) { (void)c; }  // (the last mark's slot_after stays -1: nothing starts there)
-
-// Pinned staging slots: memory from the caller's JxlMemoryManager when there is one (pinned in place
-// with hipHostRegister: "caller owns the host memory, the library pins it"), else hipHostMalloc.
-int StageAlloc(jxlhip_ctx* c, void** p, size_t bytes) {
-  if (c->mm.alloc) {
-    *p = c->mm.alloc(c->mm.opaque, bytes);
-    if (!*p) return JXLHIP_ERR_OUT_OF_MEMORY;
-    if (hipHostRegister(*p, bytes, hipHostRegisterDefault) != hipSuccess) {
-      c->mm.free(c->mm.opaque, *p);
-      *p = nullptr;
-      return JXLHIP_ERR_OUT_OF_MEMORY;
-    }
-    return JXLHIP_OK;
-  }
-  return hipHostMalloc(p, bytes, hipHostMallocDefault) == hipSuccess ? JXLHIP_OK : JXLHIP_ERR_OUT_OF_MEMORY;
-}
-void StageFree(jxlhip_ctx* c, void* p) {
-  if (c->mm.alloc) {
-    (void)hipHostUnregister(p);
-    c->mm.free(c->mm.opaque, p);
-  } else {
-    (void)hipHostFree(p);
-  }
-}
-
-void MultiDestroy(jxlhip_ctx* c);
-int MultiFrameBegin(jxlhip_ctx* c, const jxlhip_frame_params* p);
-int MultiOwner(const jxlhip_ctx* c, uint32_t group_idx);
-int MultiDecodeFrame(jxlhip_ctx* c, void* out_dev, void* host_out, size_t out_stride, size_t out_plane_stride);
-int MultiSync(jxlhip_ctx* c);
-int MultiCheck(jxlhip_ctx* c, jxlhip_ctx* child, int rc);
-#define JXLHIP_NO_MULTI(c)                                                                                   \
-  do {                                                                                                       \
-    if ((c) && !(c)->children.empty())                                                                       \
-      return Fail((c), JXLHIP_ERR_UNSUPPORTED, "%s is not available on a multi-device context", __func__); \
-  } while (0)
 
 }  // namespace
-
-extern "C" {
 
 // ---- static helpers -------------------------------------------------------
 int jxlhip_covered_blocks_x(int s) {
@@ -332,7 +90,7 @@ const char* jxlhip_status_string(int status) {
 }
 
 // ---- context ----------------------------------------------------------------
-static jxlhip_ctx* NewCtx(const JxlMemoryManagerHip* mm) {
+jxlhip_ctx* jxlhip::NewCtx(const JxlMemoryManagerHip* mm) {
   JxlMemoryManagerHip m{};
   if (mm) m = *mm;
   void* mem = m.alloc ? m.alloc(m.opaque, sizeof(jxlhip_ctx)) : malloc(sizeof(jxlhip_ctx));
@@ -341,7 +99,7 @@ static jxlhip_ctx* NewCtx(const JxlMemoryManagerHip* mm) {
   c->mm = m;
   return c;
 }
-static void DeleteCtx(jxlhip_ctx* c) {
+void jxlhip::DeleteCtx(jxlhip_ctx* c) {
   const JxlMemoryManagerHip m = c->mm;
   c->~jxlhip_ctx();
   if (m.free) m.free(m.opaque, c);
@@ -381,80 +139,43 @@ int jxlhip_create_ex(int device, const JxlMemoryManagerHip* memory_manager, jxlh
     return code;
   };
   if (hipSetDevice(device) != hipSuccess) return fail(JXLHIP_ERR_HIP);
-  if (hipStreamCreateWithFlags(&c->own_stream, hipStreamNonBlocking) != hipSuccess)
-    return fail(JXLHIP_ERR_HIP);
+  if (c->own_stream.Create() != hipSuccess) return fail(JXLHIP_ERR_HIP);
   c->stream = c->own_stream;
   for (int i = 0; i < kPoolStreams; i++) {
-    if (hipStreamCreateWithFlags(&c->pool[i], hipStreamNonBlocking) != hipSuccess ||
-        hipEventCreateWithFlags(&c->pool_ev[i], hipEventDisableTiming) != hipSuccess)
-      return fail(JXLHIP_ERR_HIP);
+    if (c->pool[i].Create() != hipSuccess || c->pool_ev[i].Create() != hipSuccess) return fail(JXLHIP_ERR_HIP);
   }
-  if (hipEventCreateWithFlags(&c->frame_ev, hipEventDisableTiming) != hipSuccess) return fail(JXLHIP_ERR_HIP);
-  if (hipMalloc((void**)&c->counts, sizeof(uint32_t) * kCountStride * kCountBlocks) != hipSuccess ||
-      hipMalloc((void**)&c->error_flag, sizeof(int32_t) * 2) != hipSuccess ||
-      hipMalloc((void**)&c->tables, sizeof(float) * (512 + 64 + 1024 + 2048 + 256)) != hipSuccess ||
-      hipMalloc((void**)&c->quant_enc, sizeof(jxlhip_quant_encoding) * JXLHIP_NUM_QUANT_TABLES) != hipSuccess)
+  if (c->frame_ev.Create() != hipSuccess) return fail(JXLHIP_ERR_HIP);
+  if (c->counts.Reserve(c, (size_t)kCountStride * kCountBlocks) || c->error_flag.Reserve(c, 2) ||
+      c->tables.Reserve(c, kTabFloats) || c->quant_enc.Reserve(c, JXLHIP_NUM_QUANT_TABLES))
     return fail(JXLHIP_ERR_OUT_OF_MEMORY);
   if (hipMemset(c->error_flag, 0, sizeof(int32_t) * 2) != hipSuccess ||
-      hipMemcpy(c->tables, kWcHost, sizeof(float) * 512, hipMemcpyHostToDevice) != hipSuccess ||
-      hipMemcpy(c->tables + 512, kResampleUpHost, sizeof(float) * 64, hipMemcpyHostToDevice) !=
+      hipMemcpy(c->tables + kTabWc, kWcHost, sizeof(float) * (kTabResample - kTabWc), hipMemcpyHostToDevice) != hipSuccess ||
+      hipMemcpy(c->tables + kTabResample, kResampleUpHost, sizeof(float) * (kTabDither - kTabResample), hipMemcpyHostToDevice) !=
           hipSuccess ||
-      hipMemcpy(c->tables + 576, kDitherPattern, sizeof(float) * 1024, hipMemcpyHostToDevice) !=
+      hipMemcpy(c->tables + kTabDither, kDitherPattern, sizeof(float) * (kTabMfma32 - kTabDither), hipMemcpyHostToDevice) !=
           hipSuccess)
     return fail(JXLHIP_ERR_HIP);
   {
-    float mfma_tab[2048 + 256];
+    float mfma_tab[kTabFloats - kTabMfma32];
     MfmaDct32Constants(mfma_tab);
-    MfmaDct16Constants(mfma_tab + 2048);
-    if (hipMemcpy(c->tables + 1600, mfma_tab, sizeof(mfma_tab), hipMemcpyHostToDevice) != hipSuccess)
+    MfmaDct16Constants(mfma_tab + (kTabMfma16 - kTabMfma32));
+    if (hipMemcpy(c->tables + kTabMfma32, mfma_tab, sizeof(mfma_tab), hipMemcpyHostToDevice) != hipSuccess)
       return fail(JXLHIP_ERR_HIP);
   }
   *out = c;
   return JXLHIP_OK;
 }
 
+// What is synchronisation happens here; the release is the owners' (~jxlhip_ctx in DeleteCtx).
 void jxlhip_destroy(jxlhip_ctx* c) {
   if (!c) return;
-  if (!c->children.empty()) return MultiDestroy(c);
+  if (c->multi) return MultiDestroy(c);
   (void)hipSetDevice(c->device);
   if (c->own_stream) (void)hipStreamSynchronize(c->own_stream);
-  for (auto& m : c->marks)
-    if (m.ev) (void)hipEventDestroy(m.ev);
-  for (int i = 0; i < kPoolStreams; i++) {
-    if (c->pool[i]) {
-      (void)hipStreamSynchronize(c->pool[i]);
-      (void)hipStreamDestroy(c->pool[i]);
-    }
-    if (c->pool_ev[i]) (void)hipEventDestroy(c->pool_ev[i]);
-  }
-  if (c->frame_ev) (void)hipEventDestroy(c->frame_ev);
-  for (int i = 0; i < kStageSlots; i++) {
-    if (c->stage_ev[i]) {
-      if (c->stage_state[i] == 2) (void)hipEventSynchronize(c->stage_ev[i]);
-      (void)hipEventDestroy(c->stage_ev[i]);
-    }
-  }
-  for (void*& chunk : c->stage_chunk) {
-    if (chunk) StageFree(c, chunk);
-    chunk = nullptr;
-  }
-  if (c->pinned_frame) StageFree(c, c->pinned_frame);
-  if (c->sp_dev) (void)hipFree(c->sp_dev);
-  if (c->alpha_host) StageFree(c, c->alpha_host);
-  if (c->sp_off_dev) (void)hipFree(c->sp_off_dev);
-  for (int i = 0; i < 2; i++) {
-    if (c->sp_off_host[i]) StageFree(c, c->sp_off_host[i]);
-    if (c->sp_off_ev[i]) (void)hipEventDestroy(c->sp_off_ev[i]);
-  }
-  void* bufs[] = {c->planes, c->inv_sigma, c->lists,        c->counts,
-                  c->error_flag, c->tables, c->up_coeffs[0], c->up_side,
-                  c->dc_tmp,     c->quant_enc,  c->dc_prec,      c->cell_info,
-                  c->qdc_dev,    c->host_frame_dev, c->planes2, c->orient_dev,
-                  c->alpha_dev,  c->noise_buf,  c->noise_jump, c->spl_segs, c->spl_tiles};
-  for (void* b : bufs)
-    if (b) (void)hipFree(b);
-  if (c->spl_ev) (void)hipEventDestroy(c->spl_ev);
-  if (c->own_stream) (void)hipStreamDestroy(c->own_stream);
+  for (int i = 0; i < kPoolStreams; i++)
+    if (c->pool[i]) (void)hipStreamSynchronize(c->pool[i]);
+  for (int i = 0; i < kStageSlots; i++)
+    if (c->stage_ev[i] && c->stage_state[i] == 2) (void)hipEventSynchronize(c->stage_ev[i]);
   DeleteCtx(c);
 }
 
@@ -462,7 +183,7 @@ const char* jxlhip_last_error(const jxlhip_ctx* c) { return c ? c->err : ""; }
 
 int jxlhip_set_stream(jxlhip_ctx* c, void* hip_stream, int external) {
   if (!c) return JXLHIP_ERR_INVALID_ARGUMENT;
-  if (!c->children.empty()) return jxlhip_set_stream(c->children[0], hip_stream, external);  // the frame's consumer is on devices[0]
+  if (c->multi) return jxlhip_set_stream(c->multi->kids[0].ctx, hip_stream, external);  // the frame's consumer is on devices[0]
   const hipStream_t st = external ? (hipStream_t)hip_stream : c->own_stream;
   // the zeroing of the next frame's counter block is ordered on the OLD stream only: a new stream starts with a memset
   if (st != c->stream) c->counts_clean[0] = c->counts_clean[1] = false;
@@ -471,45 +192,10 @@ int jxlhip_set_stream(jxlhip_ctx* c, void* hip_stream, int external) {
 }
 
 // ---- frame set-up -------------------------------------------------------------
-// A new hand-over of a frame's data begins (jxlhip_frame_begin, and jxlhip_upload_side_info: the same frame may be
-// handed over again without a new frame_begin).  Frames may follow each other without a jxlhip_sync: the group
-// uploads travel on the pool streams into buffers the previous decode's kernels (main stream) may still be reading,
-// so the pool streams wait for everything queued on the main stream; the sparse arena and its offset table start empty.
-static int BeginHandover(jxlhip_ctx* c) {
-  const DevFrame& f = c->f;
-  c->frame_serial++;
-  c->sp_any.store(false);
-  c->sp_arena_used.store(0);
-  if (c->sparse_upload && f.coeff_type == JXLHIP_COEFF_I16) {
-    const size_t ng = (size_t)f.xsg * f.ysg;
-    const int par = (int)(c->frame_serial & 1u);
-    if (c->sp_off_items < ng) {
-      for (int i = 0; i < 2; i++) {
-        if (c->sp_off_pending[i]) (void)hipEventSynchronize(c->sp_off_ev[i]);
-        c->sp_off_pending[i] = false;
-        if (c->sp_off_host[i]) StageFree(c, c->sp_off_host[i]);
-        c->sp_off_host[i] = nullptr;
-        if (StageAlloc(c, (void**)&c->sp_off_host[i], ng * 4)) return Fail(c, JXLHIP_ERR_OUT_OF_MEMORY, "sparse offset table");
-        if (!c->sp_off_ev[i]) HIPCHK(c, hipEventCreateWithFlags(&c->sp_off_ev[i], hipEventDisableTiming));
-      }
-      c->sp_off_items = ng;
-    }
-    // the table of two hand-overs ago has long been copied; make sure before it is overwritten
-    if (c->sp_off_pending[par]) HIPCHK(c, hipEventSynchronize(c->sp_off_ev[par]));
-    c->sp_off_pending[par] = false;
-    memset(c->sp_off_host[par], 0xFF, ng * 4);
-  }
-  if (c->up_coeffs[0]) {
-    HIPCHK(c, hipEventRecord(c->frame_ev, c->stream));
-    for (int i = 0; i < kPoolStreams; i++) HIPCHK(c, hipStreamWaitEvent(c->pool[i], c->frame_ev, 0));
-  }
-  return JXLHIP_OK;
-}
-
 int jxlhip_frame_begin(jxlhip_ctx* c, const jxlhip_frame_params* p) {
   if (c && p && p->undo_orientation > 8) return Fail(c, JXLHIP_ERR_INVALID_ARGUMENT, "undo_orientation %u", p->undo_orientation);
   if (!c || !p) return JXLHIP_ERR_INVALID_ARGUMENT;
-  if (!c->children.empty()) return MultiFrameBegin(c, p);
+  if (c->multi) return MultiFrameBegin(c, p);
   if (p->xsize == 0 || p->ysize == 0 || p->xsize > (1u << 19) || p->ysize > (1u << 19))
     return Fail(c, JXLHIP_ERR_INVALID_ARGUMENT, "frame size %ux%u out of range", p->xsize,
                 p->ysize);
@@ -573,10 +259,10 @@ int jxlhip_frame_begin(jxlhip_ctx* c, const jxlhip_frame_params* p) {
   f.plane_tile_rows = rows_blocks / 8 + 2;
   const size_t plane_floats = (size_t)f.plane_tile_rows * f.tile_stride * 64;
   int rc;
-  if ((rc = Grow(c, &c->planes, &c->planes_floats, 3 * plane_floats))) return rc;
+  if ((rc = c->planes.Reserve(c, 3 * plane_floats))) return rc;
   for (int ch = 0; ch < 3; ch++) f.xyb[ch] = c->planes + ch * plane_floats;
-  if (p->lf.epf_iters == 3 && (rc = Grow(c, &c->planes2, &c->planes2_floats, 3 * plane_floats))) return rc;
-  if ((rc = Grow(c, &c->inv_sigma, &c->sigma_floats, (size_t)f.xsb * f.ysb))) return rc;
+  if (p->lf.epf_iters == 3 && (rc = c->planes2.Reserve(c, 3 * plane_floats))) return rc;
+  if ((rc = c->inv_sigma.Reserve(c, (size_t)f.xsb * f.ysb))) return rc;
   f.inv_sigma = c->inv_sigma;
   f.error_flag = c->error_flag;
   // work lists, worst case per class
@@ -590,7 +276,7 @@ int jxlhip_frame_begin(jxlhip_ctx* c, const jxlhip_frame_params* p) {
     total += m;
   }
   // +64: transform kernels fetch their list entry before they know the count
-  if ((rc = Grow(c, &c->lists, &c->lists_items, total + 64))) return rc;
+  if ((rc = c->lists.Reserve(c, total + 64))) return rc;
   for (int k = 0; k < kNumClasses; k++) c->wl.list[k] = c->lists + offs[k];
   c->wl.count = c->counts;
   // stage parameters, computed as the reference stages do
@@ -622,7 +308,7 @@ int jxlhip_frame_begin(jxlhip_ctx* c, const jxlhip_frame_params* p) {
     fp.fmt = p->out_format;
     const bool is_int = fp.fmt.sample_type == JXLHIP_SAMPLE_U8 || fp.fmt.sample_type == JXLHIP_SAMPLE_U16;
     fp.sample_mul = is_int ? (float)((1u << fp.fmt.bits_per_sample) - 1u) : 1.0f;  // stage_write.cc:528
-    fp.dither = c->tables + 576;
+    fp.dither = c->tables + kTabDither;
     // TF_PQ's display_scaling_factor_to_10000_nits_ (transfer_functions-inl.h:146-148)
     fp.tf_scale = fp.fmt.transfer == JXLHIP_TF_PQ ? fp.fmt.tf_param * (1.0f / 10000.0f) : fp.fmt.tf_param;
     fp.hlg_exponent = 0.0f;
@@ -660,7 +346,7 @@ int jxlhip_frame_begin(jxlhip_ctx* c, const jxlhip_frame_params* p) {
   return JXLHIP_OK;
 }
 
-static void ApplyInputs(jxlhip_ctx* c, const jxlhip_frame_inputs* in) {
+void jxlhip::ApplyInputs(jxlhip_ctx* c, const jxlhip_frame_inputs* in) {
   c->f.coef_stride64 = in == &c->up_inputs ? 3072u : 1024u;
   for (int ch = 0; ch < 3; ch++) {
     c->f.coeffs[ch] = in->coeffs[ch];
@@ -693,95 +379,18 @@ int jxlhip_frame_set_inputs(jxlhip_ctx* c, const jxlhip_frame_inputs* in) {
   return JXLHIP_OK;
 }
 
-// lays the side-info slab out; returns total bytes
-static size_t SideLayout(const DevFrame& f, size_t off[9]) {
-  const size_t nb = (size_t)f.xsb * f.ysb;
-  const size_t nt = (size_t)f.xtiles * ((f.ysb + 7) / 8);
-  size_t pos = 0;
-  auto take = [&](size_t bytes) {
-    const size_t o = pos;
-    pos += (bytes + 255) & ~(size_t)255;
-    return o;
-  };
-  off[0] = take(nb);                   // acs
-  off[1] = take(nb * 4);               // raw_quant
-  off[2] = take(nb);                   // sharpness
-  off[3] = take(nt);                   // ytox
-  off[4] = take(nt);                   // ytob
-  off[5] = take(nb * 4);               // dc x
-  off[6] = take(nb * 4);               // dc y
-  off[7] = take(nb * 4);               // dc b
-  off[8] = take(sizeof(float) * JXLHIP_DEQUANT_TABLE_FLOATS);
-  return pos;
-}
-
-static int EnsureUploadBuffers(jxlhip_ctx* c) {
-  const DevFrame& f = c->f;
-  const size_t esz = f.coeff_type == JXLHIP_COEFF_I16 ? 2 : 4;
-  // one buffer, [group][channel][65536]: a group's three channels are contiguous, so the
-  // staging slot of jxlhip_ac_group_decode_submit goes up with ONE copy (three copies per group
-  // = ~400 hipMemcpyAsync calls per 4K frame were a 4.5 ms serial floor: the runtime serialises
-  // them whatever thread they come from)
-  const size_t cbytes = (size_t)f.xsg * f.ysg * 3 * JXLHIP_GROUP_COEFFS * esz;
-  if (cbytes > c->up_coeff_bytes || !c->up_coeffs[0]) {
-    if (c->up_coeffs[0]) HIPCHK(c, hipFree(c->up_coeffs[0]));
-    c->up_coeffs[0] = c->up_coeffs[1] = c->up_coeffs[2] = nullptr;
-    c->up_coeff_bytes = 0;
-    HIPCHK(c, hipMalloc(&c->up_coeffs[0], cbytes));
-    c->up_coeff_bytes = cbytes;
-  }
-  if (c->sparse_upload && esz == 2) {  // the landing zone of the sparse hand-off (see SubmitSparse)
-    const size_t need = (size_t)f.xsg * f.ysg * 3 * JXLHIP_GROUP_COEFFS * 2;
-    if (c->sp_bytes < need) {
-      if (c->sp_dev) HIPCHK(c, hipFree(c->sp_dev));
-      c->sp_dev = nullptr;
-      c->sp_bytes = 0;
-      // (never cleared: k_expand_sparse reads only what the offset table points at, and those bytes were uploaded.
-      // A hipMemset here runs on the NULL stream, unordered against the uploads on the non-blocking pool streams: it
-      // once landed AFTER the first batch and turned a frame into its DC image.)
-      HIPCHK(c, hipMalloc((void**)&c->sp_dev, need));
-      c->sp_bytes = need;
-    }
-  }
-  c->up_groups = f.xsg * f.ysg;
-  c->up_esz = esz;
-  c->up_coeffs[1] = (char*)c->up_coeffs[0] + (size_t)JXLHIP_GROUP_COEFFS * esz;
-  c->up_coeffs[2] = (char*)c->up_coeffs[0] + 2 * (size_t)JXLHIP_GROUP_COEFFS * esz;
-  size_t off[9];
-  const size_t sbytes = SideLayout(f, off);
-  int rc;
-  if ((rc = Grow(c, &c->up_side, &c->up_side_bytes, sbytes))) return rc;
-  jxlhip_frame_inputs in{};
-  for (int ch = 0; ch < 3; ch++) {
-    in.coeffs[ch] = c->up_coeffs[ch];
-    in.dc[ch] = (const float*)(c->up_side + off[5 + ch]);
-  }
-  in.ac_strategy = c->up_side + off[0];
-  in.raw_quant = (const int32_t*)(c->up_side + off[1]);
-  in.epf_sharpness = c->up_side + off[2];
-  in.ytox_map = (const int8_t*)(c->up_side + off[3]);
-  in.ytob_map = (const int8_t*)(c->up_side + off[4]);
-  in.dequant_table = (const float*)(c->up_side + off[8]);
-  c->up_inputs = in;
-  return JXLHIP_OK;
-}
-
 int jxlhip_alpha_staging(jxlhip_ctx* c, float** plane, size_t* stride_floats) {
   if (!c || !plane || !stride_floats) return JXLHIP_ERR_INVALID_ARGUMENT;
   if (!c->have_frame) return Fail(c, JXLHIP_ERR_STATE, "alpha_staging before frame_begin");
   const size_t need = (size_t)c->f.xsize * c->f.ysize;
-  if (need > c->alpha_host_items) {
-    if (c->alpha_host) {
+  if (need * sizeof(float) > c->alpha_host.bytes) {
+    if (c->alpha_host.p) {
       const int rc = jxlhip_sync(c);  // nothing may still be reading the old plane
       if (rc) return rc;
-      StageFree(c, c->alpha_host);
-      c->alpha_host = nullptr;
-      c->alpha_host_items = 0;
     }
-    if (StageAlloc(c, &c->alpha_host, need * sizeof(float))) return Fail(c, JXLHIP_ERR_OUT_OF_MEMORY, "pinned alpha plane");
-    c->alpha_host_items = need;
+    if (c->alpha_host.Alloc(&c->mm, need * sizeof(float))) return Fail(c, JXLHIP_ERR_OUT_OF_MEMORY, "pinned alpha plane");
   }
-  *plane = (float*)c->alpha_host;
+  *plane = (float*)c->alpha_host.p;
   *stride_floats = c->f.xsize;
   return JXLHIP_OK;
 }
@@ -791,17 +400,17 @@ int jxlhip_alpha_staging(jxlhip_ctx* c, float** plane, size_t* stride_floats) {
 int jxlhip_set_alpha(jxlhip_ctx* c, const float* host_plane, size_t stride_floats) {
   if (!c || !host_plane) return JXLHIP_ERR_INVALID_ARGUMENT;
   if (!c->have_frame) return Fail(c, JXLHIP_ERR_STATE, "set_alpha before frame_begin");
-  if (!c->children.empty()) {  // every stripe takes its own rows of the plane
-    for (jxlhip_ctx* k : c->children) {
-      const int rc = jxlhip_set_alpha(k, host_plane, stride_floats);
-      if (rc) return MultiCheck(c, k, rc);
+  if (c->multi) {  // every stripe takes its own rows of the plane
+    for (MultiChild& k : c->multi->kids) {
+      const int rc = jxlhip_set_alpha(k.ctx, host_plane, stride_floats);
+      if (rc) return MultiCheck(c, k.ctx, rc);
     }
     return JXLHIP_OK;
   }
   const size_t w = c->f.xsize, y0 = c->f.y0, rows = c->f.y1 - c->f.y0;
   if (stride_floats < w) return Fail(c, JXLHIP_ERR_INVALID_ARGUMENT, "alpha stride %zu < xsize", stride_floats);
   HIPCHK(c, hipSetDevice(c->device));
-  const int rc = Grow(c, &c->alpha_dev, &c->alpha_items, w * rows);
+  const int rc = c->alpha_dev.Reserve(c, w * rows);
   if (rc) return rc;
   // the rows of this context's stripe; the kernels index the plane by IMAGE row: the base pointer is that of row 0
   HIPCHK(c, hipMemcpy2DAsync(c->alpha_dev, w * sizeof(float), host_plane + y0 * stride_floats, stride_floats * sizeof(float),
@@ -816,7 +425,7 @@ int jxlhip_set_alpha(jxlhip_ctx* c, const float* host_plane, size_t stride_float
 // as AddNoiseStage skips it (noise.h:37-42).
 int jxlhip_set_noise(jxlhip_ctx* c, const float lut[8], uint32_t visible_frame_index, uint32_t nonvisible_frame_index) {
   if (!c || !lut) return JXLHIP_ERR_INVALID_ARGUMENT;
-  if (!c->children.empty()) return Fail(c, JXLHIP_ERR_UNSUPPORTED, "noise on a multi-device context");
+  if (c->multi) return Fail(c, JXLHIP_ERR_UNSUPPORTED, "noise on a multi-device context");
   if (!c->have_frame) return Fail(c, JXLHIP_ERR_STATE, "set_noise before frame_begin");
   if (c->f.group_y0 != 0 || c->f.group_rows != c->f.ysg) return Fail(c, JXLHIP_ERR_UNSUPPORTED, "noise with stripes");
   if (c->p.undo_orientation > 1) return Fail(c, JXLHIP_ERR_UNSUPPORTED, "noise with undo_orientation %u", c->p.undo_orientation);
@@ -831,7 +440,8 @@ int jxlhip_set_noise(jxlhip_ctx* c, const float lut[8], uint32_t visible_frame_i
       NoiseJumpTable(t.data());
       return t;
     }();
-    HIPCHK(c, hipMalloc((void**)&c->noise_jump, table.size() * sizeof(uint32_t)));
+    const int rc = c->noise_jump.Reserve(c, table.size());
+    if (rc) return rc;
     HIPCHK(c, hipMemcpyAsync(c->noise_jump, table.data(), table.size() * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
   }
   memcpy(c->noise_lut, lut, sizeof(c->noise_lut));
@@ -848,7 +458,7 @@ static int64_t SplineRound(float v) { return fabsf(v) < 9.0e18f ? (int64_t)llrou
 // size and base colour correlation, binned by 64 x 16 tile for k_splines; frame_begin resets to "no splines".
 int jxlhip_set_splines(jxlhip_ctx* c, const jxlhip_splines* s) {
   if (!c) return JXLHIP_ERR_INVALID_ARGUMENT;
-  if (!c->children.empty()) return Fail(c, JXLHIP_ERR_UNSUPPORTED, "splines on a multi-device context");
+  if (c->multi) return Fail(c, JXLHIP_ERR_UNSUPPORTED, "splines on a multi-device context");
   if (!c->have_frame) return Fail(c, JXLHIP_ERR_STATE, "set_splines before frame_begin");
   if (c->f.group_y0 != 0 || c->f.group_rows != c->f.ysg) return Fail(c, JXLHIP_ERR_UNSUPPORTED, "splines with stripes");
   if (c->p.undo_orientation > 1)
@@ -911,11 +521,11 @@ int jxlhip_set_splines(jxlhip_ctx* c, const jxlhip_splines* s) {
   }
   for (uint32_t t = 0, a = 0; t < tiles; t++)
     if (ht[t + 1] != ht[t]) ht[tiles + 1 + entries + a++] = t;
-  if ((rc = Grow(c, &c->spl_segs, &c->spl_segs_items, hs.size()))) return rc;
-  if ((rc = Grow(c, &c->spl_tiles, &c->spl_tiles_items, ht.size()))) return rc;
+  if ((rc = c->spl_segs.Reserve(c, hs.size()))) return rc;
+  if ((rc = c->spl_tiles.Reserve(c, ht.size()))) return rc;
   HIPCHK(c, hipMemcpyAsync(c->spl_segs, hs.data(), hs.size() * sizeof(SplineSeg), hipMemcpyHostToDevice, c->stream));
   HIPCHK(c, hipMemcpyAsync(c->spl_tiles, ht.data(), ht.size() * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
-  if (!c->spl_ev) HIPCHK(c, hipEventCreateWithFlags(&c->spl_ev, hipEventDisableTiming));
+  HIPCHK(c, c->spl_ev.Create());
   HIPCHK(c, hipEventRecord(c->spl_ev, c->stream));
   c->spl_ev_pending = true;
   c->spl_tiles_x = tx;
@@ -931,614 +541,6 @@ int jxlhip_noise_rng_state(uint32_t visible_frame_index, uint32_t nonvisible_fra
   if (!state) return JXLHIP_ERR_INVALID_ARGUMENT;
   NoiseStateAfter(visible_frame_index, nonvisible_frame_index, x0, y0, fills, state);
   return JXLHIP_OK;
-}
-
-int jxlhip_upload_side_info(jxlhip_ctx* c, const uint8_t* ac_strategy, const int32_t* raw_quant,
-                            const uint8_t* epf_sharpness, const int8_t* ytox_map,
-                            const int8_t* ytob_map, const float* const dc[3],
-                            const float* dequant_table) {
-  if (!c) return JXLHIP_ERR_INVALID_ARGUMENT;
-  if (!c->children.empty()) {
-    for (jxlhip_ctx* k : c->children) {
-      const int rc = jxlhip_upload_side_info(k, ac_strategy, raw_quant, epf_sharpness, ytox_map, ytob_map, dc, dequant_table);
-      if (rc) return MultiCheck(c, k, rc);
-    }
-    return JXLHIP_OK;
-  }
-  if (!c->have_frame) return Fail(c, JXLHIP_ERR_STATE, "upload_side_info before frame_begin");
-  if (!ac_strategy || !raw_quant || !ytox_map || !ytob_map || !dc || !dc[0] || !dc[1] ||
-      !dc[2] || !dequant_table || (c->p.lf.epf_iters > 0 && !epf_sharpness))
-    return Fail(c, JXLHIP_ERR_INVALID_ARGUMENT, "null side-info pointer");
-  HIPCHK(c, hipSetDevice(c->device));
-  int rc;
-  if ((rc = EnsureUploadBuffers(c))) return rc;
-  // frame_begin has just started this frame's hand-over (serial, sparse table parity, arena): starting another one
-  // here would advance the serial twice per frame -- the double-buffered offset table would then sit on ONE parity
-  // and wait for the previous frame's copy every time -- and would drop groups submitted before the side info.  Only
-  // a frame handed over AGAIN (a second upload_side_info without a frame_begin) starts over.
-  if (c->handover_fresh) c->handover_fresh = false;
-  else if ((rc = BeginHandover(c))) return rc;
-  const DevFrame& f = c->f;
-  const size_t nb = (size_t)f.xsb * f.ysb;
-  const size_t nt = (size_t)f.xtiles * ((f.ysb + 7) / 8);
-  const jxlhip_frame_inputs& in = c->up_inputs;
-  hipStream_t st = c->stream;
-  HIPCHK(c, hipMemcpyAsync((void*)in.ac_strategy, ac_strategy, nb, hipMemcpyHostToDevice, st));
-  HIPCHK(c, hipMemcpyAsync((void*)in.raw_quant, raw_quant, nb * 4, hipMemcpyHostToDevice, st));
-  if (epf_sharpness)
-    HIPCHK(c, hipMemcpyAsync((void*)in.epf_sharpness, epf_sharpness, nb, hipMemcpyHostToDevice, st));
-  HIPCHK(c, hipMemcpyAsync((void*)in.ytox_map, ytox_map, nt, hipMemcpyHostToDevice, st));
-  HIPCHK(c, hipMemcpyAsync((void*)in.ytob_map, ytob_map, nt, hipMemcpyHostToDevice, st));
-  for (int ch = 0; ch < 3; ch++)
-    HIPCHK(c, hipMemcpyAsync((void*)in.dc[ch], dc[ch], nb * 4, hipMemcpyHostToDevice, st));
-  HIPCHK(c, hipMemcpyAsync((void*)in.dequant_table, dequant_table,
-                           sizeof(float) * JXLHIP_DEQUANT_TABLE_FLOATS, hipMemcpyHostToDevice, st));
-  ApplyInputs(c, &in);
-  c->have_inputs = true;
-  c->blocks_done = false;
-  return JXLHIP_OK;
-}
-
-// JXLHIP_CODESTREAM_VERBOSE: the longest single wait of the upload path during one AC phase, microseconds
-// [0] a pinned slot (AcquireSlot), [1] one hipMemcpyAsync call, [2] one hipEventRecord call
-static std::atomic<int64_t> g_upload_wait_us[3];
-static std::atomic<bool> g_upload_wait_on{false};
-struct UploadWaitClock {
-  int which;
-  std::chrono::steady_clock::time_point t0;
-  explicit UploadWaitClock(int w) : which(w) {
-    if (g_upload_wait_on.load(std::memory_order_relaxed)) t0 = std::chrono::steady_clock::now();
-  }
-  ~UploadWaitClock() {
-    if (!g_upload_wait_on.load(std::memory_order_relaxed)) return;
-    const int64_t us = std::chrono::duration_cast<std::chrono::microseconds>(std::chrono::steady_clock::now() - t0).count();
-    int64_t seen = g_upload_wait_us[which].load(std::memory_order_relaxed);
-    while (seen < us && !g_upload_wait_us[which].compare_exchange_weak(seen, us, std::memory_order_relaxed)) {
-    }
-  }
-};
-
-static int jxlhip_submit_group_ev(jxlhip_ctx* c, uint32_t group_idx, const void* const coeffs[3],
-                                  size_t ncoeffs, hipEvent_t done);
-
-int jxlhip_submit_group(jxlhip_ctx* c, uint32_t group_idx, const void* const coeffs[3],
-                        size_t ncoeffs) {
-  return jxlhip_submit_group_ev(c, group_idx, coeffs, ncoeffs, nullptr);
-}
-
-// `done` (optional) is recorded behind the three copies on the slot's stream
-static int jxlhip_submit_group_ev(jxlhip_ctx* c, uint32_t group_idx, const void* const coeffs[3],
-                                  size_t ncoeffs, hipEvent_t done) {
-  if (!c || !coeffs) return JXLHIP_ERR_INVALID_ARGUMENT;
-  if (!c->children.empty()) {
-    if (!c->have_frame) return Fail(c, JXLHIP_ERR_STATE, "submit_group before frame_begin");
-    const int o = MultiOwner(c, group_idx);
-    if (o < 0) return Fail(c, JXLHIP_ERR_INVALID_ARGUMENT, "bad group %u", group_idx);
-    return MultiCheck(c, c->children[o], jxlhip_submit_group_ev(c->children[o], group_idx, coeffs, ncoeffs, done));
-  }
-  if (!c->have_frame) return Fail(c, JXLHIP_ERR_STATE, "submit_group before frame_begin");
-  const DevFrame& f = c->f;
-  if (group_idx >= f.xsg * f.ysg || ncoeffs > JXLHIP_GROUP_COEFFS || !coeffs[0] || !coeffs[1] ||
-      !coeffs[2])
-    return Fail(c, JXLHIP_ERR_INVALID_ARGUMENT, "bad group %u / ncoeffs %zu", group_idx, ncoeffs);
-  const size_t esz = f.coeff_type == JXLHIP_COEFF_I16 ? 2 : 4;
-  int slot;
-  {
-    // only the bookkeeping is serialised: the copies themselves are issued concurrently by the
-    // runner's threads (with the lock around them, ~400 hipMemcpyAsync calls per 4K frame were
-    // a 4.5 ms serial floor of the whole upload path).  A thread issues its three copies and
-    // then its event on ONE stream in program order, so the event still follows its copies
-    // however other threads' calls interleave on that stream.
-    std::lock_guard<std::mutex> lock(c->pool_mu);
-    if (hipSetDevice(c->device) != hipSuccess) return JXLHIP_ERR_HIP;
-    // (re)sized for THIS frame's group count and coefficient type: a context reused for a larger
-    // frame or another coefficient type must not write past the previous frame's allocation
-    if (!c->up_coeffs[0] || c->up_groups != f.xsg * f.ysg || c->up_esz != esz) {
-      int rc = EnsureUploadBuffers(c);
-      if (rc) return rc;
-    }
-    slot = (int)(c->pool_next++ % kPoolStreams);
-    c->pool_dirty[slot] = true;
-  }
-  if (hipSetDevice(c->device) != hipSuccess) return JXLHIP_ERR_HIP;
-  const size_t chan = (size_t)JXLHIP_GROUP_COEFFS * esz;
-  char* dst0 = (char*)c->up_coeffs[0] + (size_t)group_idx * 3 * chan;
-  if ((const char*)coeffs[1] == (const char*)coeffs[0] + chan && (const char*)coeffs[2] == (const char*)coeffs[0] + 2 * chan) {
-    // the three channels sit in one staging slot: one copy up to the last used coefficient
-    hipError_t e;
-    {
-      UploadWaitClock w(1);
-      e = hipMemcpyAsync(dst0, coeffs[0], 2 * chan + ncoeffs * esz, hipMemcpyHostToDevice, c->pool[slot]);
-    }
-    if (e != hipSuccess) return Fail(c, JXLHIP_ERR_HIP, "submit_group: %s", hipGetErrorString(e));
-  } else {
-    for (int ch = 0; ch < 3; ch++) {
-      hipError_t e = hipMemcpyAsync(dst0 + ch * chan, coeffs[ch], ncoeffs * esz, hipMemcpyHostToDevice, c->pool[slot]);
-      if (e != hipSuccess) return Fail(c, JXLHIP_ERR_HIP, "submit_group: %s", hipGetErrorString(e));
-    }
-  }
-  if (done && hipEventRecord(done, c->pool[slot]) != hipSuccess)
-    return Fail(c, JXLHIP_ERR_HIP, "submit_group: event record failed");
-  return JXLHIP_OK;
-}
-
-// ---- sparse hand-off ------------------------------------------------------------------------------------------
-// A single-pass, 16-bit group crosses PCIe as its NON-ZERO coefficients: 16 header bytes (three counts) + one
-// (position << 16 | value) word per non-zero, the three channels' lists back to back -- nine out of ten
-// coefficients of a d1.0 frame are zero, and the dense stream is 384 KB per group whatever it holds (8K: 196 MB per
-// frame).  The compact groups of one runner thread are collected in a staging slot and go up TOGETHER: one
-// hipMemcpyAsync costs ~15 us inside the runtime whatever thread issues it, serialised -- 510 per-group copies
-// were an 8 ms floor under an 8K frame however many threads decoded.  sp_dev is a per-frame bump arena;
-// sp_off_host[parity][g] says where group g's header landed (0xFFFFFFFF: handed over densely); BeginDecode uploads
-// that table and k_expand_sparse rebuilds the dense block stream (zero + scatter) behind the uploads.
-// entries per channel (X, Y, B), one slot's worth in total: the luma list can take EVERY coefficient of the group (a
-// noise patch at d1.0 has 45 000 non-zero luma coefficients in a group), the chroma lists a quarter each
-static constexpr uint32_t kSparseCap[3] = {16382u, 65536u, 16382u};
-static constexpr size_t kSparseStride = 3u * (size_t)JXLHIP_GROUP_COEFFS * 2u;     // arena bytes per group, worst case
-static constexpr int kBatchGroups = 96;
-
-struct SparseBatch {  // what one runner thread has collected (in its own heap buffer: a pinned staging slot is only
-  std::vector<uint8_t> buf;  // held for the moment of the copy -- more threads than slots must not starve each other)
-  size_t used = 0;
-  int n = 0;
-  uint32_t group[kBatchGroups];
-  uint32_t at[kBatchGroups];  // byte offset of the group's header inside the slot
-};
-
-static int AcquireSlot(jxlhip_ctx* c, size_t slot_bytes, int* out);
-static void ReleaseSlot(jxlhip_ctx* c, int slot, bool uploaded);
-
-
-// the batch goes up as one copy through a pinned staging slot; its groups' headers are entered into the offset table
-static int SparseFlush(jxlhip_ctx* c, SparseBatch* b) {
-  if (b->n == 0) return JXLHIP_OK;
-  int slot = -1;
-  int rc;
-  {
-    UploadWaitClock w(0);
-    rc = AcquireSlot(c, kSparseStride, &slot);
-  }
-  if (rc) return rc;
-  memcpy(c->stage[slot], b->buf.data(), b->used);
-  const size_t bytes = (b->used + 255) & ~(size_t)255;
-  const size_t off = c->sp_arena_used.fetch_add(bytes);
-  int stream;
-  {
-    std::lock_guard<std::mutex> lock(c->pool_mu);
-    stream = (int)(c->pool_next++ % kPoolStreams);
-    c->pool_dirty[stream] = true;
-  }
-  if (off + bytes > c->sp_bytes) rc = Fail(c, JXLHIP_ERR_STATE, "sparse arena overflow");
-  if (!rc && hipSetDevice(c->device) != hipSuccess) rc = JXLHIP_ERR_HIP;
-  if (!rc) {
-    hipError_t e;
-    {
-      UploadWaitClock w(1);
-      e = hipMemcpyAsync(c->sp_dev + off, c->stage[slot], b->used, hipMemcpyHostToDevice, c->pool[stream]);
-    }
-    if (e != hipSuccess) {
-      rc = Fail(c, JXLHIP_ERR_HIP, "sparse submit: %s", hipGetErrorString(e));
-    } else {
-      UploadWaitClock w(2);
-      if (hipEventRecord(c->stage_ev[slot], c->pool[stream]) != hipSuccess) rc = Fail(c, JXLHIP_ERR_HIP, "sparse submit: event record failed");
-    }
-  }
-  if (!rc) {
-    uint32_t* table = c->sp_off_host[c->frame_serial & 1u];
-    for (int i = 0; i < b->n; i++) table[b->group[i]] = (uint32_t)((off + b->at[i]) >> 4);
-    c->sp_any.store(true);
-  }
-  ReleaseSlot(c, slot, rc == JXLHIP_OK);
-  b->used = 0;
-  b->n = 0;
-  return rc;
-}
-
-// One group, single pass, decoded into `scratch` (kSparseStride bytes) and appended to the batch.
-// JXLHIP_ERR_RANGE: not representable (a chroma channel with more than kSparseCap non-zeros, a value outside 16 bits):
-// the caller hands the group over densely.
-static int SparseAppend(jxlhip_ctx* c, SparseBatch* b, uint8_t* scratch, const jxlhip_ac_pass* pass, uint32_t shift,
-                        uint32_t group_idx, const uint8_t* ac_strategy, const int32_t* raw_quant, const uint8_t* quant_dc,
-                        const uint8_t* data, size_t size, size_t* bit_pos) {
-  const DevFrame& f = c->f;
-  uint32_t* const ent[3] = {(uint32_t*)(scratch + 16), (uint32_t*)(scratch + 16) + kSparseCap[0],
-                            (uint32_t*)(scratch + 16) + kSparseCap[0] + kSparseCap[1]};
-  uint32_t cnt[3] = {0, 0, 0};
-  size_t pos = *bit_pos, ncoeffs = 0;
-  int rc = jxlhip_ac_group_decode_sparse(pass, f.xsb, f.ysb, group_idx % f.xsg, group_idx / f.xsg, ac_strategy, raw_quant, quant_dc,
-                                         data, size, &pos, shift, ent, kSparseCap, cnt, &ncoeffs);
-  if (rc) return rc;
-  *bit_pos = pos;
-  const size_t bytes = 16 + 4 * ((size_t)cnt[0] + cnt[1] + cnt[2]);
-  if (b->buf.size() < kSparseStride) b->buf.resize(kSparseStride);
-  if (b->n && (b->used + bytes > kSparseStride || b->n == kBatchGroups)) {
-    if ((rc = SparseFlush(c, b))) return rc;
-  }
-  uint8_t* dst = b->buf.data() + b->used;
-  uint32_t* hdr = (uint32_t*)dst;
-  hdr[0] = cnt[0], hdr[1] = cnt[1], hdr[2] = cnt[2], hdr[3] = 0;
-  memcpy(dst + 16, ent[0], (size_t)cnt[0] * 4);
-  memcpy(dst + 16 + (size_t)cnt[0] * 4, ent[1], (size_t)cnt[1] * 4);
-  memcpy(dst + 16 + ((size_t)cnt[0] + cnt[1]) * 4, ent[2], (size_t)cnt[2] * 4);
-  b->group[b->n] = group_idx;
-  b->at[b->n] = (uint32_t)b->used;
-  b->n++;
-  b->used += (bytes + 15) & ~(size_t)15;
-  return JXLHIP_OK;
-}
-
-static bool SparseEligible(const jxlhip_ctx* c, uint32_t num_passes) {
-  return c->sparse_upload && num_passes == 1 && c->f.coeff_type == JXLHIP_COEFF_I16 && c->sp_dev &&
-         c->sp_bytes >= (size_t)c->f.xsg * c->f.ysg * kSparseStride && c->sp_off_items >= (size_t)c->f.xsg * c->f.ysg;
-}
-
-static int SubmitPassesImpl(jxlhip_ctx* c, uint32_t num_passes, const jxlhip_ac_pass* const* passes, const uint32_t* shifts,
-                            uint32_t group_idx, const uint8_t* ac_strategy, const int32_t* raw_quant, const uint8_t* quant_dc,
-                            const uint8_t* const* data, const size_t* sizes, size_t* bit_pos, bool allow_sparse,
-                            std::vector<uint8_t>* dense_scratch = nullptr);
-
-// f1: entropy-decode all passes of one AC group into a pinned staging slot and
-// queue its upload.  The slot is reused only after its copies completed.
-int jxlhip_ac_group_decode_submit_passes(jxlhip_ctx* c, uint32_t num_passes,
-                                         const jxlhip_ac_pass* const* passes, const uint32_t* shifts,
-                                         uint32_t group_idx, const uint8_t* ac_strategy,
-                                         const int32_t* raw_quant, const uint8_t* quant_dc,
-                                         const uint8_t* const* data, const size_t* sizes,
-                                         size_t* bit_pos) {
-  if (!c || !passes || !ac_strategy || !raw_quant || !data || !sizes || !bit_pos || num_passes == 0 ||
-      num_passes > 11)
-    return JXLHIP_ERR_INVALID_ARGUMENT;
-  for (uint32_t p = 0; p < num_passes; p++)
-    if (!passes[p] || !data[p] || (shifts && shifts[p] > 3)) return JXLHIP_ERR_INVALID_ARGUMENT;
-  if (!c->have_frame) return Fail(c, JXLHIP_ERR_STATE, "ac_group_decode_submit before frame_begin");
-  if (!c->children.empty()) {
-    const int o = MultiOwner(c, group_idx);
-    if (o < 0) return Fail(c, JXLHIP_ERR_INVALID_ARGUMENT, "bad group %u", group_idx);
-    return MultiCheck(c, c->children[o], jxlhip_ac_group_decode_submit_passes(c->children[o], num_passes, passes, shifts, group_idx, ac_strategy,
-                                                                              raw_quant, quant_dc, data, sizes, bit_pos));
-  }
-  return SubmitPassesImpl(c, num_passes, passes, shifts, group_idx, ac_strategy, raw_quant, quant_dc, data, sizes, bit_pos, true);
-}
-
-// A free pinned staging slot (state 1 = owned by the caller); blocks while all are in flight / owned.
-static int AcquireSlot(jxlhip_ctx* c, size_t slot_bytes, int* out) {
-  int slot = -1;
-  std::unique_lock<std::mutex> lock(c->stage_mu);
-  if (hipSetDevice(c->device) != hipSuccess) return JXLHIP_ERR_HIP;
-  // kStageChunk more slots (the chunk after the ones there are), free
-  auto grow = [&]() -> int {
-    const int k = c->stage_count / kStageChunk;
-    if (c->stage_count + kStageChunk > c->stage_cap)
-      return Fail(c, JXLHIP_ERR_OUT_OF_MEMORY, "pinned staging: the cap of %d slots (JXLHIP_STAGE_SLOTS) is reached", c->stage_cap);
-    // the events first, then the chunk, and only then is anything published: a failure half way leaves nothing
-    // behind that a later grow() would overwrite (an event that exists already is simply kept)
-    for (int i = c->stage_count; i < c->stage_count + kStageChunk; i++)
-      if (!c->stage_ev[i] && hipEventCreateWithFlags(&c->stage_ev[i], hipEventDisableTiming) != hipSuccess)
-        return Fail(c, JXLHIP_ERR_HIP, "event creation failed");
-    void* chunk = nullptr;
-    if (StageAlloc(c, &chunk, (size_t)kStageChunk * c->stage_bytes) != JXLHIP_OK)
-      return Fail(c, JXLHIP_ERR_OUT_OF_MEMORY, "pinned staging allocation failed");
-    c->stage_chunk[k] = chunk;
-    for (int i = c->stage_count; i < c->stage_count + kStageChunk; i++) {
-      c->stage[i] = (char*)chunk + (size_t)(i - c->stage_count) * c->stage_bytes;
-      c->stage_state[i] = 0;
-    }
-    c->stage_count += kStageChunk;
-    return JXLHIP_OK;
-  };
-  if (c->stage_bytes < slot_bytes) {
-    // (re)allocation: only when no thread owns a slot
-    c->stage_cv.wait(lock, [&] {
-      for (int i = 0; i < c->stage_count; i++)
-        if (c->stage_state[i] == 1) return false;
-      return true;
-    });
-    if (c->stage_bytes < slot_bytes) {
-      for (int i = 0; i < c->stage_count; i++) {
-        if (c->stage_state[i] == 2) (void)hipEventSynchronize(c->stage_ev[i]);
-        c->stage[i] = nullptr;
-        c->stage_state[i] = 0;
-      }
-      for (void*& chunk : c->stage_chunk) {
-        if (chunk) StageFree(c, chunk);
-        chunk = nullptr;
-      }
-      c->stage_bytes = slot_bytes;
-      c->stage_count = 0;
-      static_assert(kStageSlotsFirst % kStageChunk == 0 && kStageSlots % kStageChunk == 0, "whole chunks");
-      while (c->stage_count < kStageSlotsFirst) {
-        const int rc = grow();
-        if (rc) return rc;
-      }
-    }
-  }
-  while (slot < 0) {
-    int pending = -1;
-    for (int i = 0; i < c->stage_count && slot < 0; i++) {
-      if (c->stage_state[i] == 0) slot = i;
-      else if (c->stage_state[i] == 2) {
-        if (hipEventQuery(c->stage_ev[i]) == hipSuccess) slot = i;
-        else if (pending < 0) pending = i;
-      }
-    }
-    if (slot >= 0) break;
-    if (c->stage_count < c->stage_cap) {  // nothing free: more slots rather than a wait
-      slot = c->stage_count;
-      const int rc = grow();
-      if (rc) return rc;
-    } else if (pending >= 0) {  // every slot is in flight: wait for one upload, without keeping the others out
-      hipEvent_t ev = c->stage_ev[pending];
-      lock.unlock();
-      const hipError_t e = hipEventSynchronize(ev);
-      lock.lock();
-      if (e != hipSuccess) return JXLHIP_ERR_HIP;
-    } else {  // every slot is owned by another decoding thread
-      c->stage_cv.wait(lock);
-    }
-  }
-  c->stage_state[slot] = 1;
-  *out = slot;
-  return JXLHIP_OK;
-}
-
-static void ReleaseSlot(jxlhip_ctx* c, int slot, bool uploaded) {
-  {
-    std::lock_guard<std::mutex> lock(c->stage_mu);
-    c->stage_state[slot] = uploaded ? 2 : 0;
-  }
-  c->stage_cv.notify_all();
-}
-
-static int SubmitPassesImpl(jxlhip_ctx* c, uint32_t num_passes, const jxlhip_ac_pass* const* passes, const uint32_t* shifts,
-                            uint32_t group_idx, const uint8_t* ac_strategy, const int32_t* raw_quant, const uint8_t* quant_dc,
-                            const uint8_t* const* data, const size_t* sizes, size_t* bit_pos, bool allow_sparse,
-                            std::vector<uint8_t>* dense_scratch) {
-  const DevFrame& f = c->f;
-  if (group_idx >= f.xsg * f.ysg) return Fail(c, JXLHIP_ERR_INVALID_ARGUMENT, "bad group %u", group_idx);
-  const size_t esz = f.coeff_type == JXLHIP_COEFF_I16 ? 2 : 4;
-  const size_t slot_bytes = 3 * (size_t)JXLHIP_GROUP_COEFFS * esz;
-  int rc = JXLHIP_ERR_RANGE;
-  if (allow_sparse && SparseEligible(c, num_passes)) {  // one group = one batch (callers that submit groups one by one)
-    SparseBatch b;
-    std::vector<uint8_t> scratch(kSparseStride);
-    rc = SparseAppend(c, &b, scratch.data(), passes[0], shifts ? shifts[0] : 0, group_idx, ac_strategy, raw_quant, quant_dc,
-                      data[0], sizes[0], &bit_pos[0]);
-    const int rf = SparseFlush(c, &b);
-    if (rc == JXLHIP_OK) rc = rf;
-  }
-  if (rc == JXLHIP_ERR_RANGE) {
-    // the dense form: decoded into the caller's (or a local) heap buffer; a pinned staging slot is held only for the
-    // copy into it and the submit -- a textured group decodes for milliseconds, and with the slots held that long the
-    // 33rd such group of a frame waited for the first to finish
-    std::vector<uint8_t> local;
-    std::vector<uint8_t>& buf = dense_scratch ? *dense_scratch : local;
-    if (buf.size() < slot_bytes) buf.resize(slot_bytes);
-    char* base = (char*)buf.data();
-    void* const ch[3] = {base, base + (size_t)JXLHIP_GROUP_COEFFS * esz, base + 2 * (size_t)JXLHIP_GROUP_COEFFS * esz};
-    size_t ncoeffs = 0;
-    memset(base, 0, slot_bytes);  // coefficients are accumulated (dec_group.cc:527-531)
-    rc = JXLHIP_OK;
-    for (uint32_t p = 0; p < num_passes && rc == JXLHIP_OK; p++)
-      rc = jxlhip_ac_group_decode(passes[p], f.xsb, f.ysb, group_idx % f.xsg, group_idx / f.xsg, ac_strategy,
-                                  raw_quant, quant_dc, data[p], sizes[p], &bit_pos[p], shifts ? shifts[p] : 0,
-                                  f.coeff_type, ch, &ncoeffs);
-    if (rc == JXLHIP_OK) {
-      int slot = -1;
-      {
-        UploadWaitClock w(0);
-        rc = AcquireSlot(c, slot_bytes, &slot);
-      }
-      if (rc) return rc;
-      char* pinned = (char*)c->stage[slot];
-      const size_t chan = (size_t)JXLHIP_GROUP_COEFFS * esz;
-      memcpy(pinned, base, 2 * chan + ncoeffs * esz);  // (what jxlhip_submit_group_ev sends up in one copy)
-      const void* const src[3] = {pinned, pinned + chan, pinned + 2 * chan};
-      rc = jxlhip_submit_group_ev(c, group_idx, src, ncoeffs, c->stage_ev[slot]);
-      ReleaseSlot(c, slot, rc == JXLHIP_OK);
-    }
-  }
-  if (rc == JXLHIP_ERR_BAD_STREAM) return Fail(c, rc, "AC group %u: invalid entropy-coded data", group_idx);
-  return rc;
-}
-
-namespace {
-struct GroupsJob {
-  jxlhip_ctx* c;
-  uint32_t num_passes, num_groups;
-  const jxlhip_ac_pass* const* passes;
-  const uint32_t* shifts;
-  const uint8_t* acs;
-  const int32_t* raw_quant;
-  const uint8_t* quant_dc;
-  const uint8_t* const* sections;
-  const size_t* sizes;
-  size_t* end_bits = nullptr;
-  std::atomic<int> status{JXLHIP_OK};
-  // the runner's task t is group order[t]: the sections with the most bytes first.  A group's decode time follows its
-  // bytes (r = 0.98 on the 8K d1.0 stream of tests/data) and a textured patch takes five times the mean: handed out
-  // last, one such group is the tail the whole frame waits for
-  std::vector<uint32_t> order;
-  // JXLHIP_CODESTREAM_VERBOSE=1: per task {start ms, end ms, thread}
-  std::vector<float> timeline;
-  std::chrono::steady_clock::time_point t0;
-  // sparse hand-off: one open staging slot + one decode scratch per runner thread
-  bool sparse = false;
-  std::vector<SparseBatch> batch;
-  std::vector<std::vector<uint8_t>> scratch;
-  std::vector<std::vector<uint8_t>> dense;  // per runner thread: where a group that goes up densely is decoded
-  // test hook (JXLHIP_TEST_RANGE_GROUP=g, read by GroupsInit): group g reports a coefficient beyond 16 bits on the
-  // 16-bit attempt -- no stream libjxl's encoder writes at ordinary settings does, and the redo with int32 buffers
-  // (through the single runner call and through the three barriers) has to be reachable by a test
-  int64_t test_range_group = -1;
-};
-int GroupsInit(void* opaque, size_t num_threads) {
-  GroupsJob* j = static_cast<GroupsJob*>(opaque);
-  if (j->sparse) {
-    j->batch.assign(num_threads ? num_threads : 1, SparseBatch());
-    j->scratch.assign(num_threads ? num_threads : 1, std::vector<uint8_t>());
-  }
-  j->dense.assign(num_threads ? num_threads : 1, std::vector<uint8_t>());
-  j->test_range_group = jxlhip_env::Get().test_range_group.load(std::memory_order_relaxed);
-  return 0;
-}
-// A section this large carries more non-zeros than a chroma list of the sparse form takes (kSparseCap; the stream above:
-// every group that overflowed had 32 000 bytes or more, none below 34 300 fitted with much to spare): decoded densely
-// straight away instead of finding that out three quarters of the way through the sparse attempt.
-static constexpr size_t kDenseFirstBytes = 30000;
-void GroupsFuncBody(GroupsJob* j, uint32_t g, size_t thread);
-// one group, with its entry in the timeline (keyed by group) when one is kept
-void GroupsOne(GroupsJob* j, uint32_t g, size_t thread) {
-  if (j->timeline.empty()) return GroupsFuncBody(j, g, thread);
-  const double a = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - j->t0).count();
-  GroupsFuncBody(j, g, thread);
-  const double b = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - j->t0).count();
-  j->timeline[3 * (size_t)g] = (float)a, j->timeline[3 * (size_t)g + 1] = (float)b, j->timeline[3 * (size_t)g + 2] = (float)thread;
-}
-void GroupsFunc(void* opaque, uint32_t task, size_t thread) {
-  GroupsJob* j = static_cast<GroupsJob*>(opaque);
-  GroupsOne(j, j->order.empty() ? task : j->order[task], thread);
-}
-void GroupsFuncBody(GroupsJob* j, uint32_t g, size_t thread) {
-  if (j->status.load(std::memory_order_relaxed) != JXLHIP_OK) return;
-  const DevFrame& f = j->c->f;
-  const uint32_t gy = g / f.xsg;
-  if (gy < f.group_y0 || gy >= f.group_y0 + f.group_rows) return;  // another rank's stripe
-  const uint8_t* data[11];
-  size_t sizes[11], pos[11];
-  for (uint32_t p = 0; p < j->num_passes; p++) {
-    data[p] = j->sections[(size_t)p * j->num_groups + g];
-    sizes[p] = j->sizes[(size_t)p * j->num_groups + g];
-    pos[p] = 0;
-  }
-  int rc = JXLHIP_ERR_RANGE;
-  if ((int64_t)g == j->test_range_group && f.coeff_type == JXLHIP_COEFF_I16) {
-    int expected = JXLHIP_OK;
-    j->status.compare_exchange_strong(expected, JXLHIP_ERR_RANGE);
-    return;
-  }
-  if (j->sparse && thread < j->batch.size() && sizes[0] < kDenseFirstBytes) {
-    if (j->scratch[thread].empty()) j->scratch[thread].resize(kSparseStride);
-    rc = SparseAppend(j->c, &j->batch[thread], j->scratch[thread].data(), j->passes[0], j->shifts ? j->shifts[0] : 0, g, j->acs,
-                      j->raw_quant, j->quant_dc, data[0], sizes[0], &pos[0]);
-    if (rc == JXLHIP_ERR_BAD_STREAM) Fail(j->c, rc, "AC group %u: invalid entropy-coded data", g);
-  }
-  if (rc == JXLHIP_ERR_RANGE)
-    rc = SubmitPassesImpl(j->c, j->num_passes, j->passes, j->shifts, g, j->acs, j->raw_quant, j->quant_dc, data, sizes, pos, false,
-                          thread < j->dense.size() ? &j->dense[thread] : nullptr);
-  if (rc != JXLHIP_OK) {
-    int expected = JXLHIP_OK;
-    j->status.compare_exchange_strong(expected, rc);
-  } else if (j->end_bits) {
-    for (uint32_t p = 0; p < j->num_passes; p++) j->end_bits[(size_t)p * j->num_groups + g] = pos[p];
-  }
-}
-}  // namespace
-
-// (JXLHIP_CODESTREAM_VERBOSE) per thread: first start, last end, busy time; and the longest task
-static void GroupsTimelineReport(const GroupsJob& job) {
-  const double total = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - job.t0).count();
-  struct Th { float first = 1e9f, last = 0, busy = 0; int n = 0; };
-  std::vector<Th> th(1024);
-  int used = 0;
-  float longest = 0, first_min = 1e9f, first_max = 0, last_min = 1e9f, busy_min = 1e9f, busy_max = 0;
-  for (uint32_t t = 0; t < job.num_groups; t++) {
-    const float a = job.timeline[3 * (size_t)t], b = job.timeline[3 * (size_t)t + 1];
-    if (b <= 0) continue;
-    Th& h = th[std::min<size_t>((size_t)job.timeline[3 * (size_t)t + 2], 1023)];
-    h.first = std::min(h.first, a), h.last = std::max(h.last, b), h.busy += b - a, h.n++;
-    longest = std::max(longest, b - a);
-  }
-  for (const Th& h : th) {
-    if (!h.n) continue;
-    used++;
-    first_min = std::min(first_min, h.first), first_max = std::max(first_max, h.first), last_min = std::min(last_min, h.last);
-    busy_min = std::min(busy_min, h.busy), busy_max = std::max(busy_max, h.busy);
-  }
-  fprintf(stderr, "[codestream] longest single wait in the upload path: pinned slot %.2f ms, hipMemcpyAsync %.2f ms, hipEventRecord %.2f ms\n",
-          g_upload_wait_us[0].exchange(0) * 1e-3, g_upload_wait_us[1].exchange(0) * 1e-3, g_upload_wait_us[2].exchange(0) * 1e-3);
-  fprintf(stderr, "[codestream] AC groups: %.2f ms after the runner call began, on %d threads; first group started at %.2f, last thread started at "
-          "%.2f, first finished at %.2f; busy per thread %.2f .. %.2f ms; longest group %.2f ms\n", total, used, first_min, first_max, last_min,
-          busy_min, busy_max, longest);
-}
-
-int jxlhip_ac_groups_decode_submit(jxlhip_ctx* c, jxlhip_parallel_runner runner, void* runner_opaque,
-                                   uint32_t num_passes, const jxlhip_ac_pass* const* passes,
-                                   const uint32_t* shifts, const uint8_t* ac_strategy,
-                                   const int32_t* raw_quant, const uint8_t* quant_dc,
-                                   const uint8_t* const* sections, const size_t* sizes) {
-  return jxlhip_ac_groups_decode_submit_ex(c, runner, runner_opaque, num_passes, passes, shifts, ac_strategy, raw_quant, quant_dc,
-                                           sections, sizes, nullptr);
-}
-
-int jxlhip_ac_groups_decode_submit_ex(jxlhip_ctx* c, jxlhip_parallel_runner runner, void* runner_opaque,
-                                      uint32_t num_passes, const jxlhip_ac_pass* const* passes,
-                                      const uint32_t* shifts, const uint8_t* ac_strategy,
-                                      const int32_t* raw_quant, const uint8_t* quant_dc,
-                                      const uint8_t* const* sections, const size_t* sizes, size_t* end_bits) {
-  if (!c || !passes || !ac_strategy || !raw_quant || !sections || !sizes || num_passes == 0 || num_passes > 11)
-    return JXLHIP_ERR_INVALID_ARGUMENT;
-  if (!c->have_frame) return Fail(c, JXLHIP_ERR_STATE, "ac_groups_decode_submit before frame_begin");
-  if (!c->children.empty()) {  // every child takes the groups of its stripe (GroupsFunc skips the others)
-    for (jxlhip_ctx* k : c->children) {
-      const int rc = jxlhip_ac_groups_decode_submit_ex(k, runner, runner_opaque, num_passes, passes, shifts, ac_strategy, raw_quant,
-                                                       quant_dc, sections, sizes, end_bits);
-      if (rc) return MultiCheck(c, k, rc);
-    }
-    return JXLHIP_OK;
-  }
-  GroupsJob job;
-  job.c = c;
-  job.num_passes = num_passes;
-  job.num_groups = c->f.xsg * c->f.ysg;
-  job.passes = passes;
-  job.shifts = shifts;
-  job.acs = ac_strategy;
-  job.raw_quant = raw_quant;
-  job.quant_dc = quant_dc;
-  job.sections = sections;
-  job.sizes = sizes;
-  job.end_bits = end_bits;
-  job.sparse = SparseEligible(c, num_passes);
-  if (runner && job.num_groups > 1) {
-    std::vector<uint64_t> key(job.num_groups);  // (bytes over all passes) << 32 | ~group: sorted descending = largest first, ties in group order
-    for (uint32_t g = 0; g < job.num_groups; g++) {
-      uint64_t bytes = 0;
-      for (uint32_t p = 0; p < num_passes; p++) bytes += sizes[(size_t)p * job.num_groups + g];
-      key[g] = (std::min<uint64_t>(bytes, 0xFFFFFFFFu) << 32) | (uint32_t)~g;
-    }
-    std::sort(key.begin(), key.end(), std::greater<uint64_t>());
-    job.order.resize(job.num_groups);
-    for (uint32_t t = 0; t < job.num_groups; t++) job.order[t] = ~(uint32_t)key[t];
-  }
-  const bool verbose = jxlhip_env::Get().codestream_verbose.load(std::memory_order_relaxed);
-  if (verbose) {
-    job.timeline.assign(3 * (size_t)job.num_groups, 0.0f);
-    job.t0 = std::chrono::steady_clock::now();
-  }
-  if (runner) {
-    if (runner(runner_opaque, &job, GroupsInit, GroupsFunc, 0, job.num_groups) != 0)
-      return Fail(c, JXLHIP_ERR_STATE, "parallel runner failed");
-    if (verbose) GroupsTimelineReport(job);
-  } else {
-    GroupsInit(&job, 1);
-    for (uint32_t g = 0; g < job.num_groups; g++) GroupsFunc(&job, g, 0);
-  }
-  for (SparseBatch& b : job.batch) {  // what the threads still hold
-    const int rc = SparseFlush(c, &b);
-    if (rc != JXLHIP_OK) {
-      int expected = JXLHIP_OK;
-      job.status.compare_exchange_strong(expected, rc);
-    }
-  }
-  return job.status.load();
-}
-
-int jxlhip_ac_group_decode_submit(jxlhip_ctx* c, const jxlhip_ac_pass* pass, uint32_t group_idx,
-                                  const uint8_t* ac_strategy, const int32_t* raw_quant,
-                                  const uint8_t* quant_dc, const uint8_t* data, size_t size,
-                                  size_t* bit_pos) {
-  return jxlhip_ac_group_decode_submit_passes(c, 1, &pass, nullptr, group_idx, ac_strategy, raw_quant,
-                                              quant_dc, &data, &size, bit_pos);
 }
 
 // ---- decode -------------------------------------------------------------------
@@ -1576,7 +578,7 @@ int LaunchPhase1(jxlhip_ctx* c, int fused = 0, const FilterParams* emit = nullpt
   {
     constexpr uint32_t kOthers32 = (1u << 8) | (1u << 9) | (1u << 10) | (1u << 11);  // 32x8 .. 16x32
     const bool lone32 = (f.used_acs & (1u << 5)) && !(f.used_acs & kOthers32);
-    f.mfma32 = (c->mfma > 0 || (c->mfma < 0 && lone32)) ? c->tables + 1600 : nullptr;
+    f.mfma32 = (c->mfma > 0 || (c->mfma < 0 && lone32)) ? c->tables + kTabMfma32 : nullptr;
     // DCT16X16: the same rule against the 16-point row-per-lane family (16x8, 8x16), only when no 32-point class
     // pulls the merged launch in anyway, and on frames of 16 Mpx and more (measured, all-DCT16X16 frames: 8K blocks
     // 132 -> 118 us, 16x16 + 32x32 176 -> 161 us; 4K 33.6 -> 37.6 us: the butterflies stay; on the mixed c3 frame a
@@ -1584,7 +586,7 @@ int LaunchPhase1(jxlhip_ctx* c, int fused = 0, const FilterParams* emit = nullpt
     constexpr uint32_t kOthers16 = (1u << 6) | (1u << 7);
     const bool lone16 = (f.used_acs & (1u << 4)) && !(f.used_acs & (kOthers16 | kOthers32)) &&
                         (!(f.used_acs & (1u << 5)) || f.mfma32) && (uint64_t)f.xsize * f.ysize >= (16u << 20);
-    f.mfma16 = (c->mfma > 0 || (c->mfma < 0 && lone16)) ? c->tables + 1600 + 2048 : nullptr;
+    f.mfma16 = (c->mfma > 0 || (c->mfma < 0 && lone16)) ? c->tables + kTabMfma16 : nullptr;
   }
   f.zero_counts = capturing ? nullptr : c->counts + (size_t)(block ^ 1) * kCountStride;
   if (fused == 2)  // a stripe: every cell "from the planes" until k_prepare says otherwise (whole frames: k_prepare writes every cell)
@@ -1595,9 +597,8 @@ int LaunchPhase1(jxlhip_ctx* c, int fused = 0, const FilterParams* emit = nullpt
   ProfBegin(c);
   LaunchPrepare(f, wl, c->p.lf.epf_iters > 0, c->p.lf.epf_quant_mul, c->lut, st);
   ProfMark(c, JXLHIP_KERNEL_PREPARE);
-  LaunchBlocks(f, wl, cells, c->tables, c->tables + 512, st, emit);
+  LaunchBlocks(f, wl, cells, c->tables + kTabWc, c->tables + kTabResample, st, emit);
   ProfMark(c, JXLHIP_KERNEL_BLOCKS);
-  ProfEnd(c);
   HIPCHK(c, hipGetLastError());
   if (!capturing) {
     c->counts_clean[block ^ 1] = true;
@@ -1639,16 +640,14 @@ int LaunchFiltersRows(jxlhip_ctx* c, const FilterParams& fp, uint32_t fy0, uint3
     if (rc) return rc;
     if (declined) return Fail(c, JXLHIP_ERR_STATE, "fused EPF0 kernel refused a frame FusedEpf0Supported accepted");
     ProfMark(c, JXLHIP_KERNEL_FILTERS);
-    ProfEnd(c);
-    HIPCHK(c, hipGetLastError());
+      HIPCHK(c, hipGetLastError());
     return JXLHIP_OK;
   }
   if (fused) {
     if (!LaunchFused(f, fp, (int)c->p.lf.gab, (int)c->p.lf.epf_iters, (int)c->p.output_kind, c->stream))
       return Fail(c, JXLHIP_ERR_STATE, "fused kernel refused a frame FusedSupported accepted");
     ProfMark(c, JXLHIP_KERNEL_FUSED);
-    ProfEnd(c);
-    HIPCHK(c, hipGetLastError());
+      HIPCHK(c, hipGetLastError());
     return JXLHIP_OK;
   }
   bool fast = false;
@@ -1664,7 +663,6 @@ int LaunchFiltersRows(jxlhip_ctx* c, const FilterParams& fp, uint32_t fy0, uint3
                              (int)c->p.output_kind, c->stream) != 0)
     return Fail(c, JXLHIP_ERR_INVALID_ARGUMENT, "unsupported filter configuration");
   ProfMark(c, JXLHIP_KERNEL_FILTERS);
-  ProfEnd(c);
   HIPCHK(c, hipGetLastError());
   return JXLHIP_OK;
 }
@@ -1723,8 +721,8 @@ int BeginDecode(jxlhip_ctx* c) {
     const size_t ng = (size_t)c->f.xsg * c->f.ysg;
     const int par = (int)(c->frame_serial & 1u);
     int rc;
-    if ((rc = Grow(c, &c->sp_off_dev, &c->sp_off_dev_items, ng))) return rc;
-    HIPCHK(c, hipMemcpyAsync(c->sp_off_dev, c->sp_off_host[par], ng * 4, hipMemcpyHostToDevice, st));
+    if ((rc = c->sp_off_dev.Reserve(c, ng))) return rc;
+    HIPCHK(c, hipMemcpyAsync(c->sp_off_dev, c->sp_off_host[par].p, ng * 4, hipMemcpyHostToDevice, st));
     HIPCHK(c, hipEventRecord(c->sp_off_ev[par], st));
     c->sp_off_pending[par] = true;
     LaunchExpandSparse(c->sp_dev, c->sp_off_dev, (int16_t*)c->up_coeffs[0], c->f.group_y0 * c->f.xsg, c->f.group_rows * c->f.xsg, st);
@@ -1739,9 +737,8 @@ int CheckOutArgs(jxlhip_ctx* c, void* out, size_t out_stride, size_t out_plane_s
     if (out_stride < (size_t)f.xsize * 12 || (out_stride & 3))
       return Fail(c, JXLHIP_ERR_INVALID_ARGUMENT, "RGB row stride %zu too small", out_stride);
   } else if (c->p.output_kind == JXLHIP_OUT_PACKED) {
-    const jxlhip_output_format& o = c->p.out_format;
-    const size_t ssz = o.sample_type == JXLHIP_SAMPLE_U8 ? 1 : (o.sample_type == JXLHIP_SAMPLE_F32 ? 4 : 2);
-    if (out_stride < (size_t)f.xsize * o.num_channels * ssz || (out_stride % ssz) ||
+    const size_t ssz = OutSampleBytes(c->p.out_format);
+    if (out_stride < (size_t)f.xsize * OutPixelBytes(c) || (out_stride % ssz) ||
         ((uintptr_t)out % ssz))
       return Fail(c, JXLHIP_ERR_INVALID_ARGUMENT, "packed row stride %zu / alignment invalid", out_stride);
   } else if (out_stride < f.xsize ||
@@ -1764,7 +761,7 @@ int jxlhip_decode_blocks(jxlhip_ctx* c) {
   // A whole frame through the split calls stays two-phase (the taps read the planes).
   const bool stripe = c->f.group_y0 != 0 || c->f.group_rows != c->f.ysg;
   c->blocks_fused = stripe && WantFused(c);
-  if (c->blocks_fused && (rc = Grow(c, &c->cell_info, &c->cell_info_items, (size_t)c->f.xsb * c->f.ysb))) return rc;
+  if (c->blocks_fused && (rc = c->cell_info.Reserve(c, (size_t)c->f.xsb * c->f.ysb))) return rc;
   rc = LaunchPhase1(c, c->blocks_fused ? 2 : 0);
   if (rc) return rc;
   c->blocks_done = true;
@@ -1872,17 +869,9 @@ int jxlhip_stripe_finish(jxlhip_ctx* c, const float* recv_up, const float* recv_
 static int DecodeFrameCoded(jxlhip_ctx* c, void* out, size_t out_stride, size_t out_plane_stride);
 static int DecodeFrameFeatures(jxlhip_ctx* c, void* out, size_t out_stride, size_t out_plane_stride);
 
-// bytes of one interleaved output pixel (0: planar XYB)
-static size_t OutPixelBytes(const jxlhip_ctx* c) {
-  if (c->p.output_kind == JXLHIP_OUT_LINEAR_RGB_F32) return 12;
-  if (c->p.output_kind != JXLHIP_OUT_PACKED) return 0;
-  const jxlhip_output_format& o = c->p.out_format;
-  return (size_t)o.num_channels * (o.sample_type == JXLHIP_SAMPLE_U8 ? 1 : (o.sample_type == JXLHIP_SAMPLE_F32 ? 4 : 2));
-}
-
 int jxlhip_decode_frame(jxlhip_ctx* c, void* out, size_t out_stride, size_t out_plane_stride) {
   if (!c) return JXLHIP_ERR_INVALID_ARGUMENT;
-  if (!c->children.empty()) return out ? MultiDecodeFrame(c, out, nullptr, out_stride, out_plane_stride) : JXLHIP_ERR_INVALID_ARGUMENT;
+  if (c->multi) return out ? MultiDecodeFrame(c, out, nullptr, out_stride, out_plane_stride) : JXLHIP_ERR_INVALID_ARGUMENT;
   if (!c->have_frame) return Fail(c, JXLHIP_ERR_STATE, "decode needs frame_begin + inputs");
   if (c->noise_on || c->splines_on) return DecodeFrameFeatures(c, out, out_stride, out_plane_stride);
   if (c->p.undo_orientation <= 1) return DecodeFrameCoded(c, out, out_stride, out_plane_stride);
@@ -1897,7 +886,7 @@ int jxlhip_decode_frame(jxlhip_ctx* c, void* out, size_t out_stride, size_t out_
   HIPCHK(c, hipSetDevice(c->device));
   const size_t row = ((size_t)f.xsize * bpp + 255) & ~(size_t)255;
   int rc;
-  if ((rc = Grow(c, &c->orient_dev, &c->orient_bytes, (size_t)f.ysize * row))) return rc;
+  if ((rc = c->orient_dev.Reserve(c, (size_t)f.ysize * row))) return rc;
   if ((rc = DecodeFrameCoded(c, c->orient_dev, row, 0))) return rc;
   if (!LaunchOrient(c->orient_dev, row, f.xsize, f.ysize, (uint32_t)bpp, c->p.undo_orientation, out, out_stride, c->stream))
     return Fail(c, JXLHIP_ERR_UNSUPPORTED, "undo_orientation %u with %zu-byte pixels", c->p.undo_orientation, bpp);
@@ -1932,7 +921,7 @@ static int DecodeFrameCoded(jxlhip_ctx* c, void* out, size_t out_stride, size_t 
   // halo rows to pay for and wins at 4K as well (95.8 vs 83.4 Gpx/s); never when the caller's used_acs says the
   // frame has no DCT8 block -- then the slab is only a detour (configs[4]: 76.1 vs 79.6 Gpx/s)
   if (WantFused(c) && f.group_y0 == 0 && f.group_rows == f.ysg) {
-    if ((rc = Grow(c, &c->cell_info, &c->cell_info_items, (size_t)f.xsb * f.ysb))) return rc;
+    if ((rc = c->cell_info.Reserve(c, (size_t)f.xsb * f.ysb))) return rc;
     if ((rc = LaunchPhase1(c, 1))) return rc;
     c->blocks_done = false;  // the planes do not hold the whole frame
     return LaunchFiltersRows(c, fp, f.y0, f.y1, true);
@@ -1958,7 +947,7 @@ static int DecodeFrameFeatures(jxlhip_ctx* c, void* out, size_t out_stride, size
   HIPCHK(c, hipSetDevice(c->device));
   const uint32_t ns = (f.xsize + 63u) & ~63u;
   const size_t nplane = (size_t)ns * f.ysize;
-  if ((rc = Grow(c, &c->noise_buf, &c->noise_floats, (c->noise_on ? 6 : 3) * nplane))) return rc;
+  if ((rc = c->noise_buf.Reserve(c, (c->noise_on ? 6 : 3) * nplane))) return rc;
   const uint32_t kind = c->p.output_kind;
   c->p.output_kind = JXLHIP_OUT_XYB_PLANAR;
   rc = DecodeFrameCoded(c, c->noise_buf, ns, nplane);
@@ -2006,7 +995,6 @@ static int DecodeFrameFeatures(jxlhip_ctx* c, void* out, size_t out_stride, size
     if (!LaunchNoise(N, fp, (int)kind, c->stream)) return Fail(c, JXLHIP_ERR_INVALID_ARGUMENT, "noise output kind %u", kind);
     ProfMark(c, JXLHIP_KERNEL_NOISE);
   }
-  ProfEnd(c);
   HIPCHK(c, hipGetLastError());
   return JXLHIP_OK;
 }
@@ -2015,7 +1003,7 @@ static int DecodeFrameFeatures(jxlhip_ctx* c, void* out, size_t out_stride, size
 // into a context-owned device frame, one strided device-to-host copy, synchronised.
 int jxlhip_decode_frame_host(jxlhip_ctx* c, void* host_out, size_t out_stride, size_t out_plane_stride) {
   if (!c || !host_out) return JXLHIP_ERR_INVALID_ARGUMENT;
-  if (!c->children.empty()) {
+  if (c->multi) {
     const int rc = MultiDecodeFrame(c, nullptr, host_out, out_stride, out_plane_stride);
     return rc ? rc : MultiSync(c);
   }
@@ -2024,18 +1012,15 @@ int jxlhip_decode_frame_host(jxlhip_ctx* c, void* host_out, size_t out_stride, s
   const bool transposed = c->p.undo_orientation >= 5;  // the oriented frame is ysize wide, xsize high
   const size_t rows = transposed ? f.xsize : f.y1 - f.y0;
   const size_t cols = transposed ? f.ysize : f.xsize;
-  size_t row_bytes;
-  if (c->p.output_kind == JXLHIP_OUT_LINEAR_RGB_F32) row_bytes = cols * 12;
-  else if (c->p.output_kind == JXLHIP_OUT_PACKED) row_bytes = cols * OutPixelBytes(c);
-  else row_bytes = cols * 4;
   const bool planar = c->p.output_kind == JXLHIP_OUT_XYB_PLANAR;
+  const size_t row_bytes = cols * (planar ? 4 : OutPixelBytes(c));
   const size_t host_row = planar ? out_stride * 4 : out_stride;
   if (host_row < row_bytes) return Fail(c, JXLHIP_ERR_INVALID_ARGUMENT, "host row stride %zu too small", out_stride);
   const size_t dev_row = (row_bytes + 255) & ~(size_t)255;
   const size_t planes = planar ? 3 : 1;
   HIPCHK(c, hipSetDevice(c->device));
   int rc;
-  if ((rc = Grow(c, &c->host_frame_dev, &c->host_frame_bytes, planes * rows * dev_row))) return rc;
+  if ((rc = c->host_frame_dev.Reserve(c, planes * rows * dev_row))) return rc;
   rc = planar ? jxlhip_decode_frame(c, c->host_frame_dev, dev_row / 4, rows * dev_row / 4)
               : jxlhip_decode_frame(c, c->host_frame_dev, dev_row, 0);
   if (rc) return rc;
@@ -2052,29 +1037,25 @@ int jxlhip_decode_frame_pinned(jxlhip_ctx* c, const void** host_frame, size_t* s
   const bool transposed = p.undo_orientation >= 5;
   const size_t rows = transposed ? p.xsize : p.ysize;
   const size_t cols = transposed ? p.ysize : p.xsize;
-  const size_t row_bytes = cols * (p.output_kind == JXLHIP_OUT_PACKED ? OutPixelBytes(c) : 12);
+  const size_t row_bytes = cols * OutPixelBytes(c);
   const size_t pitch = (row_bytes + 63) & ~(size_t)63;
-  if (rows * pitch > c->pinned_frame_bytes) {
-    if (c->pinned_frame) {
+  if (rows * pitch > c->pinned_frame.bytes) {
+    if (c->pinned_frame.p) {
       int rc0 = jxlhip_sync(c);  // nothing may still be writing the old frame
       if (rc0) return rc0;
-      StageFree(c, c->pinned_frame);
-      c->pinned_frame = nullptr;
-      c->pinned_frame_bytes = 0;
     }
-    if (StageAlloc(c, &c->pinned_frame, rows * pitch)) return Fail(c, JXLHIP_ERR_OUT_OF_MEMORY, "pinned frame of %zu bytes", rows * pitch);
-    c->pinned_frame_bytes = rows * pitch;
+    if (c->pinned_frame.Alloc(&c->mm, rows * pitch)) return Fail(c, JXLHIP_ERR_OUT_OF_MEMORY, "pinned frame of %zu bytes", rows * pitch);
   }
-  const int rc = jxlhip_decode_frame_host(c, c->pinned_frame, pitch, 0);
+  const int rc = jxlhip_decode_frame_host(c, c->pinned_frame.p, pitch, 0);
   if (rc) return rc;
-  *host_frame = c->pinned_frame;
+  *host_frame = c->pinned_frame.p;
   *stride = pitch;
   return JXLHIP_OK;
 }
 
 int jxlhip_sync(jxlhip_ctx* c) {
   if (!c) return JXLHIP_ERR_INVALID_ARGUMENT;
-  if (!c->children.empty()) return MultiSync(c);
+  if (c->multi) return MultiSync(c);
   HIPCHK(c, hipSetDevice(c->device));
   int32_t flag[2] = {0, 0};
   HIPCHK(c, hipMemcpyAsync(flag, c->error_flag, sizeof(flag), hipMemcpyDeviceToHost, c->stream));
@@ -2124,7 +1105,8 @@ int jxlhip_get_sigma(jxlhip_ctx* c, float** inv_sigma, size_t* row_stride) {
 int jxlhip_set_concurrency_hint(jxlhip_ctx* c, int frames_in_flight) {
   if (!c || frames_in_flight < 1) return JXLHIP_ERR_INVALID_ARGUMENT;
   c->concurrency = frames_in_flight;
-  for (jxlhip_ctx* k : c->children) k->concurrency = frames_in_flight;
+  if (c->multi)
+    for (MultiChild& k : c->multi->kids) k.ctx->concurrency = frames_in_flight;
   return JXLHIP_OK;
 }
 
@@ -2155,7 +1137,6 @@ int jxlhip_profile_read(jxlhip_ctx* c, float ms[JXLHIP_KERNEL_COUNT],
       }
     }
   }
-  for (auto& m : c->marks) (void)hipEventDestroy(m.ev);
   c->marks.clear();
   return JXLHIP_OK;
 }
@@ -2238,7 +1219,7 @@ int jxlhip_dequant_dc_groups(jxlhip_ctx* c, const int32_t* const quant_dc[3], fl
     mul_dc[ch] = (f.inv_global_scale / (float)c->p.quant_dc) * dq[ch];  // quantizer.h:133-139
   const size_t n = (size_t)f.xsb * f.ysb;
   int rc;
-  if ((rc = Grow(c, &c->dc_tmp, &c->dc_tmp_floats, 3 * n))) return rc;
+  if ((rc = c->dc_tmp.Reserve(c, 3 * n))) return rc;
   float* tmp[3] = {c->dc_tmp, c->dc_tmp + n, c->dc_tmp + 2 * n};
   const uint8_t* prec_dev = nullptr;
   if (extra_precision) {
@@ -2250,7 +1231,7 @@ int jxlhip_dequant_dc_groups(jxlhip_ctx* c, const int32_t* const quant_dc[3], fl
       any |= extra_precision[i] != 0;
     }
     if (any) {
-      if ((rc = Grow(c, &c->dc_prec, &c->dc_prec_bytes, ndc))) return rc;
+      if ((rc = c->dc_prec.Reserve(c, ndc))) return rc;
       HIPCHK(c, hipMemcpyAsync(c->dc_prec, extra_precision, ndc, hipMemcpyHostToDevice, c->stream));
       // the source may be a short-lived host array: the copy is pageable, hence already staged by
       // the runtime when hipMemcpyAsync returns
@@ -2263,7 +1244,3 @@ int jxlhip_dequant_dc_groups(jxlhip_ctx* c, const int32_t* const quant_dc[3], fl
   return JXLHIP_OK;
 }
 
-#include "multi.inc"
-#include "codestream.inc"
-
-}  // extern "C"

@@ -1,4 +1,4 @@
-// env_switches.h -- debug / test switches from the environment, shared by context.hip and entropy.cc (modular.inc).
+// env_switches.h -- debug / test switches from the environment, shared by the host units of the C ABI (context.h) and entropy.cc (modular.inc).
 #ifndef JXLHIP_ENV_SWITCHES_H_
 #define JXLHIP_ENV_SWITCHES_H_
 #include <atomic>

@@ -1,5 +1,4 @@
-// multi.inc -- jxlhip_create_multi: one context over several devices of one process (include/jxl_hip.h).
-// Included by context.hip inside extern "C".
+// multi.hip -- jxlhip_create_multi: one context over several devices of one process (include/jxl_hip.h).
 //
 // The parent keeps one child context per stripe of AC-group rows.  A frame on a multi context:
 //   jxlhip_frame_begin        every child gets the frame with its stripe (stripe_group_y0 / _rows)
@@ -10,40 +9,34 @@
 //                             of children 1.. reach devices[0]'s frame by peer copies (the final gather)
 //   jxlhip_decode_frame_host  as above, but every child copies its own stripe to the host rows
 
-namespace {
+#include "context.h"
+
+namespace jxlhip {
 
 int MultiCheck(jxlhip_ctx* c, jxlhip_ctx* child, int rc) {
   if (rc != JXLHIP_OK) snprintf(c->err, sizeof(c->err), "device %d: %s", child->device, child->err);
   return rc;
 }
 
+// every child's stream is idle before anything is released: a neighbour may still be pulling halo rows
 void MultiDestroy(jxlhip_ctx* c) {
-  for (size_t i = 0; i < c->children.size(); i++) {
-    jxlhip_ctx* k = c->children[i];
-    (void)hipSetDevice(k->device);
-    if (k->stream) (void)hipStreamSynchronize(k->stream);
-    for (int w = 0; w < 2; w++) {
-      if (i < c->halo_send[w].size() && c->halo_send[w][i]) (void)hipFree(c->halo_send[w][i]);
-      if (i < c->halo_recv[w].size() && c->halo_recv[w][i]) (void)hipFree(c->halo_recv[w][i]);
-      if (i < c->ev_halo[w].size() && c->ev_halo[w][i]) (void)hipEventDestroy(c->ev_halo[w][i]);
-      if (i < c->ev_pull[w].size() && c->ev_pull[w][i]) (void)hipEventDestroy(c->ev_pull[w][i]);
-    }
-    if (i < c->stripe_out.size() && c->stripe_out[i]) (void)hipFree(c->stripe_out[i]);
-    if (i < c->ev_done.size() && c->ev_done[i]) (void)hipEventDestroy(c->ev_done[i]);
-    jxlhip_destroy(k);
+  for (MultiChild& k : c->multi->kids) {
+    (void)hipSetDevice(k.ctx->device);
+    if (k.ctx->stream) (void)hipStreamSynchronize(k.ctx->stream);
   }
-  if (c->alpha_host) StageFree(c, c->alpha_host);
+  for (MultiChild& k : c->multi->kids) jxlhip_destroy(k.ctx);
   DeleteCtx(c);
 }
 
 // contiguous stripes of group rows, the first ysg % n one row taller (libjxl_amd/stripes.py stripe_partition)
-void MultiPartition(uint32_t ysg, size_t n, std::vector<std::pair<uint32_t, uint32_t>>* out) {
-  out->clear();
+static void MultiPartition(uint32_t ysg, std::vector<MultiChild>* kids) {
+  const size_t n = kids->size();
   const uint32_t base = ysg / (uint32_t)n, rem = ysg % (uint32_t)n;
   uint32_t g0 = 0;
   for (size_t i = 0; i < n; i++) {
     const uint32_t rows = base + (i < rem ? 1u : 0u);
-    out->push_back({g0, rows});
+    (*kids)[i].group_y0 = g0;
+    (*kids)[i].group_rows = rows;
     g0 += rows;
   }
 }
@@ -53,44 +46,36 @@ int MultiFrameBegin(jxlhip_ctx* c, const jxlhip_frame_params* p) {
     return Fail(c, JXLHIP_ERR_INVALID_ARGUMENT, "a multi-device context cuts the stripes itself");
   if (p->undo_orientation > 1) return Fail(c, JXLHIP_ERR_UNSUPPORTED, "undo_orientation over several devices");
   const uint32_t ysg = (p->ysize + 255) / 256;
-  const size_t n = c->children.size();
-  if (ysg < n) return Fail(c, JXLHIP_ERR_INVALID_ARGUMENT, "%u group rows cannot be split over %zu stripes", ysg, n);
-  MultiPartition(ysg, n, &c->stripes);
-  for (size_t i = 0; i < n; i++) {
+  std::vector<MultiChild>& kids = c->multi->kids;
+  if (ysg < kids.size())
+    return Fail(c, JXLHIP_ERR_INVALID_ARGUMENT, "%u group rows cannot be split over %zu stripes", ysg, kids.size());
+  MultiPartition(ysg, &kids);
+  for (MultiChild& k : kids) {
     jxlhip_frame_params q = *p;
-    q.stripe_group_y0 = c->stripes[i].first;
-    q.stripe_group_rows = c->stripes[i].second;
-    const int rc = jxlhip_frame_begin(c->children[i], &q);
-    if (rc) return MultiCheck(c, c->children[i], rc);
+    q.stripe_group_y0 = k.group_y0;
+    q.stripe_group_rows = k.group_rows;
+    const int rc = jxlhip_frame_begin(k.ctx, &q);
+    if (rc) return MultiCheck(c, k.ctx, rc);
   }
   c->p = *p;
-  c->f = c->children[0]->f;  // geometry of the frame (xsb, xsg ...); stripe fields are child 0's
+  c->f = kids[0].ctx->f;  // geometry of the frame (xsb, xsg ...); stripe fields are child 0's
   c->have_frame = true;
   // halo staging: dense [3][halo][xsize] floats, send and receive, up and down
   const size_t floats = (size_t)3 * c->f.halo * c->f.xsize;
-  for (size_t i = 0; i < n; i++) {
-    jxlhip_ctx* k = c->children[i];
-    HIPCHK(c, hipSetDevice(k->device));
-    if (c->halo_floats[i] < floats) {
-      for (int w = 0; w < 2; w++) {
-        if (c->halo_send[w][i]) HIPCHK(c, hipFree(c->halo_send[w][i]));
-        if (c->halo_recv[w][i]) HIPCHK(c, hipFree(c->halo_recv[w][i]));
-        c->halo_send[w][i] = c->halo_recv[w][i] = nullptr;
-        if (floats) {
-          HIPCHK(c, hipMalloc((void**)&c->halo_send[w][i], floats * sizeof(float)));
-          HIPCHK(c, hipMalloc((void**)&c->halo_recv[w][i], floats * sizeof(float)));
-        }
-      }
-      c->halo_floats[i] = floats;
-    }
+  for (MultiChild& k : kids) {
+    HIPCHK(c, hipSetDevice(k.ctx->device));
+    int rc;
+    for (int w = 0; w < 2 && floats; w++)
+      if ((rc = k.halo_send[w].Reserve(c, floats)) || (rc = k.halo_recv[w].Reserve(c, floats))) return rc;
   }
   return JXLHIP_OK;
 }
 
 int MultiOwner(const jxlhip_ctx* c, uint32_t group_idx) {
   const uint32_t gy = group_idx / c->f.xsg;
-  for (size_t i = 0; i < c->stripes.size(); i++)
-    if (gy >= c->stripes[i].first && gy < c->stripes[i].first + c->stripes[i].second) return (int)i;
+  const std::vector<MultiChild>& kids = c->multi->kids;
+  for (size_t i = 0; i < kids.size(); i++)
+    if (gy >= kids[i].group_y0 && gy < kids[i].group_y0 + kids[i].group_rows) return (int)i;
   return -1;
 }
 
@@ -99,20 +84,17 @@ int MultiDecodeFrame(jxlhip_ctx* c, void* out_dev, void* host_out, size_t out_st
   if (!c->have_frame) return Fail(c, JXLHIP_ERR_STATE, "decode needs frame_begin + inputs");
   if (c->p.output_kind == JXLHIP_OUT_XYB_PLANAR)
     return Fail(c, JXLHIP_ERR_UNSUPPORTED, "planar XYB output on a multi-device context");
-  const size_t n = c->children.size();
+  std::vector<MultiChild>& kids = c->multi->kids;
+  const size_t n = kids.size();
   const uint32_t halo = c->f.halo;
   const size_t halo_bytes = (size_t)3 * halo * c->f.xsize * sizeof(float);
-  size_t row_bytes;
-  if (c->p.output_kind == JXLHIP_OUT_LINEAR_RGB_F32) row_bytes = (size_t)c->f.xsize * 12;
-  else {
-    const jxlhip_output_format& o = c->p.out_format;
-    row_bytes = (size_t)c->f.xsize * o.num_channels * (o.sample_type == JXLHIP_SAMPLE_U8 ? 1 : (o.sample_type == JXLHIP_SAMPLE_F32 ? 4 : 2));
-  }
+  const size_t row_bytes = (size_t)c->f.xsize * OutPixelBytes(c);
   if (out_stride < row_bytes) return Fail(c, JXLHIP_ERR_INVALID_ARGUMENT, "row stride %zu too small", out_stride);
   (void)out_plane_stride;
   // ---- phase 1 on every stripe; boundary rows leave for dense staging right behind it
   for (size_t i = 0; i < n; i++) {
-    jxlhip_ctx* k = c->children[i];
+    MultiChild& m = kids[i];
+    jxlhip_ctx* k = m.ctx;
     HIPCHK(c, hipSetDevice(k->device));
     int rc = jxlhip_decode_blocks(k);
     if (rc) return MultiCheck(c, k, rc);
@@ -122,14 +104,14 @@ int MultiDecodeFrame(jxlhip_ctx* c, void* out_dev, void* host_out, size_t out_st
     // waiting on an event that was never recorded is a no-op (first frame).
     if (halo) {
       if (i > 0) {
-        HIPCHK(c, hipStreamWaitEvent(k->stream, c->ev_pull[1][i - 1], 0));  // stripe i-1 read halo_send[0][i]
-        if ((rc = jxlhip_halo_export(k, 0, c->halo_send[0][i]))) return MultiCheck(c, k, rc);
-        HIPCHK(c, hipEventRecord(c->ev_halo[0][i], k->stream));
+        HIPCHK(c, hipStreamWaitEvent(k->stream, kids[i - 1].ev_pull[1], 0));  // stripe i-1 read halo_send[0][i]
+        if ((rc = jxlhip_halo_export(k, 0, m.halo_send[0]))) return MultiCheck(c, k, rc);
+        HIPCHK(c, hipEventRecord(m.ev_halo[0], k->stream));
       }
       if (i + 1 < n) {
-        HIPCHK(c, hipStreamWaitEvent(k->stream, c->ev_pull[0][i + 1], 0));  // stripe i+1 read halo_send[1][i]
-        if ((rc = jxlhip_halo_export(k, 1, c->halo_send[1][i]))) return MultiCheck(c, k, rc);
-        HIPCHK(c, hipEventRecord(c->ev_halo[1][i], k->stream));
+        HIPCHK(c, hipStreamWaitEvent(k->stream, kids[i + 1].ev_pull[0], 0));  // stripe i+1 read halo_send[1][i]
+        if ((rc = jxlhip_halo_export(k, 1, m.halo_send[1]))) return MultiCheck(c, k, rc);
+        HIPCHK(c, hipEventRecord(m.ev_halo[1], k->stream));
       }
     }
   }
@@ -140,14 +122,15 @@ int MultiDecodeFrame(jxlhip_ctx* c, void* out_dev, void* host_out, size_t out_st
   // boundary block rows.  JXLHIP_MULTI_INTERIOR_FIRST=0: everything behind the exchange (round 3's order).
   const bool interior_first = jxlhip_env::Get().multi_interior_first.load(std::memory_order_relaxed) != 0;  // (the tests compare both orders)
   for (size_t i = 0; i < n; i++) {
-    jxlhip_ctx* k = c->children[i];
+    MultiChild& m = kids[i];
+    jxlhip_ctx* k = m.ctx;
     HIPCHK(c, hipSetDevice(k->device));
     int rc;
     const size_t y0 = k->f.y0, rows = k->f.y1 - k->f.y0;
     // stripes on devices[0] write straight into the frame (JXLHIP_MULTI_FORCE_GATHER=1: only stripe 0 does -- lets a
     // single-GPU box exercise the gather copies)
     const bool force_gather = jxlhip_env::Get().multi_force_gather.load(std::memory_order_relaxed);
-    const bool direct = out_dev && k->device == c->children[0]->device && (i == 0 || !force_gather);
+    const bool direct = out_dev && k->device == kids[0].ctx->device && (i == 0 || !force_gather);
     void* dst;
     size_t dst_stride;
     if (direct) {
@@ -158,13 +141,8 @@ int MultiDecodeFrame(jxlhip_ctx* c, void* out_dev, void* host_out, size_t out_st
       // contiguous block of the destination frame and the gather is one peer copy; otherwise a 2-D copy of
       // row_bytes per row: the bytes between row_bytes and out_stride belong to the caller and stay untouched.
       const size_t dense = (out_dev && out_stride == row_bytes) ? row_bytes : ((row_bytes + 255) & ~(size_t)255);
-      if (c->stripe_out_bytes[i] < rows * dense) {
-        if (c->stripe_out[i]) HIPCHK(c, hipFree(c->stripe_out[i]));
-        c->stripe_out[i] = nullptr;
-        HIPCHK(c, hipMalloc((void**)&c->stripe_out[i], rows * dense));
-        c->stripe_out_bytes[i] = rows * dense;
-      }
-      dst = c->stripe_out[i];
+      if ((rc = m.stripe_out.Reserve(c, rows * dense))) return rc;
+      dst = m.stripe_out;
       dst_stride = dense;
     }
     // rows that need a neighbour's halo: the first / last block row (8 >= LoopFilter::Padding(), loop_filter.h:26-29)
@@ -175,18 +153,18 @@ int MultiDecodeFrame(jxlhip_ctx* c, void* out_dev, void* host_out, size_t out_st
       if ((rc = jxlhip_decode_filters_rows(k, dst, dst_stride, 0, ya, yb))) return MultiCheck(c, k, rc);
     }
     if (halo && i > 0) {  // rows from the stripe above = its "down" export
-      HIPCHK(c, hipStreamWaitEvent(k->stream, c->ev_halo[1][i - 1], 0));
-      HIPCHK(c, hipMemcpyPeerAsync(c->halo_recv[0][i], k->device, c->halo_send[1][i - 1], c->children[i - 1]->device,
+      HIPCHK(c, hipStreamWaitEvent(k->stream, kids[i - 1].ev_halo[1], 0));
+      HIPCHK(c, hipMemcpyPeerAsync(m.halo_recv[0], k->device, kids[i - 1].halo_send[1], kids[i - 1].ctx->device,
                                    halo_bytes, k->stream));
-      HIPCHK(c, hipEventRecord(c->ev_pull[0][i], k->stream));
-      if ((rc = jxlhip_halo_import(k, 0, c->halo_recv[0][i]))) return MultiCheck(c, k, rc);
+      HIPCHK(c, hipEventRecord(m.ev_pull[0], k->stream));
+      if ((rc = jxlhip_halo_import(k, 0, m.halo_recv[0]))) return MultiCheck(c, k, rc);
     }
     if (halo && i + 1 < n) {  // rows from the stripe below = its "up" export
-      HIPCHK(c, hipStreamWaitEvent(k->stream, c->ev_halo[0][i + 1], 0));
-      HIPCHK(c, hipMemcpyPeerAsync(c->halo_recv[1][i], k->device, c->halo_send[0][i + 1], c->children[i + 1]->device,
+      HIPCHK(c, hipStreamWaitEvent(k->stream, kids[i + 1].ev_halo[0], 0));
+      HIPCHK(c, hipMemcpyPeerAsync(m.halo_recv[1], k->device, kids[i + 1].halo_send[0], kids[i + 1].ctx->device,
                                    halo_bytes, k->stream));
-      HIPCHK(c, hipEventRecord(c->ev_pull[1][i], k->stream));
-      if ((rc = jxlhip_halo_import(k, 1, c->halo_recv[1][i]))) return MultiCheck(c, k, rc);
+      HIPCHK(c, hipEventRecord(m.ev_pull[1], k->stream));
+      if ((rc = jxlhip_halo_import(k, 1, m.halo_recv[1]))) return MultiCheck(c, k, rc);
     }
     if (ya == k->f.y0 && yb == k->f.y1) {
       if ((rc = jxlhip_decode_filters(k, dst, dst_stride, 0))) return MultiCheck(c, k, rc);
@@ -196,7 +174,7 @@ int MultiDecodeFrame(jxlhip_ctx* c, void* out_dev, void* host_out, size_t out_st
     }
     if (!direct) {
       if (out_dev && out_stride == row_bytes) {  // the gather: this stripe's rows into device 0's frame over the link between the two
-        HIPCHK(c, hipMemcpyPeerAsync((char*)out_dev + y0 * out_stride, c->children[0]->device, dst, k->device,
+        HIPCHK(c, hipMemcpyPeerAsync((char*)out_dev + y0 * out_stride, kids[0].ctx->device, dst, k->device,
                                      rows * row_bytes, k->stream));
       } else if (out_dev) {
         HIPCHK(c, hipMemcpy2DAsync((char*)out_dev + y0 * out_stride, out_stride, dst, dst_stride, row_bytes, rows,
@@ -206,27 +184,27 @@ int MultiDecodeFrame(jxlhip_ctx* c, void* out_dev, void* host_out, size_t out_st
                                    hipMemcpyDeviceToHost, k->stream));
       }
     }
-    HIPCHK(c, hipEventRecord(c->ev_done[i], k->stream));
+    HIPCHK(c, hipEventRecord(m.ev_done, k->stream));
   }
   // whoever consumes the frame on device 0's stream sees all stripes: device-side join, no host wait
   if (out_dev) {
-    jxlhip_ctx* k0 = c->children[0];
+    jxlhip_ctx* k0 = kids[0].ctx;
     HIPCHK(c, hipSetDevice(k0->device));
-    for (size_t i = 1; i < n; i++) HIPCHK(c, hipStreamWaitEvent(k0->stream, c->ev_done[i], 0));
+    for (size_t i = 1; i < n; i++) HIPCHK(c, hipStreamWaitEvent(k0->stream, kids[i].ev_done, 0));
   }
   return JXLHIP_OK;
 }
 
 int MultiSync(jxlhip_ctx* c) {
   int first = JXLHIP_OK;
-  for (jxlhip_ctx* k : c->children) {
-    const int rc = jxlhip_sync(k);
-    if (rc && !first) first = MultiCheck(c, k, rc);
+  for (MultiChild& k : c->multi->kids) {
+    const int rc = jxlhip_sync(k.ctx);
+    if (rc && !first) first = MultiCheck(c, k.ctx, rc);
   }
   return first;
 }
 
-}  // namespace
+}  // namespace jxlhip
 
 int jxlhip_create_multi(const int* devices, int num_devices, const JxlMemoryManagerHip* memory_manager,
                         jxlhip_ctx** out) {
@@ -241,30 +219,22 @@ int jxlhip_create_multi(const int* devices, int num_devices, const JxlMemoryMana
   jxlhip_ctx* c = NewCtx(memory_manager);
   if (!c) return JXLHIP_ERR_OUT_OF_MEMORY;
   c->device = devices[0];
-  const size_t n = (size_t)num_devices;
-  for (int w = 0; w < 2; w++) {
-    c->halo_send[w].assign(n, nullptr);
-    c->halo_recv[w].assign(n, nullptr);
-    c->ev_halo[w].assign(n, nullptr);
-    c->ev_pull[w].assign(n, nullptr);
-  }
-  c->halo_floats.assign(n, 0);
-  c->stripe_out.assign(n, nullptr);
-  c->stripe_out_bytes.assign(n, 0);
-  c->ev_done.assign(n, nullptr);
-  for (size_t i = 0; i < n; i++) {
+  c->multi.reset(new MultiState());  // (a parent from here on: whatever fails below, MultiDestroy takes the children there are)
+  std::vector<MultiChild>& kids = c->multi->kids;
+  kids.reserve((size_t)num_devices);
+  for (size_t i = 0; i < (size_t)num_devices; i++) {
     jxlhip_ctx* k = nullptr;
     const int rc = jxlhip_create_ex(devices[i], memory_manager, &k);
     if (rc) {
       MultiDestroy(c);
       return rc;
     }
-    c->children.push_back(k);
+    kids.emplace_back();
+    MultiChild& m = kids.back();
+    m.ctx = k;
     bool ok = hipSetDevice(devices[i]) == hipSuccess;
-    for (int w = 0; w < 2 && ok; w++)
-      ok = hipEventCreateWithFlags(&c->ev_halo[w][i], hipEventDisableTiming) == hipSuccess &&
-           hipEventCreateWithFlags(&c->ev_pull[w][i], hipEventDisableTiming) == hipSuccess;
-    ok = ok && hipEventCreateWithFlags(&c->ev_done[i], hipEventDisableTiming) == hipSuccess;
+    for (int w = 0; w < 2 && ok; w++) ok = m.ev_halo[w].Create() == hipSuccess && m.ev_pull[w].Create() == hipSuccess;
+    ok = ok && m.ev_done.Create() == hipSuccess;
     if (!ok) {
       MultiDestroy(c);
       return JXLHIP_ERR_HIP;

@@ -1,7 +1,7 @@
 // runner.cc -- libjxl_threads_hip.so: the JxlParallelRunner shipped with the back-end (see
 // include/jxl_threads_hip.h).  Replaces lib/threads/thread_parallel_runner{.cc,_internal.cc} and
 // resizable_parallel_runner.cc behind the same nine C symbols.  Plain host threads: the streams and the pinned
-// staging that the group tasks' uploads use belong to the jxlhip context (context.hip: jxlhip_submit_group picks
+// staging that the group tasks' uploads use belong to the jxlhip context (handover.hip: jxlhip_submit_group picks
 // a stream of its pool per call), so that the back-end works under ANY JxlParallelRunner, this one included.
 //
 // Scheduling: one shared atomic cursor over [begin, end); every participant

@@ -143,7 +143,7 @@ def test_decode_codestream_matches_the_reference_decoder(L, ref, kw, workers):
 ])
 def test_one_runner_call_equals_three_barriers(L, ref, kw, monkeypatch):
     """With a runner the DC groups, AC global and the AC groups are ONE pool of work units in one runner call, the AC
-    groups under a DC group starting when its block info is in (codestream.inc: PipelineJob); JXLHIP_NO_PIPELINE=1 runs
+    groups under a DC group starting when its block info is in (codestream.hip: PipelineJob); JXLHIP_NO_PIPELINE=1 runs
     the three phases of FrameDecoder one after the other (dec_frame.cc:596-703).  Same pixels, bit for bit, same
     coefficient type, for several worker counts -- and equal to the reference decoder's."""
     import torch

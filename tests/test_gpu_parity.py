@@ -317,7 +317,7 @@ def test_graph_replays_interleaved_with_direct_calls_on_one_stream(dq, oracle, f
     between (which would reset the host's "counter block is clean" flags): capture, two direct calls (the second leaves
     block 0 marked clean), a replay, another direct call -- round 5 put captured frames on block 0, so that last call
     started k_prepare on the replay's non-zero counters.  Captured frames now use counter blocks of their own
-    (context.hip: kCaptureBase).  Every frame must be the same pixels, and the stream must report no fault."""
+    (context.hip: kCaptureBlock).  Every frame must be the same pixels, and the stream must report no fault."""
     monkeypatch.setenv("JXLHIP_FUSE", fuse)
     params, t, fr = frames.make_case(1000, 520, mix=synth.MIX_D1, gab=True, epf_iters=1, seed=62)
     cs = torch.cuda.Stream()

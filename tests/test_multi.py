@@ -113,7 +113,7 @@ def _upload(L, ctx, params, t, table_host):
 def test_multi_context_frames_back_to_back_without_sync(oracle, monkeypatch, padded):
     """Ten frames (two different ones, alternating) through one multi context with NO jxlhip_sync in between: the
     persistent halo staging of a stripe may only be overwritten by the next frame's export once the neighbour has
-    pulled the previous frame's rows (ev_pull, multi.inc), and the next frame's uploads must not overtake the
+    pulled the previous frame's rows (ev_pull, multi.hip), and the next frame's uploads must not overtake the
     previous frame's kernels (frame_ev, jxlhip_frame_begin).  padded: the caller's rows are wider than the pixels --
     the gather then is a 2-D copy and the padding bytes stay the caller's."""
     L = abi.load_library()
