@@ -268,7 +268,8 @@ JXLHIP_EXPORT int jxlhip_upload_side_info(
  * (stride_floats per row; 1.0 = opaque), copied into context-owned HBM.  It is written to the output like a
  * colour channel without the transfer function -- what WriteToOutputStage does with input channel alpha_c
  * (stage_write.cc:350-366); not un-premultiplied.  Without this call (jxlhip_frame_begin resets it) alpha is the
- * opaque 1.0 the reference substitutes (:355-360).  On a multi-device context every stripe takes its own rows. */
+ * opaque 1.0 the reference substitutes (:355-360).  On a multi-device context every stripe takes its own rows.
+ * JXLHIP_ERR_UNSUPPORTED on an upsampled frame (jxlhip_set_upsampling). */
 JXLHIP_EXPORT int jxlhip_set_alpha(jxlhip_ctx* ctx, const float* host_plane, size_t stride_floats);
 /* Photon noise of the current frame (FrameHeader::kNoise, what cjxl --photon_noise_iso writes): lut = NoiseParams::lut,
  * the 8 values DecodeNoise reads (lib/jxl/dec_noise.cc:155-165; jxlhip_noise_lut_decode), and the seed indices of
@@ -293,6 +294,22 @@ JXLHIP_EXPORT int jxlhip_set_noise(jxlhip_ctx* ctx, const float lut[8], uint32_t
  * JXLHIP_ERR_UNSUPPORTED on a multi-device context, for a stripe and with undo_orientation > 1; the split calls refuse
  * a spline frame. */
 JXLHIP_EXPORT int jxlhip_set_splines(jxlhip_ctx* ctx, const struct jxlhip_splines* splines);
+/* Upsampling of the current frame (FrameHeader::upsampling = factor: 2, 4 or 8; what cjxl writes by itself from
+ * distance 10 on, and with --resampling).  jxlhip_frame_begin's xsize / ysize are then the CODED size; out_xsize /
+ * out_ysize is the size the frame is upsampled and cropped to (the image), with ceil(out / factor) == coded in both
+ * directions, JXLHIP_ERR_INVALID_ARGUMENT otherwise.  weights = the 15 / 55 / 210 coded weights of that factor from
+ * the image header's transform data (jxlhip_image_header::upsampling{2,4,8}_weights where custom_weights_mask has the
+ * factor's bit), NULL = the format's defaults.  jxlhip_decode_frame then renders the reference's upsampling stage
+ * (render_pipeline/stage_upsampling.cc) where its pipeline has it (dec_cache.cc:194-218): behind the loop filters and
+ * the splines, which are drawn at coded size, in front of noise, which is generated at output size; `out`, its strides
+ * and every output kind are those of an out_xsize x out_ysize frame.  Call it before jxlhip_set_splines (the draw list
+ * is computed for the upsampled size: JXLHIP_ERR_STATE otherwise, also for a reset to factor 1 behind a draw list made
+ * for an upsampled frame).  factor 1 or a new jxlhip_frame_begin resets it;
+ * frames that never call this are untouched.  JXLHIP_ERR_UNSUPPORTED on a multi-device context, for a stripe, with
+ * undo_orientation > 1 and after jxlhip_set_alpha (which refuses an upsampled frame in turn: extra channels of
+ * upsampled frames are outside the back-end); the split calls refuse an upsampled frame. */
+JXLHIP_EXPORT int jxlhip_set_upsampling(jxlhip_ctx* ctx, uint32_t factor, const float* weights, uint32_t out_xsize,
+                                        uint32_t out_ysize);
 /* Host-side check of the noise generator's jump: the state (s0_[i], s1_[i]) of the 8 lanes of
  * Xorshift128Plus(visible_frame_index, nonvisible_frame_index, x0, y0) (lib/jxl/xorshift128plus-inl.h:46-57) after
  * `fills` calls of Fill, computed as the kernel does (one jump-matrix product, then single steps) into state[2 * i],
@@ -419,6 +436,7 @@ enum {
                                  EPF2 + output march that follows is the FILTERS span */
   JXLHIP_KERNEL_NOISE = 5,    /* photon noise (jxlhip_set_noise): k_noise_rng + k_noise_emit behind the frame's path */
   JXLHIP_KERNEL_SPLINES = 6,  /* splines (jxlhip_set_splines): k_splines behind the frame's path, in front of noise */
+  JXLHIP_KERNEL_UPSAMPLE = 7, /* upsampling (jxlhip_set_upsampling): k_upsample behind the splines, in front of noise */
   JXLHIP_KERNEL_COUNT = 8
 };
 /* A hint, not a contract: `frames_in_flight` = how many contexts the caller keeps busy on this device at the same time

@@ -17,11 +17,15 @@
  * Taken: any enumerated colour encoding and ICC originals (pixels then linear sRGB, like JxlDecoder without a CMS),
  * grey images, up to four full-resolution integer extra channels (alpha into a 4-channel output, all of them as host
  * planes) incl. the squeeze `cjxl -p` puts on them and palettes without deltas, progressive passes, orientation,
- * photon noise and splines (drawn on the device, jxlhip_set_noise / jxlhip_set_splines).
+ * photon noise and splines (drawn on the device, jxlhip_set_noise / jxlhip_set_splines), frames upsampled 2x / 4x / 8x
+ * (what cjxl writes from distance 10 on and with --resampling; upsampled on the device, jxlhip_set_upsampling, with the
+ * image header's custom weights or the format's defaults) of images without extra channels.
  * Everything this front-end does not decode is refused with JXLHIP_ERR_UNSUPPORTED so that the caller can hand the
  * file to libjxl's CPU decoder: Modular-mode frames, animation / multiple frames, previews, patches,
- * chroma subsampling and YCbCr (JPEG recompression), upsampling, cropped frames, DC frames, RAW dequant tables, RCT /
- * delta palettes in the extra channels' Modular streams.
+ * chroma subsampling and YCbCr (JPEG recompression), upsampled frames of images with extra channels (alpha included:
+ * cjxl downsamples them along with the colour, ec_upsampling != 1, and no stream the test oracle writes has one to
+ * check against), extra channels upsampled on their own, cropped frames, DC frames, RAW dequant tables, RCT / delta
+ * palettes in the extra channels' Modular streams.
  */
 #ifndef JXL_HIP_CODESTREAM_H_
 #define JXL_HIP_CODESTREAM_H_
@@ -38,7 +42,7 @@ extern "C" {
 #endif
 
 typedef struct jxlhip_codestream_info {
-  uint32_t xsize, ysize;       /* image = frame size */
+  uint32_t xsize, ysize;       /* image size (= the frame's, after its upsampling) */
   uint32_t container;          /* the bytes were an ISOBMFF container (jxlc / jxlp boxes) */
   uint32_t orientation;        /* 1..8 (ImageMetadata::orientation); see JXLHIP_OUT_UNDO_ORIENTATION */
   float intensity_target;      /* ImageMetadata::tone_mapping.intensity_target */
@@ -65,6 +69,10 @@ typedef struct jxlhip_codestream_info {
      white_point 1), grey for a grey profile -- JxlDecoder's output when no CMS is set (dec_xyb.cc:160-164).
      grey: the original is a grey image (R = G = B in every output) */
   uint32_t icc_size, grey;
+  /* headers: FrameHeader::upsampling of the frame (1, 2, 4, 8): it is coded at ceil(xsize / upsampling) x
+     ceil(ysize / upsampling) and upsampled on the device (jxlhip_set_upsampling); xsize / ysize above and every
+     output are the IMAGE size */
+  uint32_t upsampling;
 } jxlhip_codestream_info;
 
 /* Headers only (no device needed): size and colour metadata of the first frame's image.  JXLHIP_ERR_BAD_STREAM /

@@ -102,8 +102,8 @@ typedef struct jxlhip_image_header {
   float opsin_biases[3];
   float quant_biases[4];
   uint32_t custom_weights_mask;                  /* bit 0/1/2: the 2x/4x/8x upsampling weights below are coded */
-  float upsampling2_weights[15], upsampling4_weights[55], upsampling8_weights[210]; /* zero when not coded
-                                                    (upsampling is outside the back-end; defaults not carried) */
+  float upsampling2_weights[15], upsampling4_weights[55], upsampling8_weights[210]; /* zero when not coded:
+                                                    jxlhip_set_upsampling then takes NULL = the format's defaults */
 } jxlhip_image_header;
 
 /* Reads the image header of a bare codestream starting at byte 0 of data (0xFF 0x0A).  extra[] receives

@@ -8,7 +8,7 @@ _SO = os.environ.get("JXLHIP_SO") or os.path.join(_HERE, "csrc", "libjxl_hip.so"
 _RUNNER_SO = os.path.join(_HERE, "csrc", "libjxl_threads_hip.so")
 
 KERNEL_COUNT = 8
-KERNEL_NAMES = ["prepare", "blocks", "filters", "fused", "epf0", "noise", "splines", "k7"]
+KERNEL_NAMES = ["prepare", "blocks", "filters", "fused", "epf0", "noise", "splines", "upsample"]
 
 
 class JxlHipError(RuntimeError):
@@ -151,7 +151,8 @@ class CodestreamInfo(C.Structure):
                 ("num_groups", C.c_uint32), ("num_dc_groups", C.c_uint32), ("epf_iters", C.c_uint32),
                 ("gab", C.c_uint32), ("used_acs", C.c_uint32), ("coeff_type", C.c_uint32), ("fused", C.c_uint32),
                 ("num_extra_channels", C.c_uint32), ("alpha_bits", C.c_uint32), ("alpha_premultiplied", C.c_uint32),
-                ("luminances", C.c_float * 3), ("gamma", C.c_float), ("icc_size", C.c_uint32), ("grey", C.c_uint32)]
+                ("luminances", C.c_float * 3), ("gamma", C.c_float), ("icc_size", C.c_uint32), ("grey", C.c_uint32),
+                ("upsampling", C.c_uint32)]
 
 
 class FrameParams(C.Structure):
@@ -231,7 +232,7 @@ EXPORTS = [
     "jxlhip_dequant_table_offset", "jxlhip_status_string", "jxlhip_create", "jxlhip_create_ex", "jxlhip_create_multi",
     "jxlhip_destroy", "jxlhip_last_error", "jxlhip_debug_reload_env", "jxlhip_set_stream",
     "jxlhip_frame_begin", "jxlhip_frame_set_inputs", "jxlhip_upload_side_info",
-    "jxlhip_submit_group", "jxlhip_set_alpha", "jxlhip_set_noise", "jxlhip_noise_rng_state", "jxlhip_set_splines", "jxlhip_alpha_staging", "jxlhip_decode_blocks", "jxlhip_halo_rows",
+    "jxlhip_submit_group", "jxlhip_set_alpha", "jxlhip_set_noise", "jxlhip_noise_rng_state", "jxlhip_set_splines", "jxlhip_set_upsampling", "jxlhip_alpha_staging", "jxlhip_decode_blocks", "jxlhip_halo_rows",
     "jxlhip_halo_export", "jxlhip_halo_import", "jxlhip_decode_filters", "jxlhip_decode_filters_rows", "jxlhip_stripe_begin",
     "jxlhip_stripe_finish", "jxlhip_decode_frame",
     "jxlhip_decode_frame_host", "jxlhip_decode_frame_pinned",
@@ -311,6 +312,7 @@ def load_library():
     L.jxlhip_splines_destroy.restype = None
     L.jxlhip_splines_segments.argtypes = [vp, u32, u32, C.c_float, C.c_float, vp, sz, C.POINTER(sz)]
     L.jxlhip_set_splines.argtypes = [vp, vp]
+    L.jxlhip_set_upsampling.argtypes = [vp, u32, C.POINTER(C.c_float), u32, u32]
     L.jxlhip_splines_quantized.argtypes = [vp, C.POINTER(u32), C.POINTER(sz), C.POINTER(i32), vp, vp, vp, vp]
     L.jxlhip_modular_global_decode.argtypes = [vp, sz, C.POINTER(sz), C.POINTER(FrameHeader), C.POINTER(vp)]
     L.jxlhip_modular_tree_destroy.argtypes = [vp]

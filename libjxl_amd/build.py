@@ -20,7 +20,7 @@ LIB_SOURCES = ["kernels_fused.hip", "kernels_filters_fast_general.hip", "kernels
                "kernels_blocks.hip", "kernels_filters_fast.hip", "kernels_fused_epf0.hip", "entropy.cc", "context.hip",
                "handover.hip", "codestream.hip", "multi.hip",
                "kernels_filters.hip", "kernels_mfma.hip", "kernels_epf0.hip", "kernels_tables.hip", "kernels_noise.hip",
-               "kernels_splines.hip"]
+               "kernels_splines.hip", "kernels_upsample.hip"]
 RUNNER_SOURCES = ["runner.cc"]
 # Per-file flags.  kernels_blocks.hip: the SLP vectoriser pairs the butterflies of the in-register IDCTs into packed
 # fp32 operations (v_pk_fma / v_pk_add / v_pk_mul on aligned register PAIRS, stitched together with v_mov): the pairs
@@ -163,9 +163,10 @@ def check_no_scratch(so, pattern="k_fused_pc"):
     bad = {k: v for k, v in res.items() if pattern in k and (v["scratch"] or v["spills"])}
     if bad:
         os.remove(so)
-        raise RuntimeError("refusing to ship %s: %d %s kernels use scratch (inline-asm prefetch registers may be "
-                           "spilled before their loads land): %s" % (os.path.basename(so), len(bad), pattern,
-                                                                      sorted(bad.items())[:2]))
+        why = "inline-asm prefetch registers may be spilled before their loads land" if pattern == "k_fused_pc" else \
+            "its per-thread arrays must stay in registers"
+        raise RuntimeError("refusing to ship %s: %d %s kernels use scratch (%s): %s" % (
+            os.path.basename(so), len(bad), pattern, why, sorted(bad.items())[:2]))
 
 
 def build(verbose=False):
@@ -178,6 +179,7 @@ def build(verbose=False):
         objs = dict(zip(srcs, ex.map(_compile, srcs)))
     lib = _link(os.path.join(CSRC, "libjxl_hip.so"), [objs[s] for s in LIB_SOURCES])
     check_no_scratch(lib)
+    check_no_scratch(lib, "k_upsample")  # (3 x 25 samples per thread live in registers: indexed by constants only)
     out = [lib]
     if have_runner:
         out.append(_link(os.path.join(CSRC, "libjxl_threads_hip.so"),

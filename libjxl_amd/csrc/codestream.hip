@@ -135,8 +135,14 @@ int ParseHeaders(const uint8_t* cs, size_t n, ParsedHeaders* h) {
   const jxlhip_frame_header& fh = h->fh;
   if (fh.is_modular || fh.color_transform != JXLHIP_CT_XYB || fh.frame_type != JXLHIP_FRAME_REGULAR ||
       (fh.flags & (JXLHIP_FLAG_PATCHES | JXLHIP_FLAG_USE_DC_FRAME)) ||
-      fh.chroma_mode[0] || fh.chroma_mode[1] || fh.chroma_mode[2] || fh.upsampling != 1 || fh.dc_level != 0 ||
-      fh.custom_size_or_origin || !fh.is_last || fh.xsize != ih.xsize || fh.ysize != ih.ysize)
+      fh.chroma_mode[0] || fh.chroma_mode[1] || fh.chroma_mode[2] || fh.dc_level != 0 || fh.custom_size_or_origin ||
+      !fh.is_last)
+    return JXLHIP_ERR_UNSUPPORTED;
+  // upsampling 2 / 4 / 8 (jxlhip_set_upsampling): the colour channels only -- an image with extra channels has them
+  // downsampled along with the colour, and the back-end upsamples none
+  const uint32_t ups = fh.upsampling;
+  if ((ups != 1 && ups != 2 && ups != 4 && ups != 8) || (ups != 1 && ih.num_extra_channels != 0) ||
+      fh.xsize != (ih.xsize + ups - 1) / ups || fh.ysize != (ih.ysize + ups - 1) / ups)
     return JXLHIP_ERR_UNSUPPORTED;
   for (uint32_t i = 0; i < ih.num_extra_channels; i++)
     if (fh.ec_upsampling[i] != 1) return JXLHIP_ERR_UNSUPPORTED;
@@ -165,6 +171,7 @@ void FillInfo(const ParsedHeaders& h, bool container, jxlhip_codestream_info* in
     info->alpha_bits = h.extra[h.alpha_index].bit_depth.bits_per_sample;
     info->alpha_premultiplied = h.extra[h.alpha_index].alpha_associated;
   }
+  info->upsampling = h.fh.upsampling;
 }
 
 // The Modular parts of the AC-group sections on the runner (extra channels; FrameDecoder::ProcessACGroup's second
@@ -930,6 +937,13 @@ static int DecodeCodestreamImpl(jxlhip_ctx* c, jxlhip_parallel_runner runner, vo
     }
   }
   clock.Mark(JXLHIP_PHASE_EXTRA_CHANNELS);
+  // an upsampled frame: the image header's weights for the factor, or the format's defaults (in front of the splines:
+  // their draw list is made for the upsampled size)
+  if (fh.upsampling != 1) {
+    const uint32_t bit = fh.upsampling == 2 ? 1u : fh.upsampling == 4 ? 2u : 4u;
+    const float* coded = fh.upsampling == 2 ? ih.upsampling2_weights : fh.upsampling == 4 ? ih.upsampling4_weights : ih.upsampling8_weights;
+    if ((rc = jxlhip_set_upsampling(c, fh.upsampling, (ih.custom_weights_mask & bit) ? coded : nullptr, ih.xsize, ih.ysize))) return rc;
+  }
   // photon noise: the stream's only frame is visible frame 1 (FrameDecoder::InitFrame counts it before decoding,
   // dec_frame.cc:160-168)
   if ((fh.flags & JXLHIP_FLAG_NOISE) && (rc = jxlhip_set_noise(c, noise_lut, 1, 0))) return rc;

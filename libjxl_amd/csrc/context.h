@@ -264,6 +264,14 @@ struct jxlhip_ctx {
   std::vector<uint32_t> spl_host_tiles;
   Event spl_ev;
   bool spl_ev_pending = false;
+  // jxlhip_set_upsampling: the current frame is upsampled by ups_factor (1 = not; frame_begin resets) to ups_xsize x
+  // ups_ysize; ups_planes = the filtered frame as planar XYB at CODED size (kernels_upsample.hip; noise_buf then holds
+  // the upsampled planes + the random planes at output size), ups_weights = the factor's kernels (UpsampleKernels),
+  // ups_weights_host the copy their upload reads
+  uint32_t ups_factor = 1, ups_xsize = 0, ups_ysize = 0;
+  DevBuf<float> ups_planes;
+  DevBuf<float> ups_weights;
+  float ups_weights_host[64 * 25] = {0};
   bool generic_filters = false;  // JXLHIP_FILTERS=generic: LDS kernel for every stage list
   int mfma = -1;                 // DCT32X32 / DCT16X16 on the matrix cores (kernels_mfma.hip; the 16x16 rule is in
                                  // LaunchPhase1).  -1 (default): when the caller's
@@ -298,6 +306,11 @@ inline size_t OutPixelBytes(const jxlhip_ctx* c) {
   if (c->p.output_kind != JXLHIP_OUT_PACKED) return 0;
   return (size_t)c->p.out_format.num_channels * OutSampleBytes(c->p.out_format);
 }
+
+// columns / rows of what jxlhip_decode_frame writes in coded orientation: the context's stripe of the frame, or the
+// size an upsampled frame (jxlhip_set_upsampling: whole frames only) comes out at
+inline size_t OutCols(const jxlhip_ctx* c) { return c->ups_factor > 1 ? c->ups_xsize : c->f.xsize; }
+inline size_t OutRows(const jxlhip_ctx* c) { return c->ups_factor > 1 ? c->ups_ysize : c->f.y1 - c->f.y0; }
 
 // context.hip
 jxlhip_ctx* NewCtx(const JxlMemoryManagerHip* mm);

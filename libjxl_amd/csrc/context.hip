@@ -10,6 +10,7 @@
 
 #include "context.h"
 #include "dither_pattern.inc"
+#include "upsampling_constants.inc"
 
 extern "C" __attribute__((visibility("default"))) void jxlhip_debug_reload_env(void) {
   std::lock_guard<std::mutex> lock(jxlhip_env::g.mu);
@@ -343,6 +344,7 @@ int jxlhip_frame_begin(jxlhip_ctx* c, const jxlhip_frame_params* p) {
   c->blocks_done = false;
   c->noise_on = false;
   c->splines_on = false;
+  c->ups_factor = 1;
   return JXLHIP_OK;
 }
 
@@ -400,6 +402,7 @@ int jxlhip_alpha_staging(jxlhip_ctx* c, float** plane, size_t* stride_floats) {
 int jxlhip_set_alpha(jxlhip_ctx* c, const float* host_plane, size_t stride_floats) {
   if (!c || !host_plane) return JXLHIP_ERR_INVALID_ARGUMENT;
   if (!c->have_frame) return Fail(c, JXLHIP_ERR_STATE, "set_alpha before frame_begin");
+  if (c->ups_factor > 1) return Fail(c, JXLHIP_ERR_UNSUPPORTED, "alpha on an upsampled frame");
   if (c->multi) {  // every stripe takes its own rows of the plane
     for (MultiChild& k : c->multi->kids) {
       const int rc = jxlhip_set_alpha(k.ctx, host_plane, stride_floats);
@@ -466,16 +469,19 @@ int jxlhip_set_splines(jxlhip_ctx* c, const jxlhip_splines* s) {
   c->splines_on = false;
   if (!s) return JXLHIP_OK;
   const uint32_t W = c->f.xsize, H = c->f.ysize;
+  // an upsampled frame: the draw cache is made for the upsampled size (dec_frame.cc:304-308), the stage draws the
+  // rows and columns of the coded frame
+  const uint32_t DW = (uint32_t)OutCols(c), DH = c->ups_factor > 1 ? c->ups_ysize : H;
   HIPCHK(c, hipSetDevice(c->device));
   if (c->spl_ev_pending) {  // the previous frame's upload still reads the host copies
     HIPCHK(c, hipEventSynchronize(c->spl_ev));
     c->spl_ev_pending = false;
   }
   size_t n = 0;
-  int rc = jxlhip_splines_segments(s, W, H, c->p.cfl_base_x, c->p.cfl_base_b, nullptr, 0, &n);
+  int rc = jxlhip_splines_segments(s, DW, DH, c->p.cfl_base_x, c->p.cfl_base_b, nullptr, 0, &n);
   if (rc) return Fail(c, rc, "invalid splines");
   std::vector<jxlhip_spline_segment> segs(n);
-  if (n && (rc = jxlhip_splines_segments(s, W, H, c->p.cfl_base_x, c->p.cfl_base_b, segs.data(), n, &n)))
+  if (n && (rc = jxlhip_splines_segments(s, DW, DH, c->p.cfl_base_x, c->p.cfl_base_b, segs.data(), n, &n)))
     return Fail(c, rc, "invalid splines");
   // bin by tile: the column span of DrawSegment (splines.cc:116-125) clipped to the frame, the row span as computed
   const uint32_t tx = (W + 63) / 64, ty = (H + 15) / 16, tiles = tx * ty;
@@ -485,7 +491,7 @@ int jxlhip_set_splines(jxlhip_ctx* c, const jxlhip_splines* s) {
   for (const jxlhip_spline_segment& g : segs) {
     const int64_t start = SplineRound(g.center_x - g.maximum_distance);
     const int64_t end = SplineRound(g.center_x + g.maximum_distance);
-    if (end < 0 || start >= (int64_t)W || g.y1 <= g.y0) continue;
+    if (end < 0 || start >= (int64_t)W || g.y1 <= g.y0 || g.y0 >= (int64_t)H) continue;
     SplineSeg d;
     d.cx = g.center_x;
     d.cy = g.center_y;
@@ -493,7 +499,7 @@ int jxlhip_set_splines(jxlhip_ctx* c, const jxlhip_splines* s) {
     d.s4i = g.sigma_over_4_times_intensity;
     for (int k = 0; k < 3; k++) d.color[k] = g.color[k];
     d.y0 = g.y0;
-    d.y1 = g.y1;
+    d.y1 = (int32_t)std::min<int64_t>(g.y1, (int64_t)H);
     d.x0 = (int32_t)std::max<int64_t>(start, 0);
     d.x1 = (int32_t)std::min<int64_t>(end, (int64_t)W - 1);
     d.pad = 0.0f;
@@ -533,6 +539,44 @@ int jxlhip_set_splines(jxlhip_ctx* c, const jxlhip_splines* s) {
   c->spl_num_active = active;
   c->spl_entries = entries;
   c->splines_on = true;
+  return JXLHIP_OK;
+}
+
+// Upsampling of the current frame (FrameHeader::upsampling): the factor, its kernels (UpsamplingStage's constructor on
+// the coded or the default weights) and the size the frame comes out at; frame_begin resets to "not upsampled".
+int jxlhip_set_upsampling(jxlhip_ctx* c, uint32_t factor, const float* weights, uint32_t out_xsize, uint32_t out_ysize) {
+  if (!c) return JXLHIP_ERR_INVALID_ARGUMENT;
+  if (c->multi) return Fail(c, JXLHIP_ERR_UNSUPPORTED, "upsampling on a multi-device context");
+  if (!c->have_frame) return Fail(c, JXLHIP_ERR_STATE, "set_upsampling before frame_begin");
+  if (factor != 1 && factor != 2 && factor != 4 && factor != 8)
+    return Fail(c, JXLHIP_ERR_INVALID_ARGUMENT, "upsampling factor %u", factor);
+  if (factor == 1) {
+    // (a draw list made for the upsampled size must not outlive it)
+    if (c->ups_factor > 1 && c->splines_on)
+      return Fail(c, JXLHIP_ERR_STATE, "set_upsampling after set_splines (the draw list depends on it)");
+    c->ups_factor = 1;
+    return JXLHIP_OK;
+  }
+  if (c->f.group_y0 != 0 || c->f.group_rows != c->f.ysg) return Fail(c, JXLHIP_ERR_UNSUPPORTED, "upsampling with stripes");
+  if (c->p.undo_orientation > 1)
+    return Fail(c, JXLHIP_ERR_UNSUPPORTED, "upsampling with undo_orientation %u", c->p.undo_orientation);
+  if (c->fp.alpha) return Fail(c, JXLHIP_ERR_UNSUPPORTED, "alpha on an upsampled frame");
+  if (c->splines_on) return Fail(c, JXLHIP_ERR_STATE, "set_upsampling after set_splines (the draw list depends on it)");
+  if (out_xsize == 0 || out_ysize == 0 || (out_xsize + factor - 1) / factor != c->f.xsize ||
+      (out_ysize + factor - 1) / factor != c->f.ysize)
+    return Fail(c, JXLHIP_ERR_INVALID_ARGUMENT, "a %ux%u frame upsampled %ux does not give %ux%u", c->f.xsize, c->f.ysize,
+                factor, out_xsize, out_ysize);
+  HIPCHK(c, hipSetDevice(c->device));
+  const float* coded = weights ? weights : factor == 2 ? kUpsampling2Weights : factor == 4 ? kUpsampling4Weights : kUpsampling8Weights;
+  UpsampleKernels(factor, coded, c->ups_weights_host);
+  const int rc = c->ups_weights.Reserve(c, 64 * 25);
+  if (rc) return rc;
+  // (a pageable source: staged by the runtime when hipMemcpyAsync returns, the next frame may overwrite it)
+  HIPCHK(c, hipMemcpyAsync(c->ups_weights, c->ups_weights_host, sizeof(float) * factor * factor * 25, hipMemcpyHostToDevice,
+                           c->stream));
+  c->ups_factor = factor;
+  c->ups_xsize = out_xsize;
+  c->ups_ysize = out_ysize;
   return JXLHIP_OK;
 }
 
@@ -730,19 +774,18 @@ int BeginDecode(jxlhip_ctx* c) {
   return JXLHIP_OK;
 }
 
-int CheckOutArgs(jxlhip_ctx* c, void* out, size_t out_stride, size_t out_plane_stride) {
-  const DevFrame& f = c->f;
+// cols x rows: what the call writes -- the stripe at coded size, or an upsampled frame (OutCols / OutRows)
+int CheckOutArgs(jxlhip_ctx* c, void* out, size_t out_stride, size_t out_plane_stride, size_t cols, size_t rows) {
   if (!out) return Fail(c, JXLHIP_ERR_INVALID_ARGUMENT, "null output");
   if (c->p.output_kind == JXLHIP_OUT_LINEAR_RGB_F32) {
-    if (out_stride < (size_t)f.xsize * 12 || (out_stride & 3))
+    if (out_stride < cols * 12 || (out_stride & 3))
       return Fail(c, JXLHIP_ERR_INVALID_ARGUMENT, "RGB row stride %zu too small", out_stride);
   } else if (c->p.output_kind == JXLHIP_OUT_PACKED) {
     const size_t ssz = OutSampleBytes(c->p.out_format);
-    if (out_stride < (size_t)f.xsize * OutPixelBytes(c) || (out_stride % ssz) ||
+    if (out_stride < cols * OutPixelBytes(c) || (out_stride % ssz) ||
         ((uintptr_t)out % ssz))
       return Fail(c, JXLHIP_ERR_INVALID_ARGUMENT, "packed row stride %zu / alignment invalid", out_stride);
-  } else if (out_stride < f.xsize ||
-             out_plane_stride < out_stride * (size_t)(f.y1 - f.y0 - 1) + f.xsize) {
+  } else if (out_stride < cols || out_plane_stride < out_stride * (rows - 1) + cols) {
     return Fail(c, JXLHIP_ERR_INVALID_ARGUMENT, "XYB strides too small");
   }
   return JXLHIP_OK;
@@ -818,7 +861,9 @@ int jxlhip_decode_filters_rows(jxlhip_ctx* c, void* out, size_t out_stride, size
   if (c->noise_on) return Fail(c, JXLHIP_ERR_UNSUPPORTED, "noise with the split calls (jxlhip_decode_frame takes it)");
   if (c->splines_on)
     return Fail(c, JXLHIP_ERR_UNSUPPORTED, "splines with the split calls (jxlhip_decode_frame takes them)");
-  int rc = CheckOutArgs(c, out, out_stride, out_plane_stride);
+  if (c->ups_factor > 1)
+    return Fail(c, JXLHIP_ERR_UNSUPPORTED, "upsampling with the split calls (jxlhip_decode_frame takes it)");
+  int rc = CheckOutArgs(c, out, out_stride, out_plane_stride, c->f.xsize, c->f.y1 - c->f.y0);
   if (rc) return rc;
   HIPCHK(c, hipSetDevice(c->device));
   FilterParams fp = c->fp;
@@ -873,7 +918,7 @@ int jxlhip_decode_frame(jxlhip_ctx* c, void* out, size_t out_stride, size_t out_
   if (!c) return JXLHIP_ERR_INVALID_ARGUMENT;
   if (c->multi) return out ? MultiDecodeFrame(c, out, nullptr, out_stride, out_plane_stride) : JXLHIP_ERR_INVALID_ARGUMENT;
   if (!c->have_frame) return Fail(c, JXLHIP_ERR_STATE, "decode needs frame_begin + inputs");
-  if (c->noise_on || c->splines_on) return DecodeFrameFeatures(c, out, out_stride, out_plane_stride);
+  if (c->noise_on || c->splines_on || c->ups_factor > 1) return DecodeFrameFeatures(c, out, out_stride, out_plane_stride);
   if (c->p.undo_orientation <= 1) return DecodeFrameCoded(c, out, out_stride, out_plane_stride);
   // undo_orientation: coded orientation into a staging frame, k_orient into the caller's buffer
   const DevFrame& f = c->f;
@@ -899,7 +944,7 @@ static int DecodeFrameCoded(jxlhip_ctx* c, void* out, size_t out_stride, size_t 
   c->blocks_fused = false;
   int rc = BeginDecode(c);
   if (rc) return rc;
-  rc = CheckOutArgs(c, out, out_stride, out_plane_stride);
+  rc = CheckOutArgs(c, out, out_stride, out_plane_stride, f.xsize, f.y1 - f.y0);  // (always at coded size here)
   if (rc) return rc;
   FilterParams fp = c->fp;
   fp.out = out;
@@ -931,26 +976,37 @@ static int DecodeFrameCoded(jxlhip_ctx* c, void* out, size_t out_stride, size_t 
   return LaunchFiltersRows(c, fp, f.y0, f.y1);
 }
 
-// A frame with splines and / or photon noise (jxlhip_set_splines, jxlhip_set_noise; whole frames, coded orientation):
-// the frame's own path -- fused or two-phase, whatever DecodeFrameCoded picks for it -- writes the filtered frame as
-// planar XYB into context memory; the render stages the reference's pipeline has between the loop filters and the
-// XYB stage follow (dec_cache.cc:194-210), splines first, then noise, and the last launch writes the caller's output:
+// A frame with splines, upsampling and / or photon noise (jxlhip_set_splines, jxlhip_set_upsampling, jxlhip_set_noise;
+// whole frames, coded orientation): the frame's own path -- fused or two-phase, whatever DecodeFrameCoded picks for it --
+// writes the filtered frame as planar XYB into context memory; the render stages the reference's pipeline has between
+// the loop filters and the XYB stage follow in its order (dec_cache.cc:194-218): splines at coded size, upsampling,
+// noise at output size, and the last launch writes the caller's output:
 //   splines only  k_splines draws every tile and emits;
 //   noise only    k_noise_rng + k_noise_emit (kernels_noise.hip);
-//   both          k_splines draws the tiles with segments back into the planes, then the noise launches.
+//   upsampling    k_upsample emits; with noise it writes planar XYB at output size and the noise launches emit;
+//   splines in front of either: k_splines draws the tiles with segments back into the planes.
+// Noise behind upsampling is the noise of a frame of the output size: PrepareNoiseInput seeds one generator per
+// group_dim tile in OUTPUT coordinates and fills it clipped to the image (dec_noise.cc:120-151).
 static int DecodeFrameFeatures(jxlhip_ctx* c, void* out, size_t out_stride, size_t out_plane_stride) {
-  int rc = CheckOutArgs(c, out, out_stride, out_plane_stride);
+  const bool ups = c->ups_factor > 1;
+  int rc = CheckOutArgs(c, out, out_stride, out_plane_stride, OutCols(c), OutRows(c));
   if (rc) return rc;
   const DevFrame& f = c->f;
   if (f.group_y0 != 0 || f.group_rows != f.ysg || c->p.undo_orientation > 1)
-    return Fail(c, JXLHIP_ERR_UNSUPPORTED, "noise / splines need a whole frame in coded orientation");
+    return Fail(c, JXLHIP_ERR_UNSUPPORTED, "noise / splines / upsampling need a whole frame in coded orientation");
   HIPCHK(c, hipSetDevice(c->device));
-  const uint32_t ns = (f.xsize + 63u) & ~63u;
-  const size_t nplane = (size_t)ns * f.ysize;
-  if ((rc = c->noise_buf.Reserve(c, (c->noise_on ? 6 : 3) * nplane))) return rc;
+  // the filtered frame at coded size (cns x f.ysize per plane), and the frame the noise launches work on (W x H)
+  const uint32_t cns = (f.xsize + 63u) & ~63u;
+  const size_t cplane = (size_t)cns * f.ysize;
+  const uint32_t W = (uint32_t)OutCols(c), H = (uint32_t)OutRows(c);
+  const uint32_t ns = (W + 63u) & ~63u;
+  const size_t nplane = (size_t)ns * H;
+  if (ups && (rc = c->ups_planes.Reserve(c, 3 * cplane))) return rc;
+  if ((!ups || c->noise_on) && (rc = c->noise_buf.Reserve(c, (c->noise_on ? 6 : 3) * nplane))) return rc;
+  float* coded = ups ? c->ups_planes : c->noise_buf;
   const uint32_t kind = c->p.output_kind;
   c->p.output_kind = JXLHIP_OUT_XYB_PLANAR;
-  rc = DecodeFrameCoded(c, c->noise_buf, ns, nplane);
+  rc = DecodeFrameCoded(c, coded, cns, cplane);
   c->p.output_kind = kind;
   if (rc) return rc;
   FilterParams fp = c->fp;
@@ -964,24 +1020,39 @@ static int DecodeFrameFeatures(jxlhip_ctx* c, void* out, size_t out_stride, size
     S.ysize = f.ysize;
     S.tiles_x = c->spl_tiles_x;
     S.num_active = c->spl_num_active;
-    S.xyb = c->noise_buf;
-    S.xyb_out = c->noise_buf;
-    S.ns = ns;
-    S.nplane = nplane;
+    S.xyb = coded;
+    S.xyb_out = coded;
+    S.ns = cns;
+    S.nplane = cplane;
     S.segs = c->spl_segs;
     S.tile_start = c->spl_tiles;
     S.tile_idx = c->spl_tiles + c->spl_num_tiles + 1;
     S.active = c->spl_tiles + c->spl_num_tiles + 1 + c->spl_entries;
-    if (!LaunchSplines(S, fp, (int)kind, /*in_place=*/c->noise_on, c->stream))
+    if (!LaunchSplines(S, fp, (int)kind, /*in_place=*/c->noise_on || ups, c->stream))
       return Fail(c, JXLHIP_ERR_INVALID_ARGUMENT, "splines output kind %u", kind);
     ProfMark(c, JXLHIP_KERNEL_SPLINES);
   }
+  if (ups) {
+    UpsampleArgs U{};
+    U.cw = f.xsize;
+    U.ch = f.ysize;
+    U.xsize = W;
+    U.ysize = H;
+    U.n = c->ups_factor;
+    U.xyb = coded;
+    U.ns = cns;
+    U.nplane = cplane;
+    U.weights = c->ups_weights;
+    if (!LaunchUpsample(U, fp, (int)kind, c->noise_on ? (float*)c->noise_buf : nullptr, ns, nplane, c->stream))
+      return Fail(c, JXLHIP_ERR_INVALID_ARGUMENT, "upsampling output kind %u", kind);
+    ProfMark(c, JXLHIP_KERNEL_UPSAMPLE);
+  }
   if (c->noise_on) {
     NoiseArgs N{};
-    N.xsize = f.xsize;
-    N.ysize = f.ysize;
-    N.xsg = f.xsg;
-    N.ysg = f.ysg;
+    N.xsize = W;
+    N.ysize = H;
+    N.xsg = (W + 255u) / 256u;
+    N.ysg = (H + 255u) / 256u;
     N.visible = c->noise_visible;
     N.nonvisible = c->noise_nonvisible;
     memcpy(N.lut, c->noise_lut, sizeof(N.lut));
@@ -1010,8 +1081,8 @@ int jxlhip_decode_frame_host(jxlhip_ctx* c, void* host_out, size_t out_stride, s
   if (!c->have_frame) return Fail(c, JXLHIP_ERR_STATE, "decode needs frame_begin + inputs");
   const DevFrame& f = c->f;
   const bool transposed = c->p.undo_orientation >= 5;  // the oriented frame is ysize wide, xsize high
-  const size_t rows = transposed ? f.xsize : f.y1 - f.y0;
-  const size_t cols = transposed ? f.ysize : f.xsize;
+  const size_t rows = transposed ? f.xsize : OutRows(c);  // (an upsampled frame is never transposed)
+  const size_t cols = transposed ? f.ysize : OutCols(c);
   const bool planar = c->p.output_kind == JXLHIP_OUT_XYB_PLANAR;
   const size_t row_bytes = cols * (planar ? 4 : OutPixelBytes(c));
   const size_t host_row = planar ? out_stride * 4 : out_stride;
@@ -1035,8 +1106,8 @@ int jxlhip_decode_frame_pinned(jxlhip_ctx* c, const void** host_frame, size_t* s
   const jxlhip_frame_params& p = c->p;
   if (p.output_kind == JXLHIP_OUT_XYB_PLANAR) return Fail(c, JXLHIP_ERR_UNSUPPORTED, "pinned frames are interleaved outputs");
   const bool transposed = p.undo_orientation >= 5;
-  const size_t rows = transposed ? p.xsize : p.ysize;
-  const size_t cols = transposed ? p.ysize : p.xsize;
+  const size_t rows = transposed ? p.xsize : (c->ups_factor > 1 ? c->ups_ysize : p.ysize);
+  const size_t cols = transposed ? p.ysize : (c->ups_factor > 1 ? c->ups_xsize : p.xsize);
   const size_t row_bytes = cols * OutPixelBytes(c);
   const size_t pitch = (row_bytes + 63) & ~(size_t)63;
   if (rows * pitch > c->pinned_frame.bytes) {

@@ -168,6 +168,25 @@ struct SplineArgs {
 // active tiles back into S.xyb_out (planar XYB, for the noise launches).  False for a bad output kind.
 bool LaunchSplines(const SplineArgs& S, const FilterParams& p, int output_kind, bool in_place, hipStream_t st);
 
+// Upsampling (kernels_upsample.hip).  The coded frame is cut into 64 x 16 tiles; every coded pixel gives n x n output
+// pixels, each a 25-tap sum over its 5 x 5 neighbourhood clamped to the neighbourhood's range.
+struct UpsampleArgs {
+  uint32_t cw, ch;         // the coded frame: ceil(xsize / n) x ceil(ysize / n)
+  uint32_t xsize, ysize;   // the output (= image) size
+  uint32_t n;              // 2, 4, 8
+  const float* xyb;        // the filtered coded frame: 3 planes, ns floats per row, nplane floats apart
+  uint32_t ns;
+  size_t nplane;
+  const float* weights;    // device: n * n kernels of 25 taps (UpsampleKernels)
+};
+// host: the 15 / 55 / 210 coded weights of factor n expanded to its n * n kernels of 25 taps
+void UpsampleKernels(uint32_t n, const float* coded, float* kernels /* n * n * 25 */);
+// k_upsample: planes_out == nullptr: upsample and write the output tail of `output_kind` into p.out; else upsample
+// into planar XYB at output resolution (planes_ns floats per row, planes_nplane apart, for the noise launches).  False
+// for a bad output kind, factor or size pair.
+bool LaunchUpsample(const UpsampleArgs& U, const FilterParams& p, int output_kind, float* planes_out, uint32_t planes_ns,
+                    size_t planes_nplane, hipStream_t st);
+
 // block-major plane rows <-> dense row-major staging
 void LaunchZeroU32(uint32_t* p, uint32_t n, hipStream_t st);  // (kernels_tables.hip: a kernel, for captured graphs)
 void LaunchRowsCopy(const DevFrame& f, float* dense, int y_first, int nrows, int ncols,

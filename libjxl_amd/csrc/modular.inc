@@ -1224,7 +1224,9 @@ static int ModularGlobalDecodeImpl(const uint8_t* data, size_t size, size_t* bit
                                    jxlhip_modular_tree** out) {
   if (!data || !bit_pos || !fh || !out) return JXLHIP_ERR_INVALID_ARGUMENT;
   *out = nullptr;
-  if (fh->is_modular || fh->num_extra_channels > 4 || fh->upsampling != 1) return JXLHIP_ERR_UNSUPPORTED;
+  // (an upsampled frame without extra channels has an empty global image like any other)
+  if (fh->is_modular || fh->num_extra_channels > 4 || (fh->upsampling != 1 && fh->num_extra_channels != 0))
+    return JXLHIP_ERR_UNSUPPORTED;
   for (uint32_t i = 0; i < fh->num_extra_channels; i++)
     if (fh->ec_upsampling[i] != 1) return JXLHIP_ERR_UNSUPPORTED;
   BitReader br(data, size, *bit_pos);

@@ -35,6 +35,7 @@ class VarDctDecoder:
         self.params = None
         self._keep = None
         self.out = None
+        self.out_size = None
 
     def close(self):
         if self.ctx:
@@ -53,6 +54,7 @@ class VarDctDecoder:
         if isinstance(params, dict):
             params = abi.make_params(params)
         self.params = params
+        self.out_size = None  # (xsize, ysize) of an upsampled frame's output: set_upsampling
         _check(self.L, self.ctx, self.L.jxlhip_frame_begin(self.ctx, C.byref(params)), "frame_begin")
 
     def default_dequant_tables(self):
@@ -102,11 +104,15 @@ class VarDctDecoder:
         dev = f"cuda:{self.device}"
         # undo_orientation 5..8: the display frame is ysize pixels wide and xsize rows high
         oh, ow = (p.xsize, p.ysize) if p.undo_orientation >= 5 else (y1 - y0, p.xsize)
+        if self.out_size is not None:  # an upsampled frame (whole frames, coded orientation)
+            ow, oh = self.out_size
         if p.output_kind == 1:
             return torch.empty((oh, ow, 3), dtype=torch.float32, device=dev)
         if p.output_kind == 2:  # packed RGB(A): dtype of the sample type (F16 as raw uint16 bits)
             dt = {0: torch.float32, 1: torch.uint8, 2: torch.int16, 3: torch.int16}[p.out_format.sample_type]
             return torch.empty((oh, ow, p.out_format.num_channels), dtype=dt, device=dev)
+        if self.out_size is not None:
+            return torch.empty((3, oh, ow), dtype=torch.float32, device=dev)
         return torch.empty((3, y1 - y0, p.xsize), dtype=torch.float32, device=dev)
 
     def _out_args(self, out):
@@ -147,6 +153,20 @@ class VarDctDecoder:
             _check(self.L, self.ctx, self.L.jxlhip_set_splines(self.ctx, h), "set_splines")
         finally:
             abi.splines_destroy(h, self.L)
+
+    def set_upsampling(self, factor, out_size, weights=None):
+        """Upsampling of the current frame (FrameHeader::upsampling: 2, 4 or 8), jxlhip_set_upsampling: begin_frame's
+        size is the coded size, out_size = (xsize, ysize) the image the frame is upsampled and cropped to; weights =
+        the factor's 15 / 55 / 210 coded weights, None = the format's defaults.  Call it before set_splines.
+        decode_frame() then allocates the output-sized tensor.  factor 1 or begin_frame resets."""
+        w = None
+        if weights is not None:
+            vals = [float(v) for v in weights]
+            assert len(vals) == {2: 15, 4: 55, 8: 210}[int(factor)], len(vals)
+            w = (C.c_float * len(vals))(*vals)
+        ox, oy = (int(out_size[0]), int(out_size[1])) if out_size is not None else (0, 0)
+        _check(self.L, self.ctx, self.L.jxlhip_set_upsampling(self.ctx, int(factor), w, ox, oy), "set_upsampling")
+        self.out_size = (ox, oy) if int(factor) > 1 else None
 
     # -- decode ----------------------------------------------------------------
     def decode_blocks(self):
