@@ -233,7 +233,8 @@ JXLHIP_EXPORT const char* jxlhip_last_error(const jxlhip_ctx* ctx);
 /* The library samples its debug / test switches (JXLHIP_WP_GENERAL, JXLHIP_CODESTREAM_VERBOSE, JXLHIP_NO_PIPELINE,
  * JXLHIP_TEST_RANGE_GROUP, JXLHIP_MULTI_INTERIOR_FIRST, JXLHIP_MULTI_FORCE_GATHER, JXLHIP_MAX_PIXELS, the kernels'
  * launch-geometry knobs JXLHIP_FUSED_PC_RH, JXLHIP_FILTER_RH, JXLHIP_BIG_WGS, JXLHIP_R_WGS, and the path switches
- * JXLHIP_FILTERS, JXLHIP_SPARSE_UPLOAD, JXLHIP_FUSE, JXLHIP_MFMA, JXLHIP_STAGE_SLOTS) from the environment when a context is created
+ * JXLHIP_FILTERS, JXLHIP_SPARSE_UPLOAD, JXLHIP_FUSE, JXLHIP_MFMA, JXLHIP_STAGE_SLOTS, JXLHIP_PREPARE_ONCE) from the environment when a
+ * context is created
  * (jxlhip_create / _ex / _multi) and at their first use before that; a test that changes one of them under a live
  * context calls this to have them read again (the path switches stay as a context was created with them).  Decoding
  * and kernel launches never call getenv (no reference counterpart: libjxl has no run-time switches on this path). */
@@ -251,14 +252,21 @@ JXLHIP_EXPORT int jxlhip_set_stream(jxlhip_ctx* ctx, void* hip_stream,
 JXLHIP_EXPORT int jxlhip_frame_begin(jxlhip_ctx* ctx,
                                      const jxlhip_frame_params* params);
 
-/* Zero-copy path: the caller already has the inputs in device memory. */
+/* Zero-copy path: the caller already has the inputs in device memory.
+ * One hand-over, any number of decodes: the side-info arrays (ac_strategy, raw_quant, epf_sharpness, ytox_map,
+ * ytob_map) are read by the FIRST decode call after this one, which derives the work lists, the sigma image and the
+ * strategy-map check from them once (k_prepare); later decode calls of the same hand-over reuse that.  They must not
+ * change between decodes unless jxlhip_frame_set_inputs is called again (the same pointers will do).  Coefficients,
+ * DC and the dequant table may change from decode to decode: every decode reads them afresh. */
 JXLHIP_EXPORT int jxlhip_frame_set_inputs(jxlhip_ctx* ctx,
                                           const jxlhip_frame_inputs* dev);
 
 /* Host-upload path (what a libjxl FrameDecoder would call).
  * Replaces the reads of shared->ac_strategy/raw_quant_field/epf_sharpness/
  * cmap/dc in DecodeGroupImpl (dec_group.cc:275-316).  Host pointers, dense
- * frame-sized planes; copied asynchronously into context-owned HBM. */
+ * frame-sized planes; copied asynchronously into context-owned HBM.  The work lists, the sigma image and the
+ * strategy-map check (k_prepare; ComputeSigma runs per DC group in the reference too, dec_modular.cc:559) are
+ * enqueued right behind the copies, once per call: every decode until the next hand-over reuses them. */
 JXLHIP_EXPORT int jxlhip_upload_side_info(
     jxlhip_ctx* ctx, const uint8_t* ac_strategy, const int32_t* raw_quant,
     const uint8_t* epf_sharpness, const int8_t* ytox_map,
@@ -425,7 +433,8 @@ JXLHIP_EXPORT int jxlhip_get_sigma(jxlhip_ctx* ctx, float** inv_sigma,
  * jxlhip_profile_read syncs and returns accumulated milliseconds and launch
  * counts per kernel slot (see JXLHIP_KERNEL_*), then resets. */
 enum {
-  JXLHIP_KERNEL_PREPARE = 0,  /* block-offset scan, work lists, sigma */
+  JXLHIP_KERNEL_PREPARE = 0,  /* block-offset scan, work lists, sigma: once per hand-over of side info; the span of a
+                                 decode that reuses them is marked all the same and reads about 0 */
   JXLHIP_KERNEL_BLOCKS = 1,   /* dequant+CfL+LLF+inverse transforms: one launch
                                  per strategy class, overlapped on several
                                  streams; the span covers all of them */
@@ -447,6 +456,12 @@ enum {
  * stays two-phase: 77 vs 67).  The pixels do not depend on it beyond the rounding difference between the two paths
  * (both within the parity bar).  Nothing like it in libjxl. */
 JXLHIP_EXPORT int jxlhip_set_concurrency_hint(jxlhip_ctx* ctx, int frames_in_flight);
+/* Debug / test: k_prepare launches this context has enqueued (`launched`) and decode calls that saved one by reusing
+ * the lists an earlier decode had used (`reused`) since it was created -- the first decode behind
+ * jxlhip_upload_side_info / inside jxlhip_decode_codestream takes up the launch its hand-over enqueued and counts in
+ * neither; direct calls only, launches recorded into a hipGraph count in neither.  JXLHIP_PREPARE_ONCE=0 (sampled when the context is created) turns the reuse off: every phase 1 then
+ * runs its own k_prepare.  A multi-device context reports the sums over its devices. */
+JXLHIP_EXPORT int jxlhip_debug_prepare_launches(const jxlhip_ctx* ctx, uint64_t* launched, uint64_t* reused);
 JXLHIP_EXPORT int jxlhip_profile_enable(jxlhip_ctx* ctx, int enable);
 JXLHIP_EXPORT int jxlhip_profile_read(jxlhip_ctx* ctx,
                                       float ms[JXLHIP_KERNEL_COUNT],

@@ -844,6 +844,8 @@ static int DecodeCodestreamImpl(jxlhip_ctx* c, jxlhip_parallel_runner runner, vo
     ApplyInputs(c, &in);
     c->have_inputs = true;
     c->blocks_done = false;
+    DropPrepared(c);  // (new maps, and used_acs above)
+    if ((rc = PrepareAhead(c, (fh.flags & JXLHIP_FLAG_NOISE) || splines || fh.upsampling > 1))) return rc;  // under the AC groups' entropy decode instead of in front of the frame's kernels
     clock.Mark(JXLHIP_PHASE_SIDE_INFO);
     // AC groups on the runner: entropy decode into pinned staging slots + uploads
     if (ac_in_pipeline) {

@@ -178,6 +178,22 @@ struct jxlhip_ctx {
   // will use (DevFrame::zero_counts) -- no memset launch per frame.  clean[b]: block b is all zero.
   int counts_slot = 0;
   bool counts_clean[2] = {false, false};
+  // The prepared state (LaunchPhase1): k_prepare's outputs -- work lists, counters, cell_info, inv_sigma, the error
+  // flag -- are a function of the side info and the frame constants only, so one prepare serves every direct phase 1 of
+  // the same hand-over.  prepared: a prepare has been enqueued on `stream` with this key (the `fused` mode 0 / 1 / 2 and
+  // the hand-over generation) on counter block prepared_block.  DropPrepared says who ends it.
+  bool prepare_once = true;  // JXLHIP_PREPARE_ONCE=0: every phase 1 prepares
+  bool prepared = false;
+  bool prepared_ahead = false;  // ... by PrepareAhead, and no decode has used it yet (the first one is no "reuse")
+  int prepared_fused = 0;
+  int prepared_block = 0;
+  uint64_t prepared_gen = 0;
+  uint64_t handover_gen = 0;  // advances with every hand-over of side info and whatever else k_prepare reads
+  bool capture_seen = false;  // a phase 1 of this frame was recorded into a graph: its replays rewrite the shared lists
+                              // behind the host's back, direct calls prepare every time until the next frame_begin
+  // direct calls only (jxlhip_debug_prepare_launches): k_prepare launches, and phase 1s that saved one -- a decode that
+  // takes up the prepare its hand-over enqueued ahead is neither
+  uint64_t prepares_launched = 0, prepares_reused = 0;
   double cs_phase_ms[8] = {};  // jxlhip_codestream_phase_ms
   int concurrency = 1;  // jxlhip_set_concurrency_hint: contexts the caller keeps busy on this device at a time
   bool handover_fresh = false;  // frame_begin started the hand-over and upload_side_info has not been called since
@@ -316,6 +332,16 @@ inline size_t OutRows(const jxlhip_ctx* c) { return c->ups_factor > 1 ? c->ups_y
 jxlhip_ctx* NewCtx(const JxlMemoryManagerHip* mm);
 void DeleteCtx(jxlhip_ctx* c);
 void ApplyInputs(jxlhip_ctx* c, const jxlhip_frame_inputs* in);
+// Ends the prepared state and starts a new hand-over generation: whatever k_prepare reads may have changed (every
+// caller is listed at LaunchPhase1).
+inline void DropPrepared(jxlhip_ctx* c) {
+  c->prepared = false;
+  c->handover_gen++;
+}
+// The side info of the current hand-over is queued on c->stream: enqueues its prepare right behind it, in the mode the
+// context would decode it with now (jxlhip_upload_side_info, jxlhip_decode_codestream).  render_stages: the caller
+// knows that splines, upsampling or noise will be set for this frame (its own path then writes planar XYB).
+int PrepareAhead(jxlhip_ctx* c, bool render_stages = false);
 
 // multi.hip
 void MultiDestroy(jxlhip_ctx* c);

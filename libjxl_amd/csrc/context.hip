@@ -129,6 +129,7 @@ int jxlhip_create_ex(int device, const JxlMemoryManagerHip* memory_manager, jxlh
     c->sparse_upload = s.sparse_upload.load();
     c->fuse = s.fuse.load();
     c->mfma = s.mfma.load();
+    c->prepare_once = s.prepare_once.load();
     const int ss = s.stage_slots.load();
     if (ss != jxlhip_env::Switches::kUnset) {  // whole chunks, at least the first allocation
       const int v = (ss + kStageChunk - 1) / kStageChunk * kStageChunk;
@@ -187,7 +188,11 @@ int jxlhip_set_stream(jxlhip_ctx* c, void* hip_stream, int external) {
   if (c->multi) return jxlhip_set_stream(c->multi->kids[0].ctx, hip_stream, external);  // the frame's consumer is on devices[0]
   const hipStream_t st = external ? (hipStream_t)hip_stream : c->own_stream;
   // the zeroing of the next frame's counter block is ordered on the OLD stream only: a new stream starts with a memset
-  if (st != c->stream) c->counts_clean[0] = c->counts_clean[1] = false;
+  // -- and with a prepare of its own: the lists the old stream's k_prepare writes are ordered on that stream only
+  if (st != c->stream) {
+    c->counts_clean[0] = c->counts_clean[1] = false;
+    DropPrepared(c);
+  }
   c->stream = st;
   return JXLHIP_OK;
 }
@@ -218,6 +223,9 @@ int jxlhip_frame_begin(jxlhip_ctx* c, const jxlhip_frame_params* p) {
   if (p->lf.gab > 1 || p->lf.epf_iters > 3)
     return Fail(c, JXLHIP_ERR_INVALID_ARGUMENT, "bad loop filter parameters");
   HIPCHK(c, hipSetDevice(c->device));
+  // a new frame: the geometry, the constants and the buffers k_prepare reads and writes may all change below
+  DropPrepared(c);
+  c->capture_seen = false;
   DevFrame f{};
   f.xsize = p->xsize;
   f.ysize = p->ysize;
@@ -378,6 +386,7 @@ int jxlhip_frame_set_inputs(jxlhip_ctx* c, const jxlhip_frame_inputs* in) {
   ApplyInputs(c, in);
   c->have_inputs = true;
   c->blocks_done = false;
+  DropPrepared(c);  // (lazily prepared: the caller's arrays are first read by the first decode)
   return JXLHIP_OK;
 }
 
@@ -590,21 +599,77 @@ int jxlhip_noise_rng_state(uint32_t visible_frame_index, uint32_t nonvisible_fra
 // ---- decode -------------------------------------------------------------------
 namespace {
 
-// Phase 1 over the context's whole stripe (DevFrame::band_g0 / band_g1 = its group rows, set by jxlhip_frame_begin):
-// k_prepare + the transform kernels.  Every phase 1 takes its work-list counter block here.  Direct calls alternate
-// between blocks 0 and 1: a block gets a memset only when it is not marked clean, and the k_prepare of one call zeroes
-// the block the next call will use (DevFrame::zero_counts) -- no memset launch per frame.  Under stream capture -- the
-// caller records the frame's launches into a hipGraph and replays it (bench.py's `graph_replay`: the command
-// processor's ~5-8 us per dependent launch are paid once per graph instead) -- every replay must find the SAME block
-// zeroed by a node of the graph itself, and must not touch a block the direct calls keep a "clean" flag for:
-// kCaptureBlock, zeroed by a kernel (see LaunchZeroU32: no memset node at the root of a frame graph).
+// Phase 1 over the context's whole stripe (DevFrame::band_g0 / band_g1 = its group rows, set by jxlhip_frame_begin), in
+// two steps: "prepare" (EnqueuePrepare: the counter-block zeroing, the cell_info fill of a fused stripe, k_prepare) and
+// "blocks" (the transform kernels, which only READ the list lengths).
+//
+// Prepare once per hand-over.  k_prepare reads side info and frame constants only -- ac_strategy, raw_quant,
+// epf_sharpness, ytox_map, ytob_map, the geometry, the stripe, used_acs, coef_stride64, `fused`, the quantizer scale and
+// the sharpness LUT -- never a coefficient, and its outputs (work lists and their lengths, cell_info, inv_sigma, the
+// error flag) are a function of those, up to the order inside a list.  So a DIRECT phase 1 whose key -- `fused` and the
+// hand-over generation -- matches the prepare the context remembers launches the blocks on the remembered counter block
+// and no k_prepare: a progressive pass, a second output format, a loop that refreshes coefficients only.  The reference
+// has this work in the same place: ComputeSigma runs when a DC group's AC metadata is decoded (dec_modular.cc:559), not
+// per AC pass.  jxlhip_upload_side_info and jxlhip_decode_codestream enqueue the prepare right behind their side-info
+// copies (PrepareAhead), under the host's entropy decode; the zero-copy jxlhip_frame_set_inputs stays lazy.
+// Who writes what a prepare leaves behind, and so who ends the prepared state (DropPrepared / EnqueuePrepare):
+//   work lists   k_prepare only; the buffer is (re)allocated by jxlhip_frame_begin
+//   counters     the memset / LaunchZeroU32 below, k_prepare (its atomics on its own block, zero_counts on the other);
+//                allocated once by jxlhip_create_ex
+//   cell_info    k_prepare and the 0xFF fill below; reserved by EnqueuePrepare itself
+//   inv_sigma    k_prepare only; reserved by jxlhip_frame_begin
+//   error flag   k_prepare raises [0] (k_dequant_tables [1]); jxlhip_sync clears it when it reports it
+//   the inputs   jxlhip_frame_set_inputs, jxlhip_upload_side_info, jxlhip_decode_codestream (with its used_acs update)
+// -> jxlhip_frame_begin, those three hand-overs, jxlhip_set_stream to another stream (the prepare is ordered on the old
+// one), a jxlhip_sync that reports JXLHIP_ERR_BAD_STREAM (the next decode must raise the flag again) and any HIP error
+// inside a phase 1 drop the state; jxlhip_set_concurrency_hint and whatever else moves WantFused change the key.
+// JXLHIP_PREPARE_ONCE=0: every phase 1 prepares.
+//
+// Every prepare takes its work-list counter block here.  Direct calls alternate between blocks 0 and 1: a block gets a
+// memset only when it is not marked clean, and the k_prepare of one call zeroes the block the next PREPARE will use
+// (DevFrame::zero_counts) -- no memset launch per frame.  Under stream capture -- the caller records the frame's
+// launches into a hipGraph and replays it (bench.py's `graph_replay`: the command processor's ~5-8 us per dependent
+// launch are paid once per graph instead) -- nothing is reused: the captured frame carries its own k_prepare, every
+// replay must find the SAME block zeroed by a node of the graph itself, and must not touch a block the direct calls
+// keep a "clean" flag for: kCaptureBlock, zeroed by a kernel (see LaunchZeroU32: no memset node at the root of a frame
+// graph).  A replay rewrites the shared lists behind the host's back: once a context has seen a capture, its direct
+// calls prepare every time until the next jxlhip_frame_begin.
 // fused: 0 = two-phase, 1 = the whole frame through the fused kernel, 2 = a STRIPE through it (the DCT8 cells of
 // the stripe's first / last block row are decoded into the planes as well: they are the halo rows its neighbours pull)
-int LaunchPhase1(jxlhip_ctx* c, int fused = 0, const FilterParams* emit = nullptr) {
-  hipStream_t st = c->stream;
+bool Capturing(hipStream_t st) {
   hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
   (void)hipStreamIsCapturing(st, &cap);
-  const bool capturing = cap == hipStreamCaptureStatusActive;
+  return cap == hipStreamCaptureStatusActive;
+}
+
+// the frame as both steps of phase 1 see it
+DevFrame Phase1Frame(const jxlhip_ctx* c, int fused) {
+  DevFrame f = c->f;
+  f.fused = (uint32_t)fused;
+  f.cell_info = c->cell_info;
+  constexpr uint32_t kOthers32 = (1u << 8) | (1u << 9) | (1u << 10) | (1u << 11);  // 32x8 .. 16x32
+  const bool lone32 = (f.used_acs & (1u << 5)) && !(f.used_acs & kOthers32);
+  f.mfma32 = (c->mfma > 0 || (c->mfma < 0 && lone32)) ? c->tables + kTabMfma32 : nullptr;
+  // DCT16X16: the same rule against the 16-point row-per-lane family (16x8, 8x16), only when no 32-point class
+  // pulls the merged launch in anyway, and on frames of 16 Mpx and more (measured, all-DCT16X16 frames: 8K blocks
+  // 132 -> 118 us, 16x16 + 32x32 176 -> 161 us; 4K 33.6 -> 37.6 us: the butterflies stay; on the mixed c3 frame a
+  // launch of its own costs 97 -> 117 us, like DCT32X32)
+  constexpr uint32_t kOthers16 = (1u << 6) | (1u << 7);
+  const bool lone16 = (f.used_acs & (1u << 4)) && !(f.used_acs & (kOthers16 | kOthers32)) &&
+                      (!(f.used_acs & (1u << 5)) || f.mfma32) && (uint64_t)f.xsize * f.ysize >= (16u << 20);
+  f.mfma16 = (c->mfma > 0 || (c->mfma < 0 && lone16)) ? c->tables + kTabMfma16 : nullptr;
+  return f;
+}
+
+// The prepare step on c->stream; *block = the counter block it counted into.  A direct one becomes the context's
+// prepared state when everything was enqueued without an error.
+int EnqueuePrepare(jxlhip_ctx* c, int fused, bool capturing, int* block_out) {
+  hipStream_t st = c->stream;
+  c->prepared = false;  // (what the last prepare left is overwritten from here on; a replay will overwrite this one's)
+  c->prepared_ahead = false;
+  if (capturing) c->capture_seen = true;
+  int rc;
+  if (fused && (rc = c->cell_info.Reserve(c, (size_t)c->f.xsb * c->f.ysb))) return rc;
   const int block = capturing ? kCaptureBlock : c->counts_slot;
   uint32_t* counts = c->counts + (size_t)block * kCountStride;
   if (capturing) {
@@ -613,40 +678,57 @@ int LaunchPhase1(jxlhip_ctx* c, int fused = 0, const FilterParams* emit = nullpt
   } else {
     if (!c->counts_clean[block]) HIPCHK(c, hipMemsetAsync(counts, 0, sizeof(uint32_t) * kCountStride, st));
     // From here on the block is in use: whatever happens below (a failed launch after k_prepare ran), it must not be
-    // taken for clean by the next frame.  Block ^ 1 becomes clean only when the launches that zero it succeeded.
+    // taken for clean by the next prepare.  Block ^ 1 becomes clean only when the launch that zeroes it succeeded.
     c->counts_clean[block] = false;
   }
-  DevFrame f = c->f;
-  f.fused = (uint32_t)fused;
-  f.cell_info = c->cell_info;
-  {
-    constexpr uint32_t kOthers32 = (1u << 8) | (1u << 9) | (1u << 10) | (1u << 11);  // 32x8 .. 16x32
-    const bool lone32 = (f.used_acs & (1u << 5)) && !(f.used_acs & kOthers32);
-    f.mfma32 = (c->mfma > 0 || (c->mfma < 0 && lone32)) ? c->tables + kTabMfma32 : nullptr;
-    // DCT16X16: the same rule against the 16-point row-per-lane family (16x8, 8x16), only when no 32-point class
-    // pulls the merged launch in anyway, and on frames of 16 Mpx and more (measured, all-DCT16X16 frames: 8K blocks
-    // 132 -> 118 us, 16x16 + 32x32 176 -> 161 us; 4K 33.6 -> 37.6 us: the butterflies stay; on the mixed c3 frame a
-    // launch of its own costs 97 -> 117 us, like DCT32X32)
-    constexpr uint32_t kOthers16 = (1u << 6) | (1u << 7);
-    const bool lone16 = (f.used_acs & (1u << 4)) && !(f.used_acs & (kOthers16 | kOthers32)) &&
-                        (!(f.used_acs & (1u << 5)) || f.mfma32) && (uint64_t)f.xsize * f.ysize >= (16u << 20);
-    f.mfma16 = (c->mfma > 0 || (c->mfma < 0 && lone16)) ? c->tables + kTabMfma16 : nullptr;
-  }
+  DevFrame f = Phase1Frame(c, fused);
   f.zero_counts = capturing ? nullptr : c->counts + (size_t)(block ^ 1) * kCountStride;
   if (fused == 2)  // a stripe: every cell "from the planes" until k_prepare says otherwise (whole frames: k_prepare writes every cell)
     HIPCHK(c, hipMemsetAsync(c->cell_info, 0xFF, sizeof(uint2) * (size_t)f.xsb * f.ysb, st));
   WorkLists wl = c->wl;
   wl.count = counts;
-  const uint32_t cells = f.xsg * f.group_rows * 1024u;
   ProfBegin(c);
   LaunchPrepare(f, wl, c->p.lf.epf_iters > 0, c->p.lf.epf_quant_mul, c->lut, st);
   ProfMark(c, JXLHIP_KERNEL_PREPARE);
+  HIPCHK(c, hipGetLastError());
+  *block_out = block;
+  if (capturing) return JXLHIP_OK;
+  c->counts_clean[block ^ 1] = true;
+  c->counts_slot = block ^ 1;
+  c->prepares_launched++;
+  if (c->prepare_once && !c->capture_seen) {
+    c->prepared = true;
+    c->prepared_fused = fused;
+    c->prepared_block = block;
+    c->prepared_gen = c->handover_gen;
+  }
+  return JXLHIP_OK;
+}
+
+int LaunchPhase1(jxlhip_ctx* c, int fused = 0, const FilterParams* emit = nullptr) {
+  hipStream_t st = c->stream;
+  const bool capturing = Capturing(st);
+  int block;
+  if (!capturing && c->prepared && c->prepared_fused == fused && c->prepared_gen == c->handover_gen) {
+    block = c->prepared_block;
+    if (!c->prepared_ahead) c->prepares_reused++;
+    c->prepared_ahead = false;
+    ProfBegin(c);
+    ProfMark(c, JXLHIP_KERNEL_PREPARE);  // (the span is still there: about 0, nothing was launched)
+  } else {
+    const int rc = EnqueuePrepare(c, fused, capturing, &block);
+    if (rc) return rc;
+  }
+  const DevFrame f = Phase1Frame(c, fused);
+  WorkLists wl = c->wl;
+  wl.count = c->counts + (size_t)block * kCountStride;
+  const uint32_t cells = f.xsg * f.group_rows * 1024u;
   LaunchBlocks(f, wl, cells, c->tables + kTabWc, c->tables + kTabResample, st, emit);
   ProfMark(c, JXLHIP_KERNEL_BLOCKS);
-  HIPCHK(c, hipGetLastError());
-  if (!capturing) {
-    c->counts_clean[block ^ 1] = true;
-    c->counts_slot = block ^ 1;
+  const hipError_t e = hipGetLastError();
+  if (e != hipSuccess) {
+    c->prepared = false;
+    return Fail(c, e == hipErrorOutOfMemory ? JXLHIP_ERR_OUT_OF_MEMORY : JXLHIP_ERR_HIP, "phase 1: %s", hipGetErrorString(e));
   }
   return JXLHIP_OK;
 }
@@ -793,6 +875,37 @@ int CheckOutArgs(jxlhip_ctx* c, void* out, size_t out_stride, size_t out_plane_s
 
 }  // namespace
 
+int jxlhip::PrepareAhead(jxlhip_ctx* c, bool render_stages) {
+  if (!c->prepare_once || c->capture_seen || !c->have_frame || !c->have_inputs || Capturing(c->stream)) return JXLHIP_OK;
+  // the mode the context would pick now: a whole frame goes through jxlhip_decode_frame (1 or 0), a stripe through the
+  // split calls (2 or 0).  A decode that wants another one -- the split calls on a whole frame, a render stage that
+  // changes the output kind -- prepares again: correct, and one launch.
+  const bool stripe = c->f.group_y0 != 0 || c->f.group_rows != c->f.ysg;
+  const uint32_t kind = c->p.output_kind;
+  if (render_stages || c->noise_on || c->splines_on || c->ups_factor > 1) c->p.output_kind = JXLHIP_OUT_XYB_PLANAR;  // as DecodeFrameFeatures
+  const int fused = WantFused(c) ? (stripe ? 2 : 1) : 0;
+  c->p.output_kind = kind;
+  int block;
+  const int rc = EnqueuePrepare(c, fused, false, &block);
+  c->prepared_ahead = rc == JXLHIP_OK && c->prepared;
+  return rc;
+}
+
+int jxlhip_debug_prepare_launches(const jxlhip_ctx* c, uint64_t* launched, uint64_t* reused) {
+  if (!c || !launched || !reused) return JXLHIP_ERR_INVALID_ARGUMENT;
+  *launched = *reused = 0;
+  if (c->multi) {
+    for (const MultiChild& k : c->multi->kids) {
+      *launched += k.ctx->prepares_launched;
+      *reused += k.ctx->prepares_reused;
+    }
+    return JXLHIP_OK;
+  }
+  *launched = c->prepares_launched;
+  *reused = c->prepares_reused;
+  return JXLHIP_OK;
+}
+
 int jxlhip_decode_blocks(jxlhip_ctx* c) {
   if (!c) return JXLHIP_ERR_INVALID_ARGUMENT;
   JXLHIP_NO_MULTI(c);
@@ -804,7 +917,6 @@ int jxlhip_decode_blocks(jxlhip_ctx* c) {
   // A whole frame through the split calls stays two-phase (the taps read the planes).
   const bool stripe = c->f.group_y0 != 0 || c->f.group_rows != c->f.ysg;
   c->blocks_fused = stripe && WantFused(c);
-  if (c->blocks_fused && (rc = c->cell_info.Reserve(c, (size_t)c->f.xsb * c->f.ysb))) return rc;
   rc = LaunchPhase1(c, c->blocks_fused ? 2 : 0);
   if (rc) return rc;
   c->blocks_done = true;
@@ -966,7 +1078,6 @@ static int DecodeFrameCoded(jxlhip_ctx* c, void* out, size_t out_stride, size_t 
   // halo rows to pay for and wins at 4K as well (95.8 vs 83.4 Gpx/s); never when the caller's used_acs says the
   // frame has no DCT8 block -- then the slab is only a detour (configs[4]: 76.1 vs 79.6 Gpx/s)
   if (WantFused(c) && f.group_y0 == 0 && f.group_rows == f.ysg) {
-    if ((rc = c->cell_info.Reserve(c, (size_t)f.xsb * f.ysb))) return rc;
     if ((rc = LaunchPhase1(c, 1))) return rc;
     c->blocks_done = false;  // the planes do not hold the whole frame
     return LaunchFiltersRows(c, fp, f.y0, f.y1, true);
@@ -1132,6 +1243,8 @@ int jxlhip_sync(jxlhip_ctx* c) {
   HIPCHK(c, hipMemcpyAsync(flag, c->error_flag, sizeof(flag), hipMemcpyDeviceToHost, c->stream));
   HIPCHK(c, hipStreamSynchronize(c->stream));
   if (flag[0] || flag[1]) {
+    // the flag is k_prepare's to raise: the next decode of the same inputs prepares again and reports the map again
+    DropPrepared(c);
     HIPCHK(c, hipMemsetAsync(c->error_flag, 0, sizeof(flag), c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     return Fail(c, JXLHIP_ERR_BAD_STREAM,

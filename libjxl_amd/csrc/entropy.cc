@@ -34,6 +34,7 @@ void LoadLocked() {
   g.fuse.store(force(getenv("JXLHIP_FUSE")));
   g.mfma.store(force(getenv("JXLHIP_MFMA")));
   g.stage_slots.store(num(getenv("JXLHIP_STAGE_SLOTS"), Switches::kUnset));
+  g.prepare_once.store(num(getenv("JXLHIP_PREPARE_ONCE"), 1) != 0);
   {
     // unparsable / empty / 0: the default (2^30 pixels = four 16K frames' worth), not "refuse every frame"
     const char* mp = getenv("JXLHIP_MAX_PIXELS");

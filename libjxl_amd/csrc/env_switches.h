@@ -31,6 +31,7 @@ struct Switches {
   std::atomic<int> fuse{-1};                 // JXLHIP_FUSE=0 / 1 forces (-1: auto)
   std::atomic<int> mfma{-1};                 // JXLHIP_MFMA=0 / 1 forces (-1: auto)
   std::atomic<int> stage_slots{kUnset};      // JXLHIP_STAGE_SLOTS: pinned staging slots per context
+  std::atomic<bool> prepare_once{true};      // JXLHIP_PREPARE_ONCE=0: k_prepare in front of every phase 1
   std::mutex mu;
 };
 extern Switches g;  // defined in entropy.cc

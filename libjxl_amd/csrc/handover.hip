@@ -144,7 +144,8 @@ int jxlhip_upload_side_info(jxlhip_ctx* c, const uint8_t* ac_strategy, const int
   ApplyInputs(c, &in);
   c->have_inputs = true;
   c->blocks_done = false;
-  return JXLHIP_OK;
+  DropPrepared(c);
+  return PrepareAhead(c);  // behind the copies, under whatever the caller does until it decodes
 }
 
 // JXLHIP_CODESTREAM_VERBOSE: the longest single wait of the upload path during one AC phase, microseconds

@@ -256,6 +256,13 @@ class VarDctDecoder:
         from which decode_frame takes the fused kernel (12 Mpx alone, 6 Mpx with several frames in flight)."""
         _check(self.L, self.ctx, self.L.jxlhip_set_concurrency_hint(self.ctx, int(frames_in_flight)), "set_concurrency_hint")
 
+    def prepare_launches(self):
+        """(launched, reused): k_prepare launches this context has enqueued and decode calls that saved one by reusing
+        an earlier decode's work lists (jxlhip_debug_prepare_launches; direct calls only)."""
+        a, b = C.c_uint64(), C.c_uint64()
+        _check(self.L, self.ctx, self.L.jxlhip_debug_prepare_launches(self.ctx, C.byref(a), C.byref(b)), "prepare_launches")
+        return a.value, b.value
+
     def profile(self, enable=True):
         _check(self.L, self.ctx, self.L.jxlhip_profile_enable(self.ctx, int(enable)), "profile_enable")
 
