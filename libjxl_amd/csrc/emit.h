@@ -2,8 +2,11 @@
 // XYB -> linear RGB (lib/jxl/dec_xyb-inl.h:38-86, stage_xyb.cc:42-98),
 // FromLinearStage (stage_from_linear.cc:34-155) and WriteToOutputStage's sample
 // conversion + interleaving (stage_write.cc:254-330,524-640).  Operation order
-// follows the reference's scalar (single-lane) evaluation so that results are
-// bit-identical to it: explicit fmaf, IEEE sqrt and division.
+// follows the reference's scalar (single-lane) evaluation: explicit fmaf, IEEE
+// sqrt and division.  Given the same linear pixels the linear, 709, gamma and HLG
+// encodings are bit-identical to it in every sample type; sRGB and PQ use the
+// hardware square root and reciprocal and are not (see SrgbFromLinear,
+// PqFromLinear).  tests/test_gpu_output_encoding.py holds each to that.
 #ifndef JXLHIP_EMIT_H_
 #define JXLHIP_EMIT_H_
 
@@ -33,8 +36,13 @@ __device__ __forceinline__ void XybToRgb(float x, float y, float b, const Filter
 // (base/rational_polynomial-inl.h:59-97) and one division.  The square root and
 // the division are the hardware's 1-ulp v_sqrt_f32 / v_rcp_f32 (the correctly
 // rounded sequences cost ~25 VALU operations per sample and doubled the filter
-// kernel's time); the result differs from the reference's by <= 2 ulp, far
-// inside what the float pipeline in front of it already differs by.
+// kernel's time).  Against the reference's result on the same linear sample:
+// bit-equal on the 12.92 x branch; above it up to 6 float32 ulps seen over the
+// encoder's whole domain (-7e4 .. 7e4; the test's bar is 8: sqrt 1 ulp instead
+// of 1/2 times the curve's elasticity in sqrt(x) of up to ~2, the reciprocal
+// and its extra multiply ~2 more); an integer sample at most one code apart,
+// none of 8 bits in a 520x264 frame and 5e-4 of the 16-bit ones; a half-float
+// sample at most one step, 2e-5 of them.
 __device__ __forceinline__ float SrgbFromLinear(float v) {
   const float x = __builtin_fabsf(v);
   const float s = __builtin_amdgcn_sqrtf(x);
@@ -66,7 +74,12 @@ __device__ __forceinline__ float Rational44(float x, const float* p, const float
 
 // TF_PQ::EncodedFromDisplay (transfer_functions-inl.h:172-208): rational
 // polynomials in x^(1/4), one below and one above 1e-4; `to_10000` =
-// intensity_target / 10000
+// intensity_target / 10000.  x^(1/4) is two chained v_sqrt_f32 (within ~2.25 ulp
+// of the reference's) and the division a v_rcp_f32: up to 8 float32 ulps from
+// the reference's result on the same linear sample seen over the encoder's whole
+// domain (the test's bar is 12: the elasticity in x^(1/4) is up to ~2.4); an
+// integer sample at most one code apart (6e-4 of the 16-bit ones, 2e-6 of the
+// 8-bit ones), a half-float sample at most one step (3e-4 of them).
 __device__ __forceinline__ float PqFromLinear(float v, float to_10000) {
   const float kP[5] = {1.351392e-02f, -1.095778e+00f, 5.522776e+01f, 1.492516e+02f, 4.838434e+01f};
   const float kQ[5] = {1.012416e+00f, 2.016708e+01f, 9.263710e+01f, 1.120607e+02f, 2.590418e+01f};

@@ -243,6 +243,39 @@ class Frame:
         return out
 
 
+def pack_output(out_format, rgb):
+    """jxo_pack_output alone (oracle/output.c): the restatement of FromLinearStage + WriteToOutputStage applied to
+    LINEAR RGB `rgb`, an (H, W, 3) float32 array, under `out_format` (an OutputFormat, libjxl_amd.abi's included, or
+    the dict synth.synth_frame takes).  Returns the packed (H, W, channels) array: uint8, uint16 (16-bit integers and
+    raw half-float bits) or float32, bytes as they go to memory (swapped when the format says so).  The call reads
+    xsize, ysize and out_format of the frame and nothing else."""
+    rgb = np.ascontiguousarray(rgb, np.float32)
+    assert rgb.ndim == 3 and rgb.shape[2] == 3, rgb.shape
+    of = OutputFormat()
+    if isinstance(out_format, dict):
+        of.transfer = out_format.get("transfer", 0)
+        of.sample_type = out_format.get("sample_type", 0)
+        of.num_channels = out_format.get("num_channels", 3)
+        of.bits_per_sample = out_format.get("bits_per_sample", 0)
+        of.swap_endianness = out_format.get("swap_endianness", 0)
+        of.tf_param = out_format.get("tf_param", 0.0)
+        of.luminances[:] = out_format.get("luminances", (0.2126, 0.7152, 0.0722))
+    else:
+        assert C.sizeof(out_format) == C.sizeof(of)
+        C.memmove(C.byref(of), C.byref(out_format), C.sizeof(of))
+    f = OracleFrame()
+    f.p.ysize, f.p.xsize = rgb.shape[:2]
+    f.p.out_format = of
+    dt = {0: np.float32, 1: np.uint8, 2: np.uint16, 3: np.uint16}[of.sample_type]
+    out = np.zeros((rgb.shape[0], rgb.shape[1], of.num_channels), dt)
+    L = lib()
+    L.jxo_pack_output.restype = None
+    L.jxo_pack_output.argtypes = [C.POINTER(OracleFrame), C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_uint32,
+                                  C.c_uint32]
+    L.jxo_pack_output(C.byref(f), _p(rgb), rgb.shape[1] * 3, _p(out), out.strides[0], 0, rgb.shape[0])
+    return out
+
+
 # ---- oracle/_ref: the libjxl reference itself (compiled in place) ----------
 _REF_SO = os.path.join(_HERE, "_ref", "libjxl_ref.so")
 _ref = None

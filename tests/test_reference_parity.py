@@ -249,3 +249,51 @@ def test_eight_lane_build_of_the_reference_hot_path_matches_the_checker(ref):
         a, b = fr.decode_ref(threads=2), fr.decode_ref(threads=2, v8_build=True)
         scale = max(1.0, float(np.abs(a).max()))
         assert float(np.abs(a - b).max()) / scale <= 2e-4, (w, h, gab, epf)
+
+
+# ---- the output encoder over its whole domain and format space (tests/output_sweep.py) -------------------------------
+import functools  # noqa: E402
+
+import output_sweep  # noqa: E402
+
+
+@functools.lru_cache(maxsize=None)
+def _sweep_inputs(variant):
+    return output_sweep.sweep_frame(*output_sweep.KERNEL_SIZE, variant, gab=False, epf_iters=0, output_kind=1)
+
+
+def _sweep_frame_as(ref, variant, **params):
+    base, t = _sweep_inputs(variant)
+    return frames.oracle_frame(dict(base, **params), t, ref.default_dequant_tables())
+
+
+@pytest.mark.parametrize("variant", [output_sweep.SIGNED, output_sweep.NONNEG])
+def test_sweep_frame_linear_pixels(ref, variant):
+    """The sweep frame's linear pixels: restatement == reference bit for bit (-0, 7e4 and 1e-8 included), and every
+    8x8 block is the three planted values exactly."""
+    fr = _sweep_frame_as(ref, variant)
+    o = fr.decode()
+    assert np.array_equal(bits(o), bits(fr.decode_ref()))
+    xs, ys = output_sweep.KERNEL_SIZE
+    a = output_sweep.planted_cbrt((xs + 7) // 8, (ys + 7) // 8, variant)
+    half = np.float32(0.5)
+    y, x = (a[..., 0] + a[..., 1]) * half, (a[..., 0] - a[..., 1]) * half
+    want = output_sweep.cube3(np.stack([y + x, y - x, a[..., 2]], axis=-1))
+    assert np.array_equal(bits(o), bits(np.repeat(np.repeat(want, 8, axis=0), 8, axis=1)[:ys, :xs]))
+
+
+@pytest.mark.parametrize("f", output_sweep.format_grid(), ids=output_sweep.fmt_id)
+def test_packed_output_over_the_sweep_frame(ref, f):
+    """The yardstick of tests/test_gpu_output_encoding.py on the formats no frame had tried -- low bit depths, half-float
+    with PQ / 709 / gamma / HLG, HLG RGBA, swapped floats -- over the encoder's whole domain: restatement == reference
+    (FromLinearStage + WriteToOutputStage) byte for byte, and oracle.pack_output on the linear pixels is that output."""
+    variant = output_sweep.variant_of(f)
+    fr = _sweep_frame_as(ref, variant, output_kind=2, out_format=f)
+    o, r = fr.decode(), fr.decode_ref()
+    assert o.shape == r.shape and o.dtype == r.dtype
+    ob, rb = [a.view(np.uint8).reshape(a.shape + (-1,)) for a in (o, r)]  # (swapped floats compare as bytes)
+    ne = np.argwhere((ob != rb).any(axis=-1))
+    assert len(ne) == 0, (len(ne), ne[:3].tolist(), ob[tuple(ne[0])].tolist(), rb[tuple(ne[0])].tolist())
+    lin = _sweep_frame_as(ref, variant).decode()
+    p = ref.pack_output(f, lin)
+    assert p.dtype == o.dtype and np.array_equal(p.view(np.uint8), o.view(np.uint8))
