@@ -302,6 +302,32 @@ JXLHIP_EXPORT int jxlhip_set_noise(jxlhip_ctx* ctx, const float lut[8], uint32_t
  * JXLHIP_ERR_UNSUPPORTED on a multi-device context, for a stripe and with undo_orientation > 1; the split calls refuse
  * a spline frame. */
 JXLHIP_EXPORT int jxlhip_set_splines(jxlhip_ctx* ctx, const struct jxlhip_splines* splines);
+/* A reference frame for patches (what a kReferenceOnly frame with save_as_reference = slot leaves in
+ * PassesSharedState::reference_frames, dec_cache.h; the frame must have been saved BEFORE the colour transform, i.e. in
+ * XYB): copies the three planes X, Y, B of xsize x ysize floats (stride_floats per row; host memory, or device memory of
+ * the context's device when on_device != 0) into context-owned device memory.  The slot (0..3) holds until it is
+ * replaced, cleared (xsize == 0 or ysize == 0; planes may then be NULL) or the context is destroyed;
+ * jxlhip_frame_begin does not touch it.  Synchronises the context's stream.  Set the slots before
+ * jxlhip_set_patches: the uploaded dictionary points into them, and jxlhip_decode_frame answers JXLHIP_ERR_STATE when
+ * a slot was set or cleared in between.  JXLHIP_ERR_UNSUPPORTED on a multi-device context. */
+JXLHIP_EXPORT int jxlhip_set_reference_frame(jxlhip_ctx* ctx, uint32_t slot, uint32_t xsize, uint32_t ysize,
+                                             const float* const planes[3], size_t stride_floats, int on_device);
+/* Patches of the current frame (FrameHeader::kPatches; jxlhip_patches_decode / jxlhip_patches_from_list,
+ * jxl_hip_frame.h): checks the dictionary against the slots present and the frame's padded size, bins its patches by
+ * tile and uploads them; the object may be destroyed when this returns.  jxlhip_decode_frame then blends the patches
+ * where the reference's pipeline has its patch stage, behind the loop filters and in front of splines, upsampling and
+ * noise (dec_cache.cc:193-197; PatchDictionary::AddOneRow, dec_patch_dictionary.cc:319-357, PerformBlending,
+ * blending.cc:42-190), at coded size, in list order, with every output kind.  All eight colour blend modes, as on an
+ * image without an alpha channel: kNone keeps the frame, kReplace / kBlendAbove / kBlendBelow take the reference
+ * sample, kAdd / kAlphaWeightedAdd* add it, kMul multiplies by it (clamped to [0, 1] with the clamp flag,
+ * alpha.cc:82-93).  NULL or a dictionary without patches: the frame takes exactly its plain path.
+ * jxlhip_frame_begin resets it; frames that never call this are untouched.  JXLHIP_ERR_INVALID_ARGUMENT for a patch
+ * whose slot is empty or smaller than its rectangle, or that leaves the padded frame (the object was made for other
+ * slots or another frame); JXLHIP_ERR_UNSUPPORTED for a dictionary that uses extra channels
+ * (jxlhip_patches_list), after jxlhip_set_alpha (which refuses a patch frame in turn), on a multi-device context, for
+ * a stripe and with undo_orientation > 1; the split calls refuse a patch frame. */
+struct jxlhip_patches;
+JXLHIP_EXPORT int jxlhip_set_patches(jxlhip_ctx* ctx, const struct jxlhip_patches* patches);
 /* Upsampling of the current frame (FrameHeader::upsampling = factor: 2, 4 or 8; what cjxl writes by itself from
  * distance 10 on, and with --resampling).  jxlhip_frame_begin's xsize / ysize are then the CODED size; out_xsize /
  * out_ysize is the size the frame is upsampled and cropped to (the image), with ceil(out / factor) == coded in both
@@ -446,7 +472,11 @@ enum {
   JXLHIP_KERNEL_NOISE = 5,    /* photon noise (jxlhip_set_noise): k_noise_rng + k_noise_emit behind the frame's path */
   JXLHIP_KERNEL_SPLINES = 6,  /* splines (jxlhip_set_splines): k_splines behind the frame's path, in front of noise */
   JXLHIP_KERNEL_UPSAMPLE = 7, /* upsampling (jxlhip_set_upsampling): k_upsample behind the splines, in front of noise */
-  JXLHIP_KERNEL_COUNT = 8
+  JXLHIP_KERNEL_COUNT = 8,    /* the slots jxlhip_profile_read reports: FROZEN at 8, the size of its callers' arrays */
+  /* WARNING: the slots from here on equal or exceed JXLHIP_KERNEL_COUNT -- never index an array of
+   * JXLHIP_KERNEL_COUNT with them; size arrays with JXLHIP_KERNEL_COUNT_EX and read with jxlhip_profile_read_ex */
+  JXLHIP_KERNEL_PATCHES = 8,  /* patches (jxlhip_set_patches): k_patches behind the frame's path, in front of the splines */
+  JXLHIP_KERNEL_COUNT_EX = 9  /* every slot; grows with each new one (new slots are appended here only) */
 };
 /* A hint, not a contract: `frames_in_flight` = how many contexts the caller keeps busy on this device at the same time
  * (a pool of decoders over a queue of images; 1 = this context runs alone, the default).  It only moves the frame size
@@ -466,6 +496,10 @@ JXLHIP_EXPORT int jxlhip_profile_enable(jxlhip_ctx* ctx, int enable);
 JXLHIP_EXPORT int jxlhip_profile_read(jxlhip_ctx* ctx,
                                       float ms[JXLHIP_KERNEL_COUNT],
                                       uint32_t launches[JXLHIP_KERNEL_COUNT]);
+/* The call to use from now on: the same for the first `count` slots, count <= JXLHIP_KERNEL_COUNT_EX of the library
+ * at hand (JXLHIP_ERR_INVALID_ARGUMENT beyond it).  The caller says how large its arrays are, so later slots need no
+ * further variant of this call; jxlhip_profile_read stays as jxlhip_profile_read_ex(..., 8) for compiled callers. */
+JXLHIP_EXPORT int jxlhip_profile_read_ex(jxlhip_ctx* ctx, float* ms, uint32_t* launches, uint32_t count);
 
 /* ---- device-side helpers for rows of SURVEY 8(a) outside the two phases -- */
 /* a5: DequantMatrices (quant_weights.h:350-428).  One parameter set per

@@ -19,9 +19,16 @@
  * planes) incl. the squeeze `cjxl -p` puts on them and palettes without deltas, progressive passes, orientation,
  * photon noise and splines (drawn on the device, jxlhip_set_noise / jxlhip_set_splines), frames upsampled 2x / 4x / 8x
  * (what cjxl writes from distance 10 on and with --resampling; upsampled on the device, jxlhip_set_upsampling, with the
- * image header's custom weights or the format's defaults) of images without extra channels.
+ * image header's custom weights or the format's defaults) of images without extra channels, and the files cjxl writes
+ * with patches at its default effort: any number of kReferenceOnly frames -- Modular, XYB, one group, decoded on the
+ * host (jxlhip_modular_frame_decode) and handed to jxlhip_set_reference_frame(save_as_reference) -- in front of exactly
+ * one regular last frame whose flags may include kPatches (jxlhip_patches_decode, blended on the device,
+ * jxlhip_set_patches), of images without extra channels.  The four reference slots of the context are cleared at the
+ * start of every call; the info struct describes the visible frame.
  * Everything this front-end does not decode is refused with JXLHIP_ERR_UNSUPPORTED so that the caller can hand the
- * file to libjxl's CPU decoder: Modular-mode frames, animation / multiple frames, previews, patches,
+ * file to libjxl's CPU decoder: Modular-mode frames, animation / layers / any other sequence of frames, previews,
+ * reference frames of more than one group or with an RCT, squeeze or delta palette, patches on images with extra channels,
+ * a last frame that blends (blend_mode other than kReplace) behind a reference frame,
  * chroma subsampling and YCbCr (JPEG recompression), upsampled frames of images with extra channels (alpha included:
  * cjxl downsamples them along with the colour, ec_upsampling != 1, and no stream the test oracle writes has one to
  * check against), extra channels upsampled on their own, cropped frames, DC frames, RAW dequant tables, RCT / delta

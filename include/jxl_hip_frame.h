@@ -271,6 +271,47 @@ typedef struct jxlhip_spline_segment {
 JXLHIP_EXPORT int jxlhip_splines_segments(const jxlhip_splines* s, uint32_t xsize, uint32_t ysize, float y_to_x,
                                           float y_to_b, jxlhip_spline_segment* out, size_t cap, size_t* count);
 
+/* ---- Patches (FrameHeader::kPatches) ----
+ * jxlhip_patches: the patch dictionary of one frame (PatchDictionary after PatchDictionary::Decode,
+ * lib/jxl/dec_patch_dictionary.cc:31-178), an opaque object: a list of placements, each copying a rectangle of one of
+ * the four reference-frame slots (jxlhip_set_reference_frame, jxl_hip.h) to a position of the frame with a blend mode
+ * for the colour channels and one per extra channel.  The modes are PatchBlendMode (dec_patch_dictionary.h:34-67). */
+enum { JXLHIP_PATCH_NONE = 0, JXLHIP_PATCH_REPLACE = 1, JXLHIP_PATCH_ADD = 2, JXLHIP_PATCH_MUL = 3,
+       JXLHIP_PATCH_BLEND_ABOVE = 4, JXLHIP_PATCH_BLEND_BELOW = 5, JXLHIP_PATCH_ALPHA_WEIGHTED_ADD_ABOVE = 6,
+       JXLHIP_PATCH_ALPHA_WEIGHTED_ADD_BELOW = 7 };
+typedef struct jxlhip_patch {       /* PatchPosition + its PatchReferencePosition + the colour PatchBlending */
+  uint32_t ref;                     /* reference-frame slot, 0..3 */
+  uint32_t ref_x0, ref_y0;          /* the rectangle inside the reference frame ... */
+  uint32_t xsize, ysize;            /* ... and its size, both >= 1 */
+  uint32_t x, y;                    /* where its top-left sample goes in the frame */
+  uint32_t mode, alpha_channel, clamp; /* colour blending; clamp is kept for kMul and the alpha modes only */
+} jxlhip_patch;
+typedef struct jxlhip_patches jxlhip_patches;
+/* Reads the dictionary at bit *bit_pos of data -- the start of the DC-global section of a frame with
+ * JXLHIP_FLAG_PATCHES (dec_frame.cc:272-288), in front of the splines bundle, the noise LUT and what
+ * jxlhip_dc_global_decode reads; *bit_pos advances to its end.  xsize / ysize: the frame's PADDED size (multiples of
+ * 8, FrameDimensions::xsize_padded), as the reference passes it; num_extra_channels: of the image; ref_sizes[slot] =
+ * (xsize, ysize) of the reference frame saved in that slot, (0, 0) = empty.  JXLHIP_ERR_BAD_STREAM on every condition
+ * the reference rejects (too many reference patches, patches or blendings; a slot >= 4 or empty; a rectangle outside
+ * its reference frame; a negative coordinate after a delta; a patch outside the frame; a blend mode >= 8; an alpha
+ * channel out of range; a bad final ANS state) and on truncation. */
+JXLHIP_EXPORT int jxlhip_patches_decode(const uint8_t* data, size_t size, size_t* bit_pos, uint32_t xsize, uint32_t ysize,
+                                        uint32_t num_extra_channels, const uint32_t ref_sizes[4][2], jxlhip_patches** out);
+/* The same object from a caller's list, in the order the stream would hold it (later patches are blended over earlier
+ * ones).  ec_blendings: num_patches x num_extra_channels triples (mode, alpha_channel, clamp), NULL without extra
+ * channels.  The decoder's per-patch checks apply (JXLHIP_ERR_BAD_STREAM); num_patches = 0 gives an empty dictionary. */
+JXLHIP_EXPORT int jxlhip_patches_from_list(uint32_t num_patches, const jxlhip_patch* patches, uint32_t num_extra_channels,
+                                           const uint32_t* ec_blendings, uint32_t xsize, uint32_t ysize,
+                                           const uint32_t ref_sizes[4][2], jxlhip_patches** out);
+/* Read-out in the layout jxlhip_patches_from_list takes: *num_patches is always written; num_extra_channels and
+ * uses_extra_channels when not NULL; patches (num_patches entries) and ec_blendings (3 x num_patches x
+ * num_extra_channels values) are filled when not NULL.  *uses_extra_channels: blending this dictionary needs the
+ * image's extra channels -- an alpha mode on an image that has extra channels, or an extra channel with any mode but
+ * kNone (without extra channels the alpha modes fall back to kAdd / kReplace, blending.cc:150-184). */
+JXLHIP_EXPORT int jxlhip_patches_list(const jxlhip_patches* p, uint32_t* num_patches, uint32_t* num_extra_channels,
+                                      uint32_t* uses_extra_channels, jxlhip_patch* patches, uint32_t* ec_blendings);
+JXLHIP_EXPORT void jxlhip_patches_destroy(jxlhip_patches* p);
+
 /* ---- The Modular-coded parts of a VarDCT frame: global MA tree and the DC groups ----
  * Replaces (libjxl tree, lib/jxl/): ModularFrameDecoder::DecodeGlobalInfo (dec_modular.cc:207-316),
  * FrameDecoder::ProcessDCGroup (dec_frame.cc:318-342) = DecodeVarDCTDC + DecodeAcMetadata
@@ -342,6 +383,21 @@ JXLHIP_EXPORT int jxlhip_modular_uses_dc_groups(const jxlhip_modular_tree* tree)
  * image's transforms; not thread-safe, and no group may be decoded afterwards. */
 JXLHIP_EXPORT int jxlhip_modular_extra_channel_f32(jxlhip_modular_tree* tree, uint32_t ec, uint32_t ec_bits,
                                                    uint32_t image_bits, float* out, size_t stride_floats);
+
+/* A Modular-coded XYB frame of one group -- the kReferenceOnly frame a patch dictionary copies from, as the reference
+ * encoder writes it (RoundtripPatchFrame, enc_patch_dictionary.cc) -- into three float planes X, Y, B of frame->xsize x
+ * frame->ysize (stride_floats per row): FrameDecoder::ProcessDCGlobal of a Modular frame (dec_frame.cc:268-302:
+ * DequantMatrices::DecodeDC only), ModularFrameDecoder::DecodeGlobalInfo with the three colour channels
+ * (dec_modular.cc:209-318) and ModularImageToDecodedRect (dec_modular.cc:564-632: the channels are Y, X, B - Y, scaled
+ * by DCQuant).  Reads from bit *bit_pos of data, the start of the frame's first section (advanced to the end of what
+ * the frame holds: its DC-group, AC-global and AC-group parts are empty).  The pixel entropy code may use LZ77, with
+ * the special distances of 2-D streams (dec_ans.h).  JXLHIP_ERR_UNSUPPORTED, with *why (may be NULL) naming the case
+ * in a static string: more than one group; an RCT, squeeze or delta palette; any flag, a loop filter, upsampling != 1
+ * or more than one pass in the frame header; save_before_color_transform == 0; a colour transform other than XYB; an
+ * image with extra channels.  JXLHIP_ERR_BAD_STREAM where the reference rejects the stream and on truncation. */
+JXLHIP_EXPORT int jxlhip_modular_frame_decode(const uint8_t* data, size_t size, size_t* bit_pos,
+                                              const jxlhip_frame_header* frame, float* const planes[3],
+                                              size_t stride_floats, const char** why);
 
 /* One DC group section (section 1 + dc_group of the TOC).  All outputs are FRAME-level arrays in the
  * layouts jxlhip_upload_side_info / jxlhip_dequant_dc take, of which this call fills the group's

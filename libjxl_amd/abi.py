@@ -9,6 +9,12 @@ _RUNNER_SO = os.path.join(_HERE, "csrc", "libjxl_threads_hip.so")
 
 KERNEL_COUNT = 8
 KERNEL_NAMES = ["prepare", "blocks", "filters", "fused", "epf0", "noise", "splines", "upsample"]
+# jxlhip_profile_read_ex: the slots above, then those added since (JXLHIP_KERNEL_PATCHES = 8)
+KERNEL_COUNT_EX = 9
+KERNEL_NAMES_EX = KERNEL_NAMES + ["patches"]
+# PatchBlendMode (JXLHIP_PATCH_*)
+PATCH_NONE, PATCH_REPLACE, PATCH_ADD, PATCH_MUL, PATCH_BLEND_ABOVE, PATCH_BLEND_BELOW, PATCH_ALPHA_WEIGHTED_ADD_ABOVE, \
+    PATCH_ALPHA_WEIGHTED_ADD_BELOW = range(8)
 
 
 class JxlHipError(RuntimeError):
@@ -232,7 +238,7 @@ EXPORTS = [
     "jxlhip_dequant_table_offset", "jxlhip_status_string", "jxlhip_create", "jxlhip_create_ex", "jxlhip_create_multi",
     "jxlhip_destroy", "jxlhip_last_error", "jxlhip_debug_reload_env", "jxlhip_set_stream",
     "jxlhip_frame_begin", "jxlhip_frame_set_inputs", "jxlhip_upload_side_info",
-    "jxlhip_submit_group", "jxlhip_set_alpha", "jxlhip_set_noise", "jxlhip_noise_rng_state", "jxlhip_set_splines", "jxlhip_set_upsampling", "jxlhip_alpha_staging", "jxlhip_decode_blocks", "jxlhip_halo_rows",
+    "jxlhip_submit_group", "jxlhip_set_alpha", "jxlhip_set_noise", "jxlhip_noise_rng_state", "jxlhip_set_splines", "jxlhip_set_upsampling", "jxlhip_set_reference_frame", "jxlhip_set_patches", "jxlhip_profile_read_ex", "jxlhip_alpha_staging", "jxlhip_decode_blocks", "jxlhip_halo_rows",
     "jxlhip_halo_export", "jxlhip_halo_import", "jxlhip_decode_filters", "jxlhip_decode_filters_rows", "jxlhip_stripe_begin",
     "jxlhip_stripe_finish", "jxlhip_decode_frame",
     "jxlhip_decode_frame_host", "jxlhip_decode_frame_pinned",
@@ -248,7 +254,7 @@ EXPORTS = [
     "jxlhip_ac_groups_decode_submit", "jxlhip_ac_groups_decode_submit_ex", "jxlhip_num_toc_entries", "jxlhip_toc_decode", "jxlhip_ac_global_decode_at",
     # include/jxl_hip_frame.h
     "jxlhip_frame_header_decode", "jxlhip_dc_global_decode", "jxlhip_noise_lut_decode", "jxlhip_splines_decode",
-    "jxlhip_splines_from_quantized", "jxlhip_splines_destroy", "jxlhip_splines_quantized", "jxlhip_splines_segments", "jxlhip_image_header_decode", "jxlhip_icc_decode", "jxlhip_output_opsin_matrix",
+    "jxlhip_splines_from_quantized", "jxlhip_splines_destroy", "jxlhip_splines_quantized", "jxlhip_splines_segments", "jxlhip_modular_frame_decode", "jxlhip_patches_decode", "jxlhip_patches_from_list", "jxlhip_patches_list", "jxlhip_patches_destroy", "jxlhip_image_header_decode", "jxlhip_icc_decode", "jxlhip_output_opsin_matrix",
     "jxlhip_modular_global_decode", "jxlhip_modular_tree_destroy", "jxlhip_dc_group_decode", "jxlhip_dc_group_decode_staged",
     "jxlhip_modular_ac_group_decode", "jxlhip_modular_ac_group_decode_f32", "jxlhip_modular_extra_channel_f32",
     "jxlhip_modular_groups_are_final", "jxlhip_modular_uses_dc_groups", "jxlhip_modular_finalize",
@@ -313,6 +319,15 @@ def load_library():
     L.jxlhip_splines_segments.argtypes = [vp, u32, u32, C.c_float, C.c_float, vp, sz, C.POINTER(sz)]
     L.jxlhip_set_splines.argtypes = [vp, vp]
     L.jxlhip_set_upsampling.argtypes = [vp, u32, C.POINTER(C.c_float), u32, u32]
+    L.jxlhip_patches_decode.argtypes = [vp, sz, C.POINTER(sz), u32, u32, u32, vp, C.POINTER(vp)]
+    L.jxlhip_patches_from_list.argtypes = [u32, vp, u32, vp, u32, u32, vp, C.POINTER(vp)]
+    L.jxlhip_patches_list.argtypes = [vp, C.POINTER(u32), C.POINTER(u32), C.POINTER(u32), vp, vp]
+    L.jxlhip_patches_destroy.argtypes = [vp]
+    L.jxlhip_modular_frame_decode.argtypes = [vp, sz, C.POINTER(sz), C.POINTER(FrameHeader), vp, sz, C.POINTER(C.c_char_p)]
+    L.jxlhip_patches_destroy.restype = None
+    L.jxlhip_set_reference_frame.argtypes = [vp, u32, u32, u32, vp, sz, i32]
+    L.jxlhip_set_patches.argtypes = [vp, vp]
+    L.jxlhip_profile_read_ex.argtypes = [vp, C.POINTER(C.c_float), C.POINTER(u32), u32]
     L.jxlhip_splines_quantized.argtypes = [vp, C.POINTER(u32), C.POINTER(sz), C.POINTER(i32), vp, vp, vp, vp]
     L.jxlhip_modular_global_decode.argtypes = [vp, sz, C.POINTER(sz), C.POINTER(FrameHeader), C.POINTER(vp)]
     L.jxlhip_modular_tree_destroy.argtypes = [vp]
@@ -435,3 +450,72 @@ def splines_quantized(handle, L=None):
                         sigma=dcts[128 * i + 96:128 * i + 128].tolist()))
         k += m
     return adj.value, out
+
+
+class Patch(C.Structure):
+    """jxlhip_patch"""
+    _fields_ = [(n, C.c_uint32) for n in ("ref", "ref_x0", "ref_y0", "xsize", "ysize", "x", "y", "mode", "alpha_channel",
+                                          "clamp")]
+
+
+def _ref_sizes(ref_sizes):
+    import numpy as np
+    a = np.zeros((4, 2), np.uint32)
+    for slot, wh in (ref_sizes.items() if isinstance(ref_sizes, dict) else enumerate(ref_sizes)):
+        a[slot] = wh
+    return a
+
+
+def patches_decode(data, bit_pos, xsize, ysize, ref_sizes, num_extra_channels=0, L=None):
+    """jxlhip_patches_decode at bit `bit_pos` of `data`; xsize / ysize = the frame's padded size, ref_sizes = {slot:
+    (xsize, ysize)} or a list of four pairs.  Returns (rc, handle, bit position behind the dictionary); free the handle
+    with patches_destroy."""
+    L = L or load_library()
+    data = bytes(data)
+    pos, h = C.c_size_t(bit_pos), C.c_void_p()
+    rs = _ref_sizes(ref_sizes)
+    rc = L.jxlhip_patches_decode(data, len(data), C.byref(pos), xsize, ysize, num_extra_channels, rs.ctypes.data,
+                                 C.byref(h))
+    return rc, h, pos.value
+
+
+def patches_from_list(patches, xsize, ysize, ref_sizes, num_extra_channels=0, ec_blendings=None, L=None):
+    """jxlhip_patches_from_list: an owned jxlhip_patches* (c_void_p) from a list of dicts with the fields of
+    jxlhip_patch (ref_x0, ref_y0, alpha_channel and clamp default to 0, ref to 0) or an [n, 10] uint32 array in their
+    order; ec_blendings: per patch, per extra channel a (mode, alpha_channel, clamp) triple.  Returns (rc, handle); free the handle with patches_destroy."""
+    import numpy as np
+    L = L or load_library()
+    if isinstance(patches, np.ndarray):  # [n, 10] uint32 in the field order of jxlhip_patch
+        keep = np.ascontiguousarray(patches, np.uint32)
+        assert keep.ndim == 2 and keep.shape[1] == len(Patch._fields_), keep.shape
+        arr = (Patch * max(1, len(keep))).from_buffer_copy(keep.tobytes() if len(keep) else bytes(C.sizeof(Patch)))
+    else:
+        arr = (Patch * max(1, len(patches)))()
+        for i, p in enumerate(patches):
+            for name, _ in Patch._fields_:
+                setattr(arr[i], name, int(p.get(name, 0)))
+    ec = np.asarray(ec_blendings if ec_blendings is not None else [], np.uint32).reshape(-1)
+    assert ec.size == 3 * len(patches) * num_extra_channels
+    rs = _ref_sizes(ref_sizes)
+    h = C.c_void_p()
+    rc = L.jxlhip_patches_from_list(len(patches), C.addressof(arr), num_extra_channels, ec.ctypes.data if ec.size else None,
+                                    xsize, ysize, rs.ctypes.data, C.byref(h))
+    return rc, h
+
+
+def patches_list(handle, L=None):
+    """jxlhip_patches_list: (list of patch dicts, num_extra_channels, uses_extra_channels, ec_blendings as an array of
+    shape (patches, extra channels, 3))."""
+    import numpy as np
+    L = L or load_library()
+    n, nec, uses = C.c_uint32(0), C.c_uint32(0), C.c_uint32(0)
+    assert L.jxlhip_patches_list(handle, C.byref(n), C.byref(nec), C.byref(uses), None, None) == 0
+    arr = (Patch * max(1, n.value))()
+    ec = np.zeros(max(1, 3 * n.value * nec.value), np.uint32)
+    assert L.jxlhip_patches_list(handle, C.byref(n), None, None, C.addressof(arr), ec.ctypes.data) == 0
+    out = [{name: int(getattr(arr[i], name)) for name, _ in Patch._fields_} for i in range(n.value)]
+    return out, nec.value, bool(uses.value), ec[:3 * n.value * nec.value].reshape(n.value, nec.value, 3)
+
+
+def patches_destroy(handle, L=None):
+    (L or load_library()).jxlhip_patches_destroy(handle)

@@ -83,9 +83,17 @@ int ExtractCodestream(const uint8_t* data, size_t size, std::vector<uint8_t>* st
   return JXLHIP_OK;
 }
 
+// a kReferenceOnly frame in front of the visible one: what it leaves in its slot (ParseHeaders decodes it)
+struct ReferenceFrame {
+  uint32_t xsize = 0, ysize = 0;  // 0: the slot is empty
+  std::vector<float> xyb;         // three dense planes
+};
+
 struct ParsedHeaders {
   jxlhip_image_header ih;
-  jxlhip_frame_header fh;
+  jxlhip_frame_header fh;  // of the visible frame
+  ReferenceFrame refs[4];
+  const char* why = "";    // JXLHIP_ERR_UNSUPPORTED from a reference frame: which case
   size_t frame_bit_pos;  // first bit after the frame header (= the TOC)
   jxlhip_extra_channel extra[4];
   int alpha_index;       // first extra channel of type alpha, -1 = none
@@ -94,7 +102,39 @@ struct ParsedHeaders {
   size_t icc_size;       // size of the original's ICC profile (0 = an enumerated colour encoding)
 };
 
-// image header + frame header + the eligibility rules of this back-end
+// A kReferenceOnly frame (what cjxl writes in front of a frame with patches: the sheet its dictionary copies from):
+// decoded on the host into h->refs[save_as_reference]; *pos moves from the first bit behind its frame header to the
+// header of the next frame.
+int ReadReferenceFrame(const uint8_t* cs, size_t n, const jxlhip_frame_header& fh, size_t* pos, ParsedHeaders* h) {
+  if (!fh.is_modular || fh.num_toc_entries != 1) {
+    h->why = fh.is_modular ? "a reference frame of more than one section" : "a reference frame coded in VarDCT";
+    return JXLHIP_ERR_UNSUPPORTED;
+  }
+  if (fh.save_as_reference > 3) return JXLHIP_ERR_BAD_STREAM;
+  uint64_t off = 0, total = 0;
+  uint32_t sz = 0;
+  int rc = jxlhip_toc_decode(cs, n, pos, 1, &off, &sz, &total);
+  if (rc) return rc;
+  const size_t base = *pos / 8;
+  if (total > n - base) return JXLHIP_ERR_BAD_STREAM;
+  ReferenceFrame& r = h->refs[fh.save_as_reference];
+  r.xsize = r.ysize = 0;
+  const size_t plane = (size_t)fh.xsize * fh.ysize;
+  if (fh.xsize > fh.group_dim || fh.ysize > fh.group_dim) {
+    h->why = "a Modular frame of more than one group";
+    return JXLHIP_ERR_UNSUPPORTED;
+  }
+  r.xyb.assign(3 * plane, 0.0f);
+  float* const planes[3] = {r.xyb.data(), r.xyb.data() + plane, r.xyb.data() + 2 * plane};
+  size_t spos = 0;
+  if ((rc = jxlhip_modular_frame_decode(cs + base + off, sz, &spos, &fh, planes, fh.xsize, &h->why))) return rc;
+  r.xsize = fh.xsize;
+  r.ysize = fh.ysize;
+  *pos = (base + (size_t)total) * 8;
+  return JXLHIP_OK;
+}
+
+// image header + the reference frames + the visible frame's header + the eligibility rules of this back-end
 int ParseHeaders(const uint8_t* cs, size_t n, ParsedHeaders* h) {
   size_t pos = 0;
   int rc = jxlhip_image_header_decode(cs, n, &pos, h->extra, 4, &h->ih);
@@ -130,11 +170,29 @@ int ParseHeaders(const uint8_t* cs, size_t n, ParsedHeaders* h) {
   info.bits_per_sample = ih.bit_depth.bits_per_sample;
   info.have_animation = 0;
   info.have_timecodes = 0;
-  rc = jxlhip_frame_header_decode(cs, n, &pos, &info, &h->fh);
-  if (rc) return rc;
+  // any number of kReferenceOnly frames, then exactly one regular frame, the last of the file: every other sequence
+  // (animation, layers, DC frames) is outside this front-end
+  for (;;) {
+    rc = jxlhip_frame_header_decode(cs, n, &pos, &info, &h->fh);
+    if (rc) return rc;
+    if (h->fh.frame_type != JXLHIP_FRAME_REFERENCE_ONLY || h->fh.is_last) break;
+    if ((rc = ReadReferenceFrame(cs, n, h->fh, &pos, h))) return rc;
+  }
   const jxlhip_frame_header& fh = h->fh;
+  // (patches would have to blend the extra channels as well: refused for now)
+  if ((fh.flags & JXLHIP_FLAG_PATCHES) && ih.num_extra_channels != 0) {
+    h->why = "patches on an image with extra channels";
+    return JXLHIP_ERR_UNSUPPORTED;
+  }
+  // a last frame that blends over a saved frame (kAdd, kBlend, kMul, ... with blend_source naming a filled slot) is a
+  // layer, not a patch frame: the reference blends it (blending.cc:23-40), this front-end would decode it as kReplace
+  for (const ReferenceFrame& r : h->refs)
+    if (r.xsize != 0 && fh.blend_mode != 0) {
+      h->why = "a frame that blends over a reference frame";
+      return JXLHIP_ERR_UNSUPPORTED;
+    }
   if (fh.is_modular || fh.color_transform != JXLHIP_CT_XYB || fh.frame_type != JXLHIP_FRAME_REGULAR ||
-      (fh.flags & (JXLHIP_FLAG_PATCHES | JXLHIP_FLAG_USE_DC_FRAME)) ||
+      (fh.flags & JXLHIP_FLAG_USE_DC_FRAME) ||
       fh.chroma_mode[0] || fh.chroma_mode[1] || fh.chroma_mode[2] || fh.dc_level != 0 || fh.custom_size_or_origin ||
       !fh.is_last)
     return JXLHIP_ERR_UNSUPPORTED;
@@ -443,7 +501,11 @@ int jxlhip_codestream_basic_info(const uint8_t* data, size_t size, jxlhip_codest
   int rc = ExtractCodestream(data, size, &storage, &cs, &n, &container);
   if (rc) return rc;
   ParsedHeaders h;
-  if ((rc = ParseHeaders(cs, n, &h))) return rc;
+  try {
+    if ((rc = ParseHeaders(cs, n, &h))) return rc;
+  } catch (const std::bad_alloc&) {
+    return JXLHIP_ERR_OUT_OF_MEMORY;
+  }
   FillInfo(h, container, info);
   return JXLHIP_OK;
 }
@@ -526,6 +588,11 @@ static int DecodeCodestreamImpl(jxlhip_ctx* c, jxlhip_parallel_runner runner, vo
   if (!c || !data || !out || output_kind > JXLHIP_OUT_PACKED || (output_kind == JXLHIP_OUT_PACKED && !out_format))
     return JXLHIP_ERR_INVALID_ARGUMENT;
   JXLHIP_NO_MULTI(c);
+  // one file's reference frames never reach the next
+  for (uint32_t slot = 0; slot < 4; slot++) {
+    const int cleared = jxlhip_set_reference_frame(c, slot, 0, 0, nullptr, 0, 0);
+    if (cleared) return cleared;
+  }
   PhaseClock clock(c->cs_phase_ms);
   const bool verbose = jxlhip_env::Get().codestream_verbose.load(std::memory_order_relaxed);
   g_upload_wait_on.store(verbose);
@@ -537,7 +604,14 @@ static int DecodeCodestreamImpl(jxlhip_ctx* c, jxlhip_parallel_runner runner, vo
   if (rc) return Fail(c, rc, "not a JPEG XL codestream or container");
   ParsedHeaders h;
   if ((rc = ParseHeaders(cs, n, &h)))
-    return Fail(c, rc, rc == JXLHIP_ERR_UNSUPPORTED ? "stream uses features outside the VarDCT back-end" : "invalid headers");
+    return Fail(c, rc, rc == JXLHIP_ERR_UNSUPPORTED ? (h.why[0] ? h.why : "stream uses features outside the VarDCT back-end") : "invalid headers");
+  for (uint32_t slot = 0; slot < 4; slot++) {
+    const ReferenceFrame& r = h.refs[slot];
+    if (r.xsize == 0) continue;
+    const size_t plane = (size_t)r.xsize * r.ysize;
+    const float* const planes[3] = {r.xyb.data(), r.xyb.data() + plane, r.xyb.data() + 2 * plane};
+    if ((rc = jxlhip_set_reference_frame(c, slot, r.xsize, r.ysize, planes, r.xsize, 0))) return rc;
+  }
   jxlhip_codestream_info info;
   FillInfo(h, container, &info);
   const jxlhip_image_header& ih = h.ih;
@@ -572,7 +646,20 @@ static int DecodeCodestreamImpl(jxlhip_ctx* c, jxlhip_parallel_runner runner, vo
   // ---- DC global: quantizer, block context map, colour correlation; the global modular tree
   jxlhip_dc_global dcg;
   size_t spos = 0;  // bit position inside section 0 (the only section of a single-section frame)
-  // the splines bundle leads the section (dec_frame.cc:289-293); jxlhip_dc_global_decode reads on from behind it
+  // the patch dictionary leads the section (dec_frame.cc:272-288), the splines bundle follows (:289-293);
+  // jxlhip_dc_global_decode reads on from behind them
+  std::unique_ptr<jxlhip_patches, void (*)(jxlhip_patches*)> patches(nullptr, jxlhip_patches_destroy);
+  if (fh.flags & JXLHIP_FLAG_PATCHES) {
+    uint32_t ref_sizes[4][2];
+    for (int slot = 0; slot < 4; slot++) ref_sizes[slot][0] = h.refs[slot].xsize, ref_sizes[slot][1] = h.refs[slot].ysize;
+    jxlhip_patches* pt = nullptr;
+    if ((rc = jxlhip_patches_decode(sec(0), sz[0], &spos, fh.xsize_blocks * 8, fh.ysize_blocks * 8, 0, ref_sizes, &pt)))
+      return Fail(c, rc, "invalid patch dictionary");
+    patches.reset(pt);
+    uint32_t count = 0;
+    if ((rc = jxlhip_patches_list(pt, &count, nullptr, nullptr, nullptr, nullptr))) return Fail(c, rc, "invalid patch dictionary");
+    if (count == 0) patches.reset();  // an empty dictionary: the frame takes its plain path
+  }
   std::unique_ptr<jxlhip_splines, void (*)(jxlhip_splines*)> splines(nullptr, jxlhip_splines_destroy);
   if (fh.flags & JXLHIP_FLAG_SPLINES) {
     jxlhip_splines* sp = nullptr;
@@ -585,7 +672,7 @@ static int DecodeCodestreamImpl(jxlhip_ctx* c, jxlhip_parallel_runner runner, vo
     size_t npos = spos;
     if ((rc = jxlhip_noise_lut_decode(sec(0), sz[0], &npos, noise_lut))) return Fail(c, rc, "invalid noise parameters");
   }
-  if ((rc = jxlhip_dc_global_decode(sec(0), sz[0], &spos, fh.flags & ~(uint64_t)JXLHIP_FLAG_SPLINES, &dcg)))
+  if ((rc = jxlhip_dc_global_decode(sec(0), sz[0], &spos, fh.flags & ~(uint64_t)(JXLHIP_FLAG_SPLINES | JXLHIP_FLAG_PATCHES), &dcg)))
     return Fail(c, rc, "invalid DC global section");
   jxlhip_modular_tree* tree_raw = nullptr;
   if ((rc = jxlhip_modular_global_decode(sec(0), sz[0], &spos, &fh, &tree_raw)))
@@ -845,7 +932,7 @@ static int DecodeCodestreamImpl(jxlhip_ctx* c, jxlhip_parallel_runner runner, vo
     c->have_inputs = true;
     c->blocks_done = false;
     DropPrepared(c);  // (new maps, and used_acs above)
-    if ((rc = PrepareAhead(c, (fh.flags & JXLHIP_FLAG_NOISE) || splines || fh.upsampling > 1))) return rc;  // under the AC groups' entropy decode instead of in front of the frame's kernels
+    if ((rc = PrepareAhead(c, (fh.flags & JXLHIP_FLAG_NOISE) || splines || patches || fh.upsampling > 1))) return rc;  // under the AC groups' entropy decode instead of in front of the frame's kernels
     clock.Mark(JXLHIP_PHASE_SIDE_INFO);
     // AC groups on the runner: entropy decode into pinned staging slots + uploads
     if (ac_in_pipeline) {
@@ -949,6 +1036,7 @@ static int DecodeCodestreamImpl(jxlhip_ctx* c, jxlhip_parallel_runner runner, vo
   // photon noise: the stream's only frame is visible frame 1 (FrameDecoder::InitFrame counts it before decoding,
   // dec_frame.cc:160-168)
   if ((fh.flags & JXLHIP_FLAG_NOISE) && (rc = jxlhip_set_noise(c, noise_lut, 1, 0))) return rc;
+  if (patches && (rc = jxlhip_set_patches(c, patches.get()))) return rc;
   if (splines && (rc = jxlhip_set_splines(c, splines.get()))) return rc;
   if ((rc = jxlhip_decode_frame(c, out, out_stride, out_plane_stride))) return rc;
   if ((rc = jxlhip_sync(c))) return rc;

@@ -280,6 +280,23 @@ struct jxlhip_ctx {
   std::vector<uint32_t> spl_host_tiles;
   Event spl_ev;
   bool spl_ev_pending = false;
+  // jxlhip_set_reference_frame: the four reference-frame slots patches copy from, each three dense XYB planes of
+  // ref_w x ref_h floats (0: empty); they outlive frames.  jxlhip_set_patches: the dictionary of the current frame
+  // (frame_begin resets patches_on), binned by 64 x 16 tile (kernels_patches.hip); pat_tiles = tile_start (tiles + 1),
+  // tile_idx, active tiles.  The records point into the slots.  The host copies stay alive until pat_ev says their
+  // upload is done.
+  DevBuf<float> ref_planes[4];
+  uint32_t ref_w[4] = {0, 0, 0, 0}, ref_h[4] = {0, 0, 0, 0};
+  bool patches_on = false;
+  uint64_t ref_serial = 0, pat_ref_serial = 0;  // set_reference_frame calls so far / at the dictionary's upload
+  DevBuf<PatchRec> pat_recs;
+  DevBuf<uint32_t> pat_tiles;
+  uint32_t pat_tiles_x = 0, pat_num_tiles = 0, pat_num_active = 0;
+  size_t pat_entries = 0;
+  std::vector<PatchRec> pat_host_recs;
+  std::vector<uint32_t> pat_host_tiles;
+  Event pat_ev;
+  bool pat_ev_pending = false;
   // jxlhip_set_upsampling: the current frame is upsampled by ups_factor (1 = not; frame_begin resets) to ups_xsize x
   // ups_ysize; ups_planes = the filtered frame as planar XYB at CODED size (kernels_upsample.hip; noise_buf then holds
   // the upsampled planes + the random planes at output size), ups_weights = the factor's kernels (UpsampleKernels),

@@ -352,6 +352,7 @@ int jxlhip_frame_begin(jxlhip_ctx* c, const jxlhip_frame_params* p) {
   c->blocks_done = false;
   c->noise_on = false;
   c->splines_on = false;
+  c->patches_on = false;
   c->ups_factor = 1;
   return JXLHIP_OK;
 }
@@ -412,6 +413,7 @@ int jxlhip_set_alpha(jxlhip_ctx* c, const float* host_plane, size_t stride_float
   if (!c || !host_plane) return JXLHIP_ERR_INVALID_ARGUMENT;
   if (!c->have_frame) return Fail(c, JXLHIP_ERR_STATE, "set_alpha before frame_begin");
   if (c->ups_factor > 1) return Fail(c, JXLHIP_ERR_UNSUPPORTED, "alpha on an upsampled frame");
+  if (c->patches_on) return Fail(c, JXLHIP_ERR_UNSUPPORTED, "alpha on a frame with patches (they would have to blend it)");
   if (c->multi) {  // every stripe takes its own rows of the plane
     for (MultiChild& k : c->multi->kids) {
       const int rc = jxlhip_set_alpha(k.ctx, host_plane, stride_floats);
@@ -548,6 +550,131 @@ int jxlhip_set_splines(jxlhip_ctx* c, const jxlhip_splines* s) {
   c->spl_num_active = active;
   c->spl_entries = entries;
   c->splines_on = true;
+  return JXLHIP_OK;
+}
+
+// A reference frame for patches: three XYB planes into slot `slot` of the context (dense, xsize floats per row).
+int jxlhip_set_reference_frame(jxlhip_ctx* c, uint32_t slot, uint32_t xsize, uint32_t ysize, const float* const planes[3],
+                               size_t stride_floats, int on_device) {
+  if (!c || slot > 3) return JXLHIP_ERR_INVALID_ARGUMENT;
+  if (c->multi) return Fail(c, JXLHIP_ERR_UNSUPPORTED, "reference frames on a multi-device context");
+  c->ref_serial++;  // (an uploaded dictionary points into the slots: DecodeFrameFeatures refuses it from here on)
+  if (xsize == 0 || ysize == 0) {  // cleared; the memory stays for the next frame of the slot
+    c->ref_w[slot] = c->ref_h[slot] = 0;
+    return JXLHIP_OK;
+  }
+  if (!planes || !planes[0] || !planes[1] || !planes[2]) return Fail(c, JXLHIP_ERR_INVALID_ARGUMENT, "null reference plane");
+  if (stride_floats < xsize) return Fail(c, JXLHIP_ERR_INVALID_ARGUMENT, "reference stride %zu < xsize", stride_floats);
+  HIPCHK(c, hipSetDevice(c->device));
+  c->ref_w[slot] = c->ref_h[slot] = 0;
+  const size_t plane = (size_t)xsize * ysize;
+  HIPCHK(c, hipStreamSynchronize(c->stream));  // an earlier frame's k_patches may still read the slot
+  const int rc = c->ref_planes[slot].Reserve(c, 3 * plane);
+  if (rc) return rc;
+  for (int k = 0; k < 3; k++)
+    HIPCHK(c, hipMemcpy2DAsync(c->ref_planes[slot] + k * plane, xsize * sizeof(float), planes[k], stride_floats * sizeof(float),
+                               xsize * sizeof(float), ysize, on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice,
+                               c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));  // (the caller's planes are free when this returns)
+  c->ref_w[slot] = xsize;
+  c->ref_h[slot] = ysize;
+  return JXLHIP_OK;
+}
+
+// Patches of the current frame (FrameHeader::kPatches): the dictionary as records of k_patches, binned by 64 x 16 tile
+// in dictionary order; frame_begin resets to "no patches".
+int jxlhip_set_patches(jxlhip_ctx* c, const jxlhip_patches* s) {
+  if (!c) return JXLHIP_ERR_INVALID_ARGUMENT;
+  if (c->multi) return Fail(c, JXLHIP_ERR_UNSUPPORTED, "patches on a multi-device context");
+  if (!c->have_frame) return Fail(c, JXLHIP_ERR_STATE, "set_patches before frame_begin");
+  if (c->f.group_y0 != 0 || c->f.group_rows != c->f.ysg) return Fail(c, JXLHIP_ERR_UNSUPPORTED, "patches with stripes");
+  if (c->p.undo_orientation > 1)
+    return Fail(c, JXLHIP_ERR_UNSUPPORTED, "patches with undo_orientation %u", c->p.undo_orientation);
+  c->patches_on = false;
+  if (!s) return JXLHIP_OK;
+  uint32_t n = 0, nec = 0, uses_ec = 0;
+  int rc = jxlhip_patches_list(s, &n, &nec, &uses_ec, nullptr, nullptr);
+  if (rc) return Fail(c, rc, "invalid patch dictionary");
+  if (n == 0) return JXLHIP_OK;  // nothing reaches the frame: the plain path
+  if (uses_ec) return Fail(c, JXLHIP_ERR_UNSUPPORTED, "patches that blend extra channels");
+  if (c->fp.alpha) return Fail(c, JXLHIP_ERR_UNSUPPORTED, "patches on a frame with alpha (they would have to blend it)");
+  std::vector<jxlhip_patch> list(n);
+  if ((rc = jxlhip_patches_list(s, &n, nullptr, nullptr, list.data(), nullptr))) return Fail(c, rc, "invalid patch dictionary");
+  const uint32_t W = c->f.xsize, H = c->f.ysize;
+  const uint64_t WP = ((uint64_t)W + 7) & ~7ull, HP = ((uint64_t)H + 7) & ~7ull;  // FrameDimensions::xsize_padded
+  HIPCHK(c, hipSetDevice(c->device));
+  if (c->pat_ev_pending) {  // the previous frame's upload still reads the host copies
+    HIPCHK(c, hipEventSynchronize(c->pat_ev));
+    c->pat_ev_pending = false;
+  }
+  const uint32_t tx = (W + 63) / 64, ty = (H + 15) / 16, tiles = tx * ty;
+  std::vector<PatchRec>& hr = c->pat_host_recs;
+  hr.clear();
+  std::vector<uint32_t> count(tiles + 1, 0);
+  for (uint32_t i = 0; i < n; i++) {
+    const jxlhip_patch& p = list[i];
+    if (p.ref > 3 || c->ref_w[p.ref] == 0)
+      return Fail(c, JXLHIP_ERR_INVALID_ARGUMENT, "patch %u: reference slot %u is empty", i, p.ref);
+    const uint32_t rw = c->ref_w[p.ref], rh = c->ref_h[p.ref];
+    if (p.xsize == 0 || p.ysize == 0 || (uint64_t)p.ref_x0 + p.xsize > rw || (uint64_t)p.ref_y0 + p.ysize > rh)
+      return Fail(c, JXLHIP_ERR_INVALID_ARGUMENT, "patch %u: %ux%u at (%u, %u) leaves the %ux%u frame of slot %u", i, p.xsize,
+                  p.ysize, p.ref_x0, p.ref_y0, rw, rh, p.ref);
+    if ((uint64_t)p.x + p.xsize > WP || (uint64_t)p.y + p.ysize > HP)
+      return Fail(c, JXLHIP_ERR_INVALID_ARGUMENT, "patch %u: %ux%u at (%u, %u) leaves the frame", i, p.xsize, p.ysize, p.x, p.y);
+    if (p.mode > 7) return Fail(c, JXLHIP_ERR_INVALID_ARGUMENT, "patch %u: blend mode %u", i, p.mode);
+    if (p.mode == JXLHIP_PATCH_NONE || p.x >= W || p.y >= H) continue;  // the frame keeps its samples
+    PatchRec r;
+    r.x0 = (int32_t)p.x;
+    r.y0 = (int32_t)p.y;
+    r.x1 = (int32_t)std::min<uint64_t>((uint64_t)p.x + p.xsize, W);
+    r.y1 = (int32_t)std::min<uint64_t>((uint64_t)p.y + p.ysize, H);
+    r.src = c->ref_planes[p.ref] + (size_t)p.ref_y0 * rw + p.ref_x0;
+    r.stride = rw;
+    r.plane = rw * rh;
+    // PerformBlending's colour modes without an alpha channel (blending.cc:150-184)
+    r.op = p.mode == JXLHIP_PATCH_MUL ? (p.clamp ? kPatchOpMulClamp : kPatchOpMul)
+           : (p.mode == JXLHIP_PATCH_ADD || p.mode >= JXLHIP_PATCH_ALPHA_WEIGHTED_ADD_ABOVE) ? kPatchOpAdd
+                                                                                             : kPatchOpReplace;
+    r.pad = 0;
+    hr.push_back(r);
+    for (uint32_t y = (uint32_t)r.y0 / 16; y <= (uint32_t)(r.y1 - 1) / 16; y++)
+      for (uint32_t x = (uint32_t)r.x0 / 64; x <= (uint32_t)(r.x1 - 1) / 64; x++) count[y * tx + x + 1]++;
+  }
+  std::vector<uint32_t>& ht = c->pat_host_tiles;
+  ht.assign(tiles + 1, 0);
+  uint32_t active = 0;
+  uint64_t total = 0;
+  for (uint32_t t = 0; t < tiles; t++) {
+    active += count[t + 1] != 0;
+    total += count[t + 1];
+    ht[t + 1] = (uint32_t)total;
+  }
+  if (total == 0) return JXLHIP_OK;
+  if (total > 0xFFFFFFFFull - tiles - active - 1) return Fail(c, JXLHIP_ERR_OUT_OF_MEMORY, "patch list too long");
+  const size_t entries = (size_t)total;
+  ht.resize(tiles + 1 + entries + active);
+  uint32_t* fill = count.data();  // write cursor per tile
+  for (uint32_t t = 0; t < tiles; t++) fill[t] = ht[t];
+  for (uint32_t i = 0; i < (uint32_t)hr.size(); i++) {
+    const PatchRec& r = hr[i];
+    for (uint32_t y = (uint32_t)r.y0 / 16; y <= (uint32_t)(r.y1 - 1) / 16; y++)
+      for (uint32_t x = (uint32_t)r.x0 / 64; x <= (uint32_t)(r.x1 - 1) / 64; x++) ht[tiles + 1 + fill[y * tx + x]++] = i;
+  }
+  for (uint32_t t = 0, a = 0; t < tiles; t++)
+    if (ht[t + 1] != ht[t]) ht[tiles + 1 + entries + a++] = t;
+  if ((rc = c->pat_recs.Reserve(c, hr.size()))) return rc;
+  if ((rc = c->pat_tiles.Reserve(c, ht.size()))) return rc;
+  HIPCHK(c, hipMemcpyAsync(c->pat_recs, hr.data(), hr.size() * sizeof(PatchRec), hipMemcpyHostToDevice, c->stream));
+  HIPCHK(c, hipMemcpyAsync(c->pat_tiles, ht.data(), ht.size() * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
+  HIPCHK(c, c->pat_ev.Create());
+  HIPCHK(c, hipEventRecord(c->pat_ev, c->stream));
+  c->pat_ev_pending = true;
+  c->pat_tiles_x = tx;
+  c->pat_num_tiles = tiles;
+  c->pat_num_active = active;
+  c->pat_entries = entries;
+  c->pat_ref_serial = c->ref_serial;
+  c->patches_on = true;
   return JXLHIP_OK;
 }
 
@@ -882,7 +1009,7 @@ int jxlhip::PrepareAhead(jxlhip_ctx* c, bool render_stages) {
   // changes the output kind -- prepares again: correct, and one launch.
   const bool stripe = c->f.group_y0 != 0 || c->f.group_rows != c->f.ysg;
   const uint32_t kind = c->p.output_kind;
-  if (render_stages || c->noise_on || c->splines_on || c->ups_factor > 1) c->p.output_kind = JXLHIP_OUT_XYB_PLANAR;  // as DecodeFrameFeatures
+  if (render_stages || c->noise_on || c->splines_on || c->patches_on || c->ups_factor > 1) c->p.output_kind = JXLHIP_OUT_XYB_PLANAR;  // as DecodeFrameFeatures
   const int fused = WantFused(c) ? (stripe ? 2 : 1) : 0;
   c->p.output_kind = kind;
   int block;
@@ -973,6 +1100,8 @@ int jxlhip_decode_filters_rows(jxlhip_ctx* c, void* out, size_t out_stride, size
   if (c->noise_on) return Fail(c, JXLHIP_ERR_UNSUPPORTED, "noise with the split calls (jxlhip_decode_frame takes it)");
   if (c->splines_on)
     return Fail(c, JXLHIP_ERR_UNSUPPORTED, "splines with the split calls (jxlhip_decode_frame takes them)");
+  if (c->patches_on)
+    return Fail(c, JXLHIP_ERR_UNSUPPORTED, "patches with the split calls (jxlhip_decode_frame takes them)");
   if (c->ups_factor > 1)
     return Fail(c, JXLHIP_ERR_UNSUPPORTED, "upsampling with the split calls (jxlhip_decode_frame takes it)");
   int rc = CheckOutArgs(c, out, out_stride, out_plane_stride, c->f.xsize, c->f.y1 - c->f.y0);
@@ -1030,7 +1159,7 @@ int jxlhip_decode_frame(jxlhip_ctx* c, void* out, size_t out_stride, size_t out_
   if (!c) return JXLHIP_ERR_INVALID_ARGUMENT;
   if (c->multi) return out ? MultiDecodeFrame(c, out, nullptr, out_stride, out_plane_stride) : JXLHIP_ERR_INVALID_ARGUMENT;
   if (!c->have_frame) return Fail(c, JXLHIP_ERR_STATE, "decode needs frame_begin + inputs");
-  if (c->noise_on || c->splines_on || c->ups_factor > 1) return DecodeFrameFeatures(c, out, out_stride, out_plane_stride);
+  if (c->noise_on || c->splines_on || c->patches_on || c->ups_factor > 1) return DecodeFrameFeatures(c, out, out_stride, out_plane_stride);
   if (c->p.undo_orientation <= 1) return DecodeFrameCoded(c, out, out_stride, out_plane_stride);
   // undo_orientation: coded orientation into a staging frame, k_orient into the caller's buffer
   const DevFrame& f = c->f;
@@ -1105,6 +1234,8 @@ static int DecodeFrameFeatures(jxlhip_ctx* c, void* out, size_t out_stride, size
   const DevFrame& f = c->f;
   if (f.group_y0 != 0 || f.group_rows != f.ysg || c->p.undo_orientation > 1)
     return Fail(c, JXLHIP_ERR_UNSUPPORTED, "noise / splines / upsampling need a whole frame in coded orientation");
+  if (c->patches_on && c->pat_ref_serial != c->ref_serial)  // (in front of every launch of the frame)
+    return Fail(c, JXLHIP_ERR_STATE, "set_reference_frame after set_patches (the uploaded dictionary points into the slots)");
   HIPCHK(c, hipSetDevice(c->device));
   // the filtered frame at coded size (cns x f.ysize per plane), and the frame the noise launches work on (W x H)
   const uint32_t cns = (f.xsize + 63u) & ~63u;
@@ -1125,6 +1256,24 @@ static int DecodeFrameFeatures(jxlhip_ctx* c, void* out, size_t out_stride, size
   fp.out_stride = out_stride;
   fp.out_plane_stride = out_plane_stride;
   ProfBegin(c);
+  if (c->patches_on) {
+    PatchArgs A{};
+    A.xsize = f.xsize;
+    A.ysize = f.ysize;
+    A.tiles_x = c->pat_tiles_x;
+    A.num_active = c->pat_num_active;
+    A.xyb = coded;
+    A.xyb_out = coded;
+    A.ns = cns;
+    A.nplane = cplane;
+    A.recs = c->pat_recs;
+    A.tile_start = c->pat_tiles;
+    A.tile_idx = c->pat_tiles + c->pat_num_tiles + 1;
+    A.active = c->pat_tiles + c->pat_num_tiles + 1 + c->pat_entries;
+    if (!LaunchPatches(A, fp, (int)kind, /*in_place=*/c->splines_on || c->noise_on || ups, c->stream))
+      return Fail(c, JXLHIP_ERR_INVALID_ARGUMENT, "patches output kind %u", kind);
+    ProfMark(c, JXLHIP_KERNEL_PATCHES);
+  }
   if (c->splines_on) {
     SplineArgs S{};
     S.xsize = f.xsize;
@@ -1303,17 +1452,21 @@ int jxlhip_profile_enable(jxlhip_ctx* c, int enable) {
 
 int jxlhip_profile_read(jxlhip_ctx* c, float ms[JXLHIP_KERNEL_COUNT],
                         uint32_t launches[JXLHIP_KERNEL_COUNT]) {
-  if (!c || !ms || !launches) return JXLHIP_ERR_INVALID_ARGUMENT;
+  return jxlhip_profile_read_ex(c, ms, launches, JXLHIP_KERNEL_COUNT);
+}
+
+int jxlhip_profile_read_ex(jxlhip_ctx* c, float* ms, uint32_t* launches, uint32_t count) {
+  if (!c || !ms || !launches || count > JXLHIP_KERNEL_COUNT_EX) return JXLHIP_ERR_INVALID_ARGUMENT;
   JXLHIP_NO_MULTI(c);
   HIPCHK(c, hipSetDevice(c->device));
   HIPCHK(c, hipStreamSynchronize(c->stream));
-  for (int i = 0; i < JXLHIP_KERNEL_COUNT; i++) {
+  for (int i = 0; i < (int)count; i++) {
     ms[i] = 0;
     launches[i] = 0;
   }
   for (size_t i = 0; i + 1 < c->marks.size(); i++) {
     const int slot = c->marks[i].slot_after;
-    if (slot >= 0 && slot < JXLHIP_KERNEL_COUNT) {
+    if (slot >= 0 && slot < (int)count) {
       float t = 0;
       if (hipEventElapsedTime(&t, c->marks[i].ev, c->marks[i + 1].ev) == hipSuccess) {
         ms[slot] += t;

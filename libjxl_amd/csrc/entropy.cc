@@ -590,6 +590,20 @@ struct EntropyCode {  // ANSCode
 };
 
 constexpr uint32_t kLz77Window = 1u << 20;
+// The special distance codes of 2-D streams (ISO/IEC 18181-1, the LZ77 distance table; the table of WebP lossless):
+// code i stands for the sample (x offset, rows up) away, max(1, x + multiplier * rows).
+constexpr uint32_t kNumSpecialDistances = 120;
+constexpr int8_t kSpecialDistances[kNumSpecialDistances][2] = {
+    {0, 1},  {1, 0},  {1, 1},  {-1, 1}, {0, 2},  {2, 0},  {1, 2},  {-1, 2}, {2, 1},  {-2, 1}, {2, 2},  {-2, 2},
+    {0, 3},  {3, 0},  {1, 3},  {-1, 3}, {3, 1},  {-3, 1}, {2, 3},  {-2, 3}, {3, 2},  {-3, 2}, {0, 4},  {4, 0},
+    {1, 4},  {-1, 4}, {4, 1},  {-4, 1}, {3, 3},  {-3, 3}, {2, 4},  {-2, 4}, {4, 2},  {-4, 2}, {0, 5},  {3, 4},
+    {-3, 4}, {4, 3},  {-4, 3}, {5, 0},  {1, 5},  {-1, 5}, {5, 1},  {-5, 1}, {2, 5},  {-2, 5}, {5, 2},  {-5, 2},
+    {4, 4},  {-4, 4}, {3, 5},  {-3, 5}, {5, 3},  {-5, 3}, {0, 6},  {6, 0},  {1, 6},  {-1, 6}, {6, 1},  {-6, 1},
+    {2, 6},  {-2, 6}, {6, 2},  {-6, 2}, {4, 5},  {-4, 5}, {5, 4},  {-5, 4}, {3, 6},  {-3, 6}, {6, 3},  {-6, 3},
+    {0, 7},  {7, 0},  {1, 7},  {-1, 7}, {5, 5},  {-5, 5}, {7, 1},  {-7, 1}, {4, 6},  {-4, 6}, {6, 4},  {-6, 4},
+    {2, 7},  {-2, 7}, {7, 2},  {-7, 2}, {3, 7},  {-3, 7}, {7, 3},  {-7, 3}, {5, 6},  {-5, 6}, {6, 5},  {-6, 5},
+    {8, 0},  {4, 7},  {-4, 7}, {7, 4},  {-7, 4}, {8, 1},  {8, 2},  {6, 6},  {-6, 6}, {8, 3},  {5, 7},  {-5, 7},
+    {7, 5},  {-7, 5}, {8, 4},  {6, 7},  {-6, 7}, {7, 6},  {-7, 6}, {8, 5},  {7, 7},  {-7, 7}, {8, 6},  {8, 7}};
 
 class SymbolReader {  // ANSSymbolReader
  public:
@@ -602,6 +616,15 @@ class SymbolReader {  // ANSSymbolReader
     if (code->lz77.enabled) window_.reset(new (std::nothrow) uint32_t[kLz77Window]);
   }
   bool Ok() const { return !code_->lz77.enabled || window_; }
+  // A 2-D stream (the channels of a Modular image, multiplier = the widest channel's width; encoding.cc:590-652): the
+  // first 120 distance codes are the special distances (ANSSymbolReader's constructor, dec_ans.cc).  0 = a 1-D stream.
+  void SetDistanceMultiplier(uint32_t multiplier) {
+    num_special_ = multiplier ? kNumSpecialDistances : 0;
+    for (uint32_t i = 0; i < num_special_; i++) {
+      const int64_t d = kSpecialDistances[i][0] + (int64_t)multiplier * kSpecialDistances[i][1];
+      special_[i] = (uint32_t)std::max<int64_t>(d, 1);
+    }
+  }
   bool FinalStateOk() const { return state_ == (kAnsSignature << 16); }
   // The same with the histogram's alias row and hybrid-uint config handed in (plain ANS): a caller that knows the TWO
   // contexts the next symbol can have before this symbol's value is in looks both rows up ahead and only selects
@@ -658,7 +681,8 @@ class SymbolReader {  // ANSSymbolReader
         br->Refill();
         const uint32_t d_token = ReadToken(z.distance_context, br);
         uint32_t distance = FinishHybridUint(code_->configs[z.distance_context], d_token, br);
-        distance += 1;  // no special distances for 1-D streams (distance_multiplier == 0)
+        if (distance < num_special_) distance = special_[distance];
+        else distance = distance + 1 - num_special_;  // (1-D streams, distance_multiplier == 0, have no special distances)
         if (distance > num_decoded_) distance = num_decoded_;
         if (distance > kLz77Window) distance = kLz77Window;
         copy_pos_ = num_decoded_ - distance;
@@ -713,6 +737,7 @@ class SymbolReader {  // ANSSymbolReader
   uint32_t log_entry_ = 0, entry_mask_ = 0;
   std::unique_ptr<uint32_t[]> window_;
   uint32_t num_decoded_ = 0, num_to_copy_ = 0, copy_pos_ = 0;
+  uint32_t num_special_ = 0, special_[kNumSpecialDistances];
   bool corrupt_ = false;
 };
 
@@ -2727,3 +2752,4 @@ int jxlhip_ac_group_decode_sparse(const jxlhip_ac_pass* pass, uint32_t xsb, uint
 }  // extern "C"
 
 #include "splines.inc"
+#include "patches.inc"

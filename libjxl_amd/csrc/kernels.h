@@ -168,6 +168,35 @@ struct SplineArgs {
 // active tiles back into S.xyb_out (planar XYB, for the noise launches).  False for a bad output kind.
 bool LaunchSplines(const SplineArgs& S, const FilterParams& p, int output_kind, bool in_place, hipStream_t st);
 
+// Patches (kernels_patches.hip).  The frame is cut into 64 x 16 tiles; tile t blends the records
+// recs[tile_idx[tile_start[t] .. tile_start[t + 1])] in that (increasing) order -- the order of the dictionary, which
+// GetPatchesForRow restores for every row (dec_patch_dictionary.cc:309-312).
+enum : uint32_t { kPatchOpReplace = 0, kPatchOpAdd = 1, kPatchOpMul = 2, kPatchOpMulClamp = 3 };
+struct PatchRec {          // one placement, 40 bytes
+  int32_t x0, y0, x1, y1;  // its rectangle in the frame, [x0, x1) x [y0, y1), clipped to the frame
+  const float* src;        // the reference sample that goes to (x0, y0): plane X of its slot
+  uint32_t stride, plane;  // of the slot: floats per row, floats between planes
+  uint32_t op;             // kPatchOp*: what PerformBlending's colour mode comes to without an alpha channel
+  uint32_t pad;
+};
+struct PatchArgs {
+  uint32_t xsize, ysize, tiles_x;
+  uint32_t num_active;     // tiles with records (blend-in-place covers only these)
+  const float* xyb;        // the filtered frame: 3 planes, ns floats per row, nplane floats apart
+  float* xyb_out;          // blend-in-place: where the planes go (same layout; may be xyb)
+  uint32_t ns;
+  size_t nplane;
+  const PatchRec* recs;
+  const uint32_t* tile_start;  // tiles + 1 entries
+  const uint32_t* tile_idx;
+  const uint32_t* active;      // num_active tile indices
+};
+// records one LDS batch of k_patches holds (a tile with more is blended in several batches)
+constexpr uint32_t kPatchBatch = 128;
+// k_patches: in_place = false: blend every tile and write the output tail of `output_kind` into p.out; true: blend the
+// active tiles back into A.xyb_out (planar XYB, for the launches that follow).  False for a bad output kind.
+bool LaunchPatches(const PatchArgs& A, const FilterParams& p, int output_kind, bool in_place, hipStream_t st);
+
 // Upsampling (kernels_upsample.hip).  The coded frame is cut into 64 x 16 tiles; every coded pixel gives n x n output
 // pixels, each a 25-tap sum over its 5 x 5 neighbourhood clamped to the neighbourhood's range.
 struct UpsampleArgs {

@@ -1092,7 +1092,10 @@ struct PendingTransforms {  // of the frame's global image, until every group is
 // group is in (FinalizeDecoding, dec_modular.cc:739-760).
 int ModularDecodeImage(BitReader* br, std::vector<ModularChannel>& image, uint32_t stream_id,
                        const jxlhip_modular_tree* global, uint32_t max_chan_size, uint32_t image_bits,
-                       PendingTransforms* pending = nullptr, const std::function<int(uint32_t)>* after_channel = nullptr) {
+                       PendingTransforms* pending = nullptr, const std::function<int(uint32_t)>* after_channel = nullptr,
+                       bool allow_lz77 = false, const char** why = nullptr) {
+  // allow_lz77: an entropy code with LZ77 is read with the 2-D special distances (jxlhip_modular_frame_decode; the
+  // other callers keep refusing it).  why: where JXLHIP_ERR_UNSUPPORTED came from, as a static string.
   // after_channel(c): channel c's samples are final -- called between the channels of a stream WITHOUT transforms only
   // (with a palette or a squeeze nothing is final before the end); a non-zero return stops the decode with that status
   if (image.empty()) return kOk;  // not even a group header (encoding.cc:558)
@@ -1101,6 +1104,7 @@ int ModularDecodeImage(BitReader* br, std::vector<ModularChannel>& image, uint32
   std::vector<ModularPalette> palettes;
   ModularSqueeze squeeze;
   int rc = ReadModularGroupHeader(br, &use_global_tree, &wp, &palettes, pending ? &squeeze : nullptr);
+  if (rc == JXLHIP_ERR_UNSUPPORTED && why) *why = "a transform of the Modular frame (RCT, squeeze, delta palette)";
   if (rc) return rc;
   // MetaPalette with begin_c == end_c (palette.cc:171-200): the palette becomes channel 0 (nb_colors x 1, shifts -1),
   // the channel itself now holds indices
@@ -1144,24 +1148,32 @@ int ModularDecodeImage(BitReader* br, std::vector<ModularChannel>& image, uint32
   };
   uint64_t pixels = 0;
   size_t num_chans = 0;
+  uint32_t distance_multiplier = 0;  // the widest channel this stream holds (encoding.cc:590-604)
   for (uint32_t i = 0; i < image.size(); i++) {
     if (stops(i)) break;
     const ModularChannel& c = image[i];
-    if (c.w && c.h) num_chans++;
+    if (c.w && c.h) {
+      num_chans++;
+      distance_multiplier = std::max(distance_multiplier, c.w);
+    }
     pixels += (uint64_t)c.w * c.h;
   }
   if (num_chans == 0) return undo();
   jxlhip_modular_tree local;
   const jxlhip_modular_tree* tree = global;
   if (!use_global_tree) {
-    if ((rc = DecodeMaTree(br, (size_t)std::min<uint64_t>(1u << 20, 1024 + pixels), &local))) return rc;
+    if ((rc = DecodeMaTree(br, (size_t)std::min<uint64_t>(1u << 20, 1024 + pixels), &local))) {
+      if (rc == JXLHIP_ERR_UNSUPPORTED && why) *why = "the MA tree of the Modular frame";
+      return rc;
+    }
     tree = &local;
   } else if (!global || global->nodes.empty()) {
     return kBad;
   }
-  if (tree->code.lz77.enabled) return JXLHIP_ERR_UNSUPPORTED;  // 2-D special distances
+  if (tree->code.lz77.enabled && !allow_lz77) return JXLHIP_ERR_UNSUPPORTED;  // 2-D special distances
   SymbolReader reader(&tree->code, br);
   if (!reader.Ok()) return JXLHIP_ERR_OUT_OF_MEMORY;
+  reader.SetDistanceMultiplier(distance_multiplier);
   for (uint32_t c = 0; c < image.size(); c++) {
     if (stops(c)) break;
     if ((rc = DecodeModularChannel(br, &reader, *tree, wp, image, c, stream_id))) return rc;
@@ -1677,4 +1689,83 @@ int jxlhip_dc_group_decode_staged(const jxlhip_modular_tree* global, const uint8
   if (!br.Healthy()) return kBad;
   *bit_pos = br.BitsConsumed();
   return kOk;
+}
+
+// ---- a Modular-coded frame of one group: the reference frame of a patch dictionary ------------------------------
+// FrameDecoder::ProcessDCGlobal of a Modular frame (dec_frame.cc:268-302: DequantMatrices::DecodeDC only),
+// ModularFrameDecoder::DecodeGlobalInfo with the colour channels (dec_modular.cc:209-318) and
+// ModularImageToDecodedRect for XYB (dec_modular.cc:564-632 with MultiplySum, :61-73).  A frame of one group has all
+// its samples in the global stream: its DC-group, AC-global and AC-group parts read nothing (dec_modular.cc:344-350).
+static int ModularFrameDecodeImpl(const uint8_t* data, size_t size, size_t* bit_pos, const jxlhip_frame_header* fh,
+                                  float* const planes[3], size_t stride_floats, const char** why) {
+  auto refuse = [&](const char* what) {
+    if (why) *why = what;
+    return JXLHIP_ERR_UNSUPPORTED;
+  };
+  if (why) *why = "";
+  if (!data || !bit_pos || !fh || !planes || !planes[0] || !planes[1] || !planes[2] || !fh->is_modular || fh->xsize == 0 ||
+      fh->ysize == 0 || stride_floats < fh->xsize)
+    return JXLHIP_ERR_INVALID_ARGUMENT;
+  if (fh->color_transform != JXLHIP_CT_XYB) return refuse("a Modular frame that is not XYB");
+  if (fh->num_groups != 1 || fh->xsize > fh->group_dim || fh->ysize > fh->group_dim)
+    return refuse("a Modular frame of more than one group");
+  if (fh->flags != 0) return refuse("a Modular frame with flags (noise, patches, splines, a DC frame)");
+  if (fh->lf.gab || fh->lf.epf_iters) return refuse("a Modular frame with a loop filter");
+  if (fh->upsampling != 1) return refuse("an upsampled Modular frame");
+  if (fh->num_passes != 1) return refuse("a Modular frame of more than one pass");
+  if (fh->dc_level != 0) return refuse("a Modular DC frame");
+  if (!fh->save_before_color_transform) return refuse("a Modular frame saved behind the colour transform");
+  if (fh->num_extra_channels != 0) return refuse("a Modular frame of an image with extra channels");
+  BitReader br(data, size, *bit_pos);
+  float dc_quant[3] = {1.0f / 4096.0f, 1.0f / 512.0f, 1.0f / 256.0f};  // DequantMatrices::DecodeDC
+  if (!br.Read(1)) {
+    for (float& q : dc_quant) {
+      float v;
+      if (!ReadF16(&br, &v)) return kBad;
+      v *= 1.0f / 128.0f;
+      if (v < 1e-8f) return kBad;
+      q = v;
+    }
+  }
+  if (!br.Healthy()) return kBad;
+  jxlhip_modular_tree tree;
+  if (br.Read(1)) {  // has_tree
+    const uint64_t limit = std::min<uint64_t>(1u << 22, 1024 + (uint64_t)fh->xsize * fh->ysize * 3 / 16);
+    const int rc = DecodeMaTree(&br, (size_t)limit, &tree);
+    if (rc == JXLHIP_ERR_UNSUPPORTED) return refuse("the MA tree of the Modular frame");
+    if (rc) return rc;
+  }
+  std::vector<ModularChannel> image(3);
+  for (ModularChannel& c : image) c.Resize(fh->xsize, fh->ysize);
+  const char* where = "a Modular feature outside this front-end";
+  const int rc = ModularDecodeImage(&br, image, 0, &tree, fh->group_dim, fh->image_bits, nullptr, nullptr, /*allow_lz77=*/true,
+                                    &where);
+  if (rc == JXLHIP_ERR_UNSUPPORTED) return refuse(where);
+  if (rc) return rc;
+  if (!br.Healthy() || image.size() != 3) return kBad;
+  for (const ModularChannel& c : image)
+    if (c.w != fh->xsize || c.h != fh->ysize) return kBad;
+  // coded as Y, X, B - Y
+  for (uint32_t y = 0; y < fh->ysize; y++) {
+    const int32_t *r0 = image[0].Row(y), *r1 = image[1].Row(y), *r2 = image[2].Row(y);
+    float* ox = planes[0] + (size_t)y * stride_floats;
+    float* oy = planes[1] + (size_t)y * stride_floats;
+    float* ob = planes[2] + (size_t)y * stride_floats;
+    for (uint32_t x = 0; x < fh->xsize; x++) {
+      ox[x] = (float)r1[x] * dc_quant[0];
+      oy[x] = (float)r0[x] * dc_quant[1];
+      ob[x] = (float)(int32_t)((uint32_t)r2[x] + (uint32_t)r0[x]) * dc_quant[2];  // MultiplySum: the sum in int32
+    }
+  }
+  *bit_pos = br.BitsConsumed();
+  return kOk;
+}
+
+int jxlhip_modular_frame_decode(const uint8_t* data, size_t size, size_t* bit_pos, const jxlhip_frame_header* fh,
+                                float* const planes[3], size_t stride_floats, const char** why) {
+  try {
+    return ModularFrameDecodeImpl(data, size, bit_pos, fh, planes, stride_floats, why);
+  } catch (const std::bad_alloc&) {
+    return JXLHIP_ERR_OUT_OF_MEMORY;
+  }
 }

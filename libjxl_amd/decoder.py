@@ -36,6 +36,7 @@ class VarDctDecoder:
         self._keep = None
         self.out = None
         self.out_size = None
+        self._ref_sizes = {}  # set_reference_frame: slot -> (xsize, ysize)
 
     def close(self):
         if self.ctx:
@@ -154,6 +155,45 @@ class VarDctDecoder:
         finally:
             abi.splines_destroy(h, self.L)
 
+    def set_reference_frame(self, slot, planes):
+        """A reference frame for patches, jxlhip_set_reference_frame: planes = float32 XYB of shape [3, ysize, xsize]
+        (a host array, or a CUDA tensor of this device) into slot 0..3 of the context; None clears the slot.  The slots
+        outlive frames."""
+        import numpy as np
+        if planes is None:
+            _check(self.L, self.ctx, self.L.jxlhip_set_reference_frame(self.ctx, int(slot), 0, 0, (C.c_void_p * 3)(), 0, 0),
+                   "set_reference_frame")
+            self._ref_sizes.pop(int(slot), None)
+            return
+        on_device = isinstance(planes, torch.Tensor) and planes.is_cuda
+        if on_device:
+            a = planes.to(torch.float32).contiguous()
+            base, esz = a.data_ptr(), 4
+        else:
+            a = np.ascontiguousarray(planes, dtype=np.float32)
+            base, esz = a.ctypes.data, 4
+        assert a.ndim == 3 and a.shape[0] == 3, tuple(a.shape)
+        h, w = int(a.shape[1]), int(a.shape[2])
+        ptrs = (C.c_void_p * 3)(*[base + k * h * w * esz for k in range(3)])
+        _check(self.L, self.ctx, self.L.jxlhip_set_reference_frame(self.ctx, int(slot), w, h, ptrs, w, int(on_device)),
+               "set_reference_frame")  # (synchronous: `a` may go away)
+        self._ref_sizes[int(slot)] = (w, h)
+
+    def set_patches(self, patches):
+        """Patches of the current frame (FrameHeader::kPatches), jxlhip_set_patches: a jxlhip_patches* handle
+        (abi.patches_from_list, abi.patches_decode) or a list of patch dicts in the form abi.patches_from_list takes,
+        checked against the slots set_reference_frame has filled; None = no patches.  begin_frame resets to no patches."""
+        if patches is None or isinstance(patches, (int, C.c_void_p)):
+            _check(self.L, self.ctx, self.L.jxlhip_set_patches(self.ctx, patches), "set_patches")
+            return
+        p = self.params
+        rc, h = abi.patches_from_list(patches, (p.xsize + 7) & ~7, (p.ysize + 7) & ~7, self._ref_sizes, L=self.L)
+        _check(self.L, self.ctx, rc, "patches_from_list")
+        try:
+            _check(self.L, self.ctx, self.L.jxlhip_set_patches(self.ctx, h), "set_patches")
+        finally:
+            abi.patches_destroy(h, self.L)
+
     def set_upsampling(self, factor, out_size, weights=None):
         """Upsampling of the current frame (FrameHeader::upsampling: 2, 4 or 8), jxlhip_set_upsampling: begin_frame's
         size is the coded size, out_size = (xsize, ysize) the image the frame is upsampled and cropped to; weights =
@@ -267,10 +307,10 @@ class VarDctDecoder:
         _check(self.L, self.ctx, self.L.jxlhip_profile_enable(self.ctx, int(enable)), "profile_enable")
 
     def profile_read(self):
-        ms = (C.c_float * abi.KERNEL_COUNT)()
-        n = (C.c_uint32 * abi.KERNEL_COUNT)()
-        _check(self.L, self.ctx, self.L.jxlhip_profile_read(self.ctx, ms, n), "profile_read")
-        return {abi.KERNEL_NAMES[i]: (ms[i], n[i]) for i in range(abi.KERNEL_COUNT) if n[i]}
+        ms = (C.c_float * abi.KERNEL_COUNT_EX)()
+        n = (C.c_uint32 * abi.KERNEL_COUNT_EX)()
+        _check(self.L, self.ctx, self.L.jxlhip_profile_read_ex(self.ctx, ms, n, abi.KERNEL_COUNT_EX), "profile_read")
+        return {abi.KERNEL_NAMES_EX[i]: (ms[i], n[i]) for i in range(abi.KERNEL_COUNT_EX) if n[i]}
 
 
 class _CudaArray:

@@ -9,8 +9,9 @@ extensions (tools/djxl_main.cc, lib/extras/enc/pnm.cc):
   .ppm  8-bit RGB               .pam  8-bit RGBA (the image's alpha channel, opaque without one)
         -- both in the image's original colour encoding (its transfer function over its primaries; an ICC
            original: linear sRGB, like djxl without a CMS)
-Photon noise (kNoise frames) and splines (kSplines) are rendered on the device.  Streams outside the back-end (Modular
-frames, patches, animation ...) exit with status 3 and the error text so that a
+Photon noise (kNoise frames), splines (kSplines) and patches (kPatches behind their kReferenceOnly frames: what cjxl
+writes for screenshots and text) are rendered on the device.  Streams outside the back-end (Modular frames, animation
+...) exit with status 3 and the error text so that a
 wrapper can fall back to libjxl's djxl.  Prints Mpx/s of the decode call like djxl's SpeedStats."""
 import argparse
 import ctypes as C
