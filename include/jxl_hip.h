@@ -344,6 +344,59 @@ JXLHIP_EXPORT int jxlhip_set_patches(jxlhip_ctx* ctx, const struct jxlhip_patche
  * upsampled frames are outside the back-end); the split calls refuse an upsampled frame. */
 JXLHIP_EXPORT int jxlhip_set_upsampling(jxlhip_ctx* ctx, uint32_t factor, const float* weights, uint32_t out_xsize,
                                         uint32_t out_ysize);
+/* ---- blending: frame sequences (animations, layers, cropped frames) ----
+ * The four slots of jxlhip_set_reference_frame hold one of two things each: the XYB reference frame patches copy from
+ * (a frame saved BEFORE the colour transform), or a CANVAS: a frame saved AFTER the colour transform, as float RGB in
+ * the output's transfer function at image size (ReferenceFrame::ib_is_in_xyb = false, dec_frame.cc:879).  Storing one
+ * kind drops the other; jxlhip_set_reference_frame(slot, 0, 0, ...) clears both; jxlhip_set_patches refuses a patch
+ * whose slot holds a canvas ("Patches cannot use frames saved post color transforms", dec_patch_dictionary.cc:70).
+ * Canvas memory is the context's and grows as needed.
+ *
+ * jxlhip_set_blending: the current frame is blended over the canvas of slot `source` at its origin and / or saved
+ * (FrameHeader::blending_info, frame_origin, save_as_reference; BlendingStage, render_pipeline/stage_blending.cc).
+ * Call it after jxlhip_frame_begin, which resets it; NULL switches it off.  The frame that is blended is the frame's
+ * own output (an upsampled frame at its upsampled size), after every render stage it has (patches, splines,
+ * upsampling, noise).  With blending on, jxlhip_decode_frame / _host / _pinned take and check `out` and its stride as
+ * an image_xsize x image_ysize frame; `out` may be NULL when a save slot is named (a layer nobody displays).  Per
+ * canvas pixel: bg = the source canvas (0 when the slot is empty); inside the frame's rectangle clipped to the image
+ * the result is PerformBlending's colour mode on an image without an alpha channel (blending.cc:150-184): kReplace and
+ * kBlend fg, kAdd and kAlphaWeightedAdd bg + fg, kMul bg * fg with fg clamped to [0, 1] when `clamp` is set; outside
+ * it the result is bg.  It goes to the save slot and, through the sample conversion of the output format (dither,
+ * clamp, rounding, half floats, byte swap, opaque alpha), to `out`.
+ * The reference blends after FromLinearStage, in the ORIGINAL's encoding; this call blends in the transfer function
+ * of the caller's output format (JXLHIP_OUT_LINEAR_RGB_F32: linear).  The two agree when the caller asks for the
+ * original's transfer function (jxlhip_codestream_info::transfer_function); otherwise the blend is done in another
+ * encoding than the reference's.  All frames of a sequence must use the same output transfer function.
+ * A full-size kReplace frame at the origin with no save slot launches exactly what it does without this call.
+ * JXLHIP_ERR_UNSUPPORTED: multi-device contexts, stripes, undo_orientation > 1, JXLHIP_OUT_XYB_PLANAR, a stream that is
+ * being captured into a graph (canvas and staging memory may have to grow), a frame with
+ * jxlhip_set_alpha (blending and saving extra channels is not in the back-end; jxlhip_set_alpha refuses a blended
+ * frame in turn), and the split calls on a blended frame.  JXLHIP_ERR_INVALID_ARGUMENT: a bad mode or slot, a source
+ * slot that holds an XYB frame ("Trying to blend XYB reference frame"), a source canvas smaller than the image (neither
+ * is looked at for a full-size kReplace frame at the origin, which never reads its source), and
+ * save_slot == source with a source canvas of another size than the image. */
+typedef enum jxlhip_blend_mode {  /* BlendMode, frame_header.h */
+  JXLHIP_BLEND_REPLACE = 0,
+  JXLHIP_BLEND_ADD = 1,
+  JXLHIP_BLEND_BLEND = 2,
+  JXLHIP_BLEND_ALPHA_WEIGHTED_ADD = 3,
+  JXLHIP_BLEND_MUL = 4
+} jxlhip_blend_mode;
+#define JXLHIP_BLEND_NO_SAVE 0xFFFFFFFFu
+typedef struct jxlhip_blend_params {
+  uint32_t image_xsize, image_ysize; /* the canvas: W x H */
+  int32_t x0, y0;                    /* FrameHeader::frame_origin */
+  uint32_t mode;                     /* jxlhip_blend_mode */
+  uint32_t clamp;                    /* BlendingInfo::clamp */
+  uint32_t source;                   /* BlendingInfo::source: slot 0..3 */
+  uint32_t save_slot;                /* slot 0..3 the blended frame is saved into, or JXLHIP_BLEND_NO_SAVE */
+} jxlhip_blend_params;
+JXLHIP_EXPORT int jxlhip_set_blending(jxlhip_ctx* ctx, const jxlhip_blend_params* params);
+/* Reads the canvas of `slot`: device-to-device into dev_out as interleaved float RGB, stride_floats per row
+ * (>= 3 * width), enqueued on the context's stream.  dev_out == NULL only reports the size.  *w = *h = 0 and nothing
+ * written when the slot holds no canvas. */
+JXLHIP_EXPORT int jxlhip_canvas_read(jxlhip_ctx* ctx, uint32_t slot, float* dev_out, size_t stride_floats, uint32_t* w,
+                                     uint32_t* h);
 /* Host-side check of the noise generator's jump: the state (s0_[i], s1_[i]) of the 8 lanes of
  * Xorshift128Plus(visible_frame_index, nonvisible_frame_index, x0, y0) (lib/jxl/xorshift128plus-inl.h:46-57) after
  * `fills` calls of Fill, computed as the kernel does (one jump-matrix product, then single steps) into state[2 * i],
@@ -476,7 +529,8 @@ enum {
   /* WARNING: the slots from here on equal or exceed JXLHIP_KERNEL_COUNT -- never index an array of
    * JXLHIP_KERNEL_COUNT with them; size arrays with JXLHIP_KERNEL_COUNT_EX and read with jxlhip_profile_read_ex */
   JXLHIP_KERNEL_PATCHES = 8,  /* patches (jxlhip_set_patches): k_patches behind the frame's path, in front of the splines */
-  JXLHIP_KERNEL_COUNT_EX = 9  /* every slot; grows with each new one (new slots are appended here only) */
+  JXLHIP_KERNEL_BLEND = 9,    /* blending (jxlhip_set_blending): k_blend behind the frame's whole path */
+  JXLHIP_KERNEL_COUNT_EX = 10 /* every slot; grows with each new one (new slots are appended here only) */
 };
 /* A hint, not a contract: `frames_in_flight` = how many contexts the caller keeps busy on this device at the same time
  * (a pool of decoders over a queue of images; 1 = this context runs alone, the default).  It only moves the frame size

@@ -25,8 +25,12 @@
  * one regular last frame whose flags may include kPatches (jxlhip_patches_decode, blended on the device,
  * jxlhip_set_patches), of images without extra channels.  The four reference slots of the context are cleared at the
  * start of every call; the info struct describes the visible frame.
+ * Animations, layers, cropped and blended frames go through jxlhip_codestream_sequence_info /
+ * jxlhip_decode_codestream_next below (blended on the device, jxlhip_set_blending); the single-frame calls refuse them.
  * Everything this front-end does not decode is refused with JXLHIP_ERR_UNSUPPORTED so that the caller can hand the
- * file to libjxl's CPU decoder: Modular-mode frames, animation / layers / any other sequence of frames, previews,
+ * file to libjxl's CPU decoder: Modular-mode frames, animation / layers / any other sequence of frames (single-frame
+ * calls; the sequence calls refuse frames that need blending on images with extra channels, VarDCT
+ * reference-only frames, regular frames saved before the colour transform and kSkipProgressive), previews,
  * reference frames of more than one group or with an RCT, squeeze or delta palette, patches on images with extra channels,
  * a last frame that blends (blend_mode other than kReplace) behind a reference frame,
  * chroma subsampling and YCbCr (JPEG recompression), upsampled frames of images with extra channels (alpha included:
@@ -144,6 +148,65 @@ enum {
   JXLHIP_CODESTREAM_PHASES = 7
 };
 JXLHIP_EXPORT int jxlhip_codestream_phase_ms(const jxlhip_ctx* ctx, double* ms);
+
+/* ---- sequences of frames: animations, layers, cropped and blended frames --------------------------------------------
+ * jxlhip_codestream_basic_info and jxlhip_decode_codestream[_extra] above keep refusing every file with more than one
+ * visible frame.  The two calls below take them: they walk every frame of the file up front (header, TOC, skip the
+ * sections) and decode them in order, blending on the device (jxlhip_set_blending): the canvas stays in the context's
+ * slots between calls and makes no host round trip.
+ * A DISPLAYED frame is what the reference's coalescing decoder reports (decode.cc:1346-1356): a regular frame with
+ * is_last or duration > 0, blended over whatever its zero-duration layers and earlier frames left in its source slot.
+ * Refused up front with JXLHIP_ERR_UNSUPPORTED and a named reason (jxlhip_last_error of the decode call): previews,
+ * Modular regular frames, VarDCT kReferenceOnly frames, DC frames and kUseDcFrame, kSkipProgressive, regular frames
+ * saved before the colour transform; on an image with extra channels a frame that NeedsBlending (blending.cc:23-40: a
+ * crop, or a blend mode other than kReplace on the colour or on any extra channel) and a frame with patches -- the only
+ * readers of a saved frame, so nothing is ever saved there (blending and saving extra channels, kBlend with real alpha
+ * included, is not in the back-end; full-frame kReplace sequences with alpha are taken); and everything the
+ * single-frame calls refuse per frame. */
+typedef struct jxlhip_sequence_info {
+  uint32_t have_animation, tps_numerator, tps_denominator, num_loops, have_timecodes; /* AnimationHeader */
+  uint32_t num_coded_frames;     /* every frame of the file, reference-only frames and layers included */
+  uint32_t num_displayed_frames; /* calls of jxlhip_decode_codestream_next until is_last */
+  const char* why;               /* a static string: which case, when the call returns JXLHIP_ERR_UNSUPPORTED; else "" */
+} jxlhip_sequence_info;
+
+/* Headers only (no device needed): fills *info like jxlhip_codestream_basic_info (upsampling: the first displayed
+ * frame's) and *seq.  JXLHIP_ERR_BAD_STREAM for a file that ends inside the walk (a frame's sections included);
+ * JXLHIP_ERR_UNSUPPORTED with seq->why naming the case (the other fields of *seq are then 0). */
+JXLHIP_EXPORT int jxlhip_codestream_sequence_info(const uint8_t* data, size_t size, jxlhip_codestream_info* info,
+                                                  jxlhip_sequence_info* seq);
+
+typedef struct jxlhip_sequence_frame {
+  uint32_t index;               /* of the displayed frame, from 0 */
+  uint32_t duration, timecode;  /* AnimationFrame (ticks of tps_numerator / tps_denominator per second) */
+  uint32_t is_last;
+  uint32_t name_length;
+  /* the displayed frame's own rectangle and blending (FrameHeader): the whole image when not cropped */
+  uint32_t have_crop;
+  int32_t x0, y0;
+  uint32_t xsize, ysize;
+  uint32_t blend_mode, blend_source, blend_clamp, save_as_reference;
+  uint32_t coded_frames;        /* coded frames this call decoded (reference-only frames and layers included) */
+} jxlhip_sequence_frame;
+
+/* The next displayed frame of a file.  *cursor == 0 starts a sequence: the four slots of the context are cleared.
+ * Each call decodes the coded frames from the cursor up to and including the next displayed frame -- reference-only
+ * Modular frames into their slots (as jxlhip_decode_codestream), zero-duration layers blended into theirs -- writes the
+ * displayed frame at IMAGE size into `out` (arguments as jxlhip_decode_codestream; blended frames refuse
+ * JXLHIP_OUT_UNDO_ORIENTATION with orientations above 1 and JXLHIP_OUT_XYB_PLANAR), fills *frame and advances *cursor.
+ * The context remembers the cursor it expects: any other non-zero value, and a call after the frame with is_last, is
+ * JXLHIP_ERR_STATE.  Pass the same bytes to every call of a sequence.
+ * A frame is saved only when a later frame of the file reads its slot before the slot is overwritten (it blends with
+ * that source, or carries a patch dictionary): cjxl gives every frame of an animation save_as_reference = 1 whether it
+ * is used or not, and a plain full-frame animation takes exactly the single-frame path per frame.
+ * Blending happens in the transfer function of out_format (jxlhip_set_blending): it matches the reference when that is
+ * the original's (info->transfer_function).  Noise frames get the reference's seed counters (dec_frame.cc:160-168) as
+ * the walk has counted them.  jxlhip_codestream_phase_ms covers the last call. */
+JXLHIP_EXPORT int jxlhip_decode_codestream_next(jxlhip_ctx* ctx, jxlhip_parallel_runner runner, void* runner_opaque,
+                                                const uint8_t* data, size_t size, uint64_t* cursor, uint32_t output_kind,
+                                                const jxlhip_output_format* out_format, void* out, size_t out_stride,
+                                                size_t out_plane_stride, jxlhip_codestream_info* info,
+                                                jxlhip_sequence_frame* frame);
 
 #ifdef __cplusplus
 }

@@ -194,6 +194,11 @@ typedef struct jxlhip_frame_header {
   uint32_t image_bits;         /* jxlhip_image_info::bits_per_sample (the Modular Image's bitdepth: the implicit entries
                                   of multi-channel palettes scale with it, palette.h:53-122); 0 = not given: such a
                                   palette is then JXLHIP_ERR_UNSUPPORTED */
+  /* FrameHeader::extra_channel_blending_info of the first four extra channels of a regular frame (BlendingInfo, as
+     blend_* above for the colour channels), and whether ANY extra channel's mode is not kReplace: with blend_mode and
+     custom_size_or_origin, what NeedsBlending reads (blending.cc:23-40) */
+  uint32_t ec_blend_mode[4], ec_blend_alpha_channel[4], ec_blend_clamp[4], ec_blend_source[4];
+  uint32_t ec_blend_any;
 } jxlhip_frame_header;
 
 /* ReadFrameHeader (frame_header.cc:212-215): reads the header at bit *bit_pos of data (advanced to

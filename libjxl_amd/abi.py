@@ -9,9 +9,12 @@ _RUNNER_SO = os.path.join(_HERE, "csrc", "libjxl_threads_hip.so")
 
 KERNEL_COUNT = 8
 KERNEL_NAMES = ["prepare", "blocks", "filters", "fused", "epf0", "noise", "splines", "upsample"]
-# jxlhip_profile_read_ex: the slots above, then those added since (JXLHIP_KERNEL_PATCHES = 8)
-KERNEL_COUNT_EX = 9
-KERNEL_NAMES_EX = KERNEL_NAMES + ["patches"]
+# jxlhip_profile_read_ex: the slots above, then those added since (JXLHIP_KERNEL_PATCHES = 8, JXLHIP_KERNEL_BLEND = 9)
+KERNEL_COUNT_EX = 10
+KERNEL_NAMES_EX = KERNEL_NAMES + ["patches", "blend"]
+# BlendMode (JXLHIP_BLEND_*) and jxlhip_blend_params::save_slot's "none"
+BLEND_REPLACE, BLEND_ADD, BLEND_BLEND, BLEND_ALPHA_WEIGHTED_ADD, BLEND_MUL = range(5)
+BLEND_NO_SAVE = 0xFFFFFFFF
 # PatchBlendMode (JXLHIP_PATCH_*)
 PATCH_NONE, PATCH_REPLACE, PATCH_ADD, PATCH_MUL, PATCH_BLEND_ABOVE, PATCH_BLEND_BELOW, PATCH_ALPHA_WEIGHTED_ADD_ABOVE, \
     PATCH_ALPHA_WEIGHTED_ADD_BELOW = range(8)
@@ -146,7 +149,9 @@ class FrameHeader(C.Structure):
                 ("group_dim", C.c_uint32), ("xsize_groups", C.c_uint32), ("ysize_groups", C.c_uint32),
                 ("num_groups", C.c_uint64), ("num_dc_groups", C.c_uint64), ("num_toc_entries", C.c_uint64),
                 ("x_dm_multiplier", C.c_float), ("b_dm_multiplier", C.c_float),
-                ("num_extra_channels", C.c_uint32), ("ec_upsampling", C.c_uint32 * 4), ("image_bits", C.c_uint32)]
+                ("num_extra_channels", C.c_uint32), ("ec_upsampling", C.c_uint32 * 4), ("image_bits", C.c_uint32),
+                ("ec_blend_mode", C.c_uint32 * 4), ("ec_blend_alpha_channel", C.c_uint32 * 4), ("ec_blend_clamp", C.c_uint32 * 4),
+                ("ec_blend_source", C.c_uint32 * 4), ("ec_blend_any", C.c_uint32)]
 
 
 class CodestreamInfo(C.Structure):
@@ -159,6 +164,20 @@ class CodestreamInfo(C.Structure):
                 ("num_extra_channels", C.c_uint32), ("alpha_bits", C.c_uint32), ("alpha_premultiplied", C.c_uint32),
                 ("luminances", C.c_float * 3), ("gamma", C.c_float), ("icc_size", C.c_uint32), ("grey", C.c_uint32),
                 ("upsampling", C.c_uint32)]
+
+
+class SequenceInfo(C.Structure):
+    """jxlhip_sequence_info"""
+    _fields_ = [(n, C.c_uint32) for n in ("have_animation", "tps_numerator", "tps_denominator", "num_loops", "have_timecodes",
+                                          "num_coded_frames", "num_displayed_frames")] + [("why", C.c_char_p)]
+
+
+class SequenceFrame(C.Structure):
+    """jxlhip_sequence_frame"""
+    _fields_ = [("index", C.c_uint32), ("duration", C.c_uint32), ("timecode", C.c_uint32), ("is_last", C.c_uint32),
+                ("name_length", C.c_uint32), ("have_crop", C.c_uint32), ("x0", C.c_int32), ("y0", C.c_int32),
+                ("xsize", C.c_uint32), ("ysize", C.c_uint32), ("blend_mode", C.c_uint32), ("blend_source", C.c_uint32),
+                ("blend_clamp", C.c_uint32), ("save_as_reference", C.c_uint32), ("coded_frames", C.c_uint32)]
 
 
 class FrameParams(C.Structure):
@@ -176,6 +195,12 @@ class FrameParams(C.Structure):
                 ("stripe_group_rows", C.c_uint32),
                 ("out_format", OutputFormat),
                 ("used_acs", C.c_uint32), ("undo_orientation", C.c_uint32)]
+
+
+class BlendParams(C.Structure):
+    """jxlhip_blend_params"""
+    _fields_ = [("image_xsize", C.c_uint32), ("image_ysize", C.c_uint32), ("x0", C.c_int32), ("y0", C.c_int32),
+                ("mode", C.c_uint32), ("clamp", C.c_uint32), ("source", C.c_uint32), ("save_slot", C.c_uint32)]
 
 
 class FrameInputs(C.Structure):
@@ -238,7 +263,7 @@ EXPORTS = [
     "jxlhip_dequant_table_offset", "jxlhip_status_string", "jxlhip_create", "jxlhip_create_ex", "jxlhip_create_multi",
     "jxlhip_destroy", "jxlhip_last_error", "jxlhip_debug_reload_env", "jxlhip_set_stream",
     "jxlhip_frame_begin", "jxlhip_frame_set_inputs", "jxlhip_upload_side_info",
-    "jxlhip_submit_group", "jxlhip_set_alpha", "jxlhip_set_noise", "jxlhip_noise_rng_state", "jxlhip_set_splines", "jxlhip_set_upsampling", "jxlhip_set_reference_frame", "jxlhip_set_patches", "jxlhip_profile_read_ex", "jxlhip_alpha_staging", "jxlhip_decode_blocks", "jxlhip_halo_rows",
+    "jxlhip_submit_group", "jxlhip_set_alpha", "jxlhip_set_noise", "jxlhip_noise_rng_state", "jxlhip_set_splines", "jxlhip_set_upsampling", "jxlhip_set_reference_frame", "jxlhip_set_patches", "jxlhip_set_blending", "jxlhip_canvas_read", "jxlhip_profile_read_ex", "jxlhip_alpha_staging", "jxlhip_decode_blocks", "jxlhip_halo_rows",
     "jxlhip_halo_export", "jxlhip_halo_import", "jxlhip_decode_filters", "jxlhip_decode_filters_rows", "jxlhip_stripe_begin",
     "jxlhip_stripe_finish", "jxlhip_decode_frame",
     "jxlhip_decode_frame_host", "jxlhip_decode_frame_pinned",
@@ -261,7 +286,8 @@ EXPORTS = [
     "jxlhip_modular_extra_channel_rows_f32", "jxlhip_modular_ac_group_decode_f32_strided",
     # include/jxl_hip_codestream.h
     "jxlhip_codestream_basic_info", "jxlhip_decode_codestream", "jxlhip_decode_codestream_extra",
-    "jxlhip_codestream_icc_profile", "jxlhip_codestream_phase_ms",
+    "jxlhip_codestream_icc_profile", "jxlhip_codestream_phase_ms", "jxlhip_codestream_sequence_info",
+    "jxlhip_decode_codestream_next",
 ]
 
 
@@ -327,6 +353,8 @@ def load_library():
     L.jxlhip_patches_destroy.restype = None
     L.jxlhip_set_reference_frame.argtypes = [vp, u32, u32, u32, vp, sz, i32]
     L.jxlhip_set_patches.argtypes = [vp, vp]
+    L.jxlhip_set_blending.argtypes = [vp, C.POINTER(BlendParams)]
+    L.jxlhip_canvas_read.argtypes = [vp, u32, vp, sz, C.POINTER(u32), C.POINTER(u32)]
     L.jxlhip_profile_read_ex.argtypes = [vp, C.POINTER(C.c_float), C.POINTER(u32), u32]
     L.jxlhip_splines_quantized.argtypes = [vp, C.POINTER(u32), C.POINTER(sz), C.POINTER(i32), vp, vp, vp, vp]
     L.jxlhip_modular_global_decode.argtypes = [vp, sz, C.POINTER(sz), C.POINTER(FrameHeader), C.POINTER(vp)]
@@ -386,6 +414,9 @@ def load_library():
     L.jxlhip_codestream_icc_profile.argtypes = [vp, sz, vp, sz, C.POINTER(sz)]
     L.jxlhip_icc_decode.argtypes = [vp, sz, C.POINTER(sz), vp, sz, C.POINTER(sz)]
     L.jxlhip_decode_codestream.argtypes = [vp, vp, vp, vp, sz, u32, vp, vp, sz, sz, C.POINTER(CodestreamInfo)]
+    L.jxlhip_codestream_sequence_info.argtypes = [vp, sz, C.POINTER(CodestreamInfo), C.POINTER(SequenceInfo)]
+    L.jxlhip_decode_codestream_next.argtypes = [vp, vp, vp, vp, sz, C.POINTER(C.c_uint64), u32, vp, vp, sz, sz,
+                                                C.POINTER(CodestreamInfo), C.POINTER(SequenceFrame)]
     L.jxlhip_codestream_phase_ms.argtypes = [vp, C.POINTER(C.c_double)]
     L.jxlhip_decode_codestream_extra.argtypes = [vp, vp, vp, vp, sz, u32, vp, vp, sz, sz, C.POINTER(vp), u32, sz,
                                                  C.POINTER(CodestreamInfo)]

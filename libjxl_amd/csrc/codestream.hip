@@ -4,6 +4,7 @@
 #include <functional>
 
 #include "context.h"
+#include "sequence_walk.h"
 
 namespace {
 
@@ -83,25 +84,6 @@ int ExtractCodestream(const uint8_t* data, size_t size, std::vector<uint8_t>* st
   return JXLHIP_OK;
 }
 
-// a kReferenceOnly frame in front of the visible one: what it leaves in its slot (ParseHeaders decodes it)
-struct ReferenceFrame {
-  uint32_t xsize = 0, ysize = 0;  // 0: the slot is empty
-  std::vector<float> xyb;         // three dense planes
-};
-
-struct ParsedHeaders {
-  jxlhip_image_header ih;
-  jxlhip_frame_header fh;  // of the visible frame
-  ReferenceFrame refs[4];
-  const char* why = "";    // JXLHIP_ERR_UNSUPPORTED from a reference frame: which case
-  size_t frame_bit_pos;  // first bit after the frame header (= the TOC)
-  jxlhip_extra_channel extra[4];
-  int alpha_index;       // first extra channel of type alpha, -1 = none
-  float inv_matrix[9];   // inverse opsin matrix into the ORIGINAL colour space (unscaled), jxlhip_output_opsin_matrix
-  float luminances[3];   // luminance weights of that space
-  size_t icc_size;       // size of the original's ICC profile (0 = an enumerated colour encoding)
-};
-
 // A kReferenceOnly frame (what cjxl writes in front of a frame with patches: the sheet its dictionary copies from):
 // decoded on the host into h->refs[save_as_reference]; *pos moves from the first bit behind its frame header to the
 // header of the next frame.
@@ -137,39 +119,10 @@ int ReadReferenceFrame(const uint8_t* cs, size_t n, const jxlhip_frame_header& f
 // image header + the reference frames + the visible frame's header + the eligibility rules of this back-end
 int ParseHeaders(const uint8_t* cs, size_t n, ParsedHeaders* h) {
   size_t pos = 0;
-  int rc = jxlhip_image_header_decode(cs, n, &pos, h->extra, 4, &h->ih);
+  jxlhip_image_info info{};
+  int rc = ParseImagePart(cs, n, h, &pos, &info, false);
   if (rc) return rc;
   const jxlhip_image_header& ih = h->ih;
-  h->icc_size = 0;
-  if (!ih.xyb_encoded || ih.num_extra_channels > 4 || ih.have_preview || ih.have_animation) return JXLHIP_ERR_UNSUPPORTED;
-  // an ICC original: the coded profile sits between the image header and the frame; it has to be decoded to find
-  // its end (jxlhip_codestream_icc_profile hands it out).  Pixels: linear sRGB, like the reference without a CMS
-  if (ih.color_encoding.want_icc && (rc = jxlhip_icc_decode(cs, n, &pos, nullptr, 0, &h->icc_size))) return rc;
-  // extra channels (alpha, depth, ...): full-resolution integer samples; the Modular front-end decodes them all,
-  // the back-end writes the first alpha channel
-  h->alpha_index = -1;
-  uint8_t dim_shift[4] = {0, 0, 0, 0};
-  for (uint32_t i = 0; i < ih.num_extra_channels; i++) {
-    const jxlhip_extra_channel& e = h->extra[i];
-    if (e.dim_shift != 0 || e.bit_depth.floating_point_sample || e.bit_depth.bits_per_sample == 0 ||
-        e.bit_depth.bits_per_sample > 24)
-      return JXLHIP_ERR_UNSUPPORTED;
-    if (e.type == JXLHIP_EC_ALPHA && h->alpha_index < 0) h->alpha_index = (int)i;
-  }
-  // Colour: the pixels come out in the image's ORIGINAL colour space, like JxlDecoder's default -- the inverse opsin
-  // matrix is adapted to the original's primaries / white point as OutputEncodingInfo::SetColorEncoding does
-  // (dec_xyb.cc:180-249); the caller applies the original's transfer function through out_format (the info struct
-  // says which).  ICC and grey originals are outside this front-end.
-  if ((rc = jxlhip_output_opsin_matrix(&ih, h->inv_matrix, h->luminances))) return rc;
-  jxlhip_image_info info{};
-  info.xsize = ih.xsize;
-  info.ysize = ih.ysize;
-  info.xyb_encoded = ih.xyb_encoded;
-  info.num_extra_channels = ih.num_extra_channels;
-  info.ec_dim_shift = dim_shift;
-  info.bits_per_sample = ih.bit_depth.bits_per_sample;
-  info.have_animation = 0;
-  info.have_timecodes = 0;
   // any number of kReferenceOnly frames, then exactly one regular frame, the last of the file: every other sequence
   // (animation, layers, DC frames) is outside this front-end
   for (;;) {
@@ -579,6 +532,26 @@ int jxlhip_codestream_phase_ms(const jxlhip_ctx* c, double* ms) {
   return JXLHIP_OK;
 }
 
+// what the caller of one frame's decode wants (DecodeFrameAt)
+struct FrameCall {
+  jxlhip_parallel_runner runner = nullptr;
+  void* runner_opaque = nullptr;
+  uint32_t output_kind = 0;      // without JXLHIP_OUT_UNDO_ORIENTATION
+  bool undo_orientation = false;
+  const jxlhip_output_format* out_format = nullptr;
+  void* out = nullptr;           // (NULL: a blended frame that is only saved)
+  size_t out_stride = 0, out_plane_stride = 0;
+  float* const* extra_planes = nullptr;
+  uint32_t num_extra_planes = 0;
+  size_t extra_stride = 0;
+  uint32_t out_xsize = 0, out_ysize = 0;  // the size an upsampled frame comes out at: the image's, or a cropped frame's own
+  uint32_t noise_visible = 1, noise_nonvisible = 0;  // PassesDecoderState::visible_frame_index / nonvisible_frame_index
+  const jxlhip_blend_params* blend = nullptr;
+};
+static int DecodeFrameAt(jxlhip_ctx* c, const uint8_t* cs, size_t n, const ParsedHeaders& h, const jxlhip_frame_header& fh,
+                         size_t frame_bit_pos, const FrameCall& fc, PhaseClock& clock, bool verbose, jxlhip_codestream_info* info_p,
+                         size_t* end_bit_pos);
+
 static int DecodeCodestreamImpl(jxlhip_ctx* c, jxlhip_parallel_runner runner, void* runner_opaque, const uint8_t* data,
                                 size_t size, uint32_t output_kind, const jxlhip_output_format* out_format, void* out,
                                 size_t out_stride, size_t out_plane_stride, float* const* extra_planes,
@@ -614,8 +587,42 @@ static int DecodeCodestreamImpl(jxlhip_ctx* c, jxlhip_parallel_runner runner, vo
   }
   jxlhip_codestream_info info;
   FillInfo(h, container, &info);
+  FrameCall fc;
+  fc.runner = runner;
+  fc.runner_opaque = runner_opaque;
+  fc.output_kind = output_kind;
+  fc.undo_orientation = undo_orientation;
+  fc.out_format = out_format;
+  fc.out = out;
+  fc.out_stride = out_stride;
+  fc.out_plane_stride = out_plane_stride;
+  fc.extra_planes = extra_planes;
+  fc.num_extra_planes = num_extra_planes;
+  fc.extra_stride = extra_stride;
+  fc.out_xsize = h.ih.xsize;
+  fc.out_ysize = h.ih.ysize;
+  if ((rc = DecodeFrameAt(c, cs, n, h, h.fh, h.frame_bit_pos, fc, clock, verbose, &info, nullptr))) return rc;
+  if (info_out) *info_out = info;
+  return JXLHIP_OK;
+}
+
+// One VarDCT frame of a file: from the first bit behind its frame header (the TOC) to the pixels (FrameCall::out; with
+// FrameCall::blend, blended over a canvas and / or saved, jxlhip_set_blending).  *end_bit_pos (may be NULL) = the first
+// bit behind its sections: the next frame's header.
+static int DecodeFrameAt(jxlhip_ctx* c, const uint8_t* cs, size_t n, const ParsedHeaders& h, const jxlhip_frame_header& fh,
+                         size_t frame_bit_pos, const FrameCall& fc, PhaseClock& clock, bool verbose, jxlhip_codestream_info* info_p,
+                         size_t* end_bit_pos) {
+  jxlhip_codestream_info& info = *info_p;
+  const jxlhip_parallel_runner runner = fc.runner;
+  void* const runner_opaque = fc.runner_opaque;
+  const uint32_t output_kind = fc.output_kind;
+  const bool undo_orientation = fc.undo_orientation;
+  const jxlhip_output_format* const out_format = fc.out_format;
+  float* const* const extra_planes = fc.extra_planes;
+  const uint32_t num_extra_planes = fc.num_extra_planes;
+  const size_t extra_stride = fc.extra_stride;
+  int rc;
   const jxlhip_image_header& ih = h.ih;
-  const jxlhip_frame_header& fh = h.fh;
   if (fh.num_groups > (1u << 22) || fh.num_passes == 0 || fh.num_passes > 11)
     return Fail(c, JXLHIP_ERR_UNSUPPORTED, "frame too large");
   {
@@ -631,7 +638,7 @@ static int DecodeCodestreamImpl(jxlhip_ctx* c, jxlhip_parallel_runner runner, vo
   const size_t nt = (size_t)((xsb + 7) / 8) * ((ysb + 7) / 8);
 
   // ---- table of contents
-  size_t pos = h.frame_bit_pos;
+  size_t pos = frame_bit_pos;
   const uint32_t ntoc = (uint32_t)fh.num_toc_entries;
   std::vector<uint64_t> off(ntoc);
   std::vector<uint32_t> sz(ntoc);
@@ -651,7 +658,12 @@ static int DecodeCodestreamImpl(jxlhip_ctx* c, jxlhip_parallel_runner runner, vo
   std::unique_ptr<jxlhip_patches, void (*)(jxlhip_patches*)> patches(nullptr, jxlhip_patches_destroy);
   if (fh.flags & JXLHIP_FLAG_PATCHES) {
     uint32_t ref_sizes[4][2];
-    for (int slot = 0; slot < 4; slot++) ref_sizes[slot][0] = h.refs[slot].xsize, ref_sizes[slot][1] = h.refs[slot].ysize;
+    // what the slots hold; a canvas (a sequence's saved frame) with its size, so that the dictionary decodes and
+    // jxlhip_set_patches names the refusal ("saved after the colour transform")
+    for (int slot = 0; slot < 4; slot++) {
+      ref_sizes[slot][0] = c->ref_w[slot] ? c->ref_w[slot] : c->canvas_w[slot];
+      ref_sizes[slot][1] = c->ref_h[slot] ? c->ref_h[slot] : c->canvas_h[slot];
+    }
     jxlhip_patches* pt = nullptr;
     if ((rc = jxlhip_patches_decode(sec(0), sz[0], &spos, fh.xsize_blocks * 8, fh.ysize_blocks * 8, 0, ref_sizes, &pt)))
       return Fail(c, rc, "invalid patch dictionary");
@@ -1031,14 +1043,15 @@ static int DecodeCodestreamImpl(jxlhip_ctx* c, jxlhip_parallel_runner runner, vo
   if (fh.upsampling != 1) {
     const uint32_t bit = fh.upsampling == 2 ? 1u : fh.upsampling == 4 ? 2u : 4u;
     const float* coded = fh.upsampling == 2 ? ih.upsampling2_weights : fh.upsampling == 4 ? ih.upsampling4_weights : ih.upsampling8_weights;
-    if ((rc = jxlhip_set_upsampling(c, fh.upsampling, (ih.custom_weights_mask & bit) ? coded : nullptr, ih.xsize, ih.ysize))) return rc;
+    if ((rc = jxlhip_set_upsampling(c, fh.upsampling, (ih.custom_weights_mask & bit) ? coded : nullptr, fc.out_xsize, fc.out_ysize))) return rc;
   }
-  // photon noise: the stream's only frame is visible frame 1 (FrameDecoder::InitFrame counts it before decoding,
-  // dec_frame.cc:160-168)
-  if ((fh.flags & JXLHIP_FLAG_NOISE) && (rc = jxlhip_set_noise(c, noise_lut, 1, 0))) return rc;
+  // photon noise: a file's only visible frame is visible frame 1 (FrameDecoder::InitFrame counts it before decoding,
+  // dec_frame.cc:160-168); a sequence counts its frames (WalkSequence)
+  if ((fh.flags & JXLHIP_FLAG_NOISE) && (rc = jxlhip_set_noise(c, noise_lut, fc.noise_visible, fc.noise_nonvisible))) return rc;
   if (patches && (rc = jxlhip_set_patches(c, patches.get()))) return rc;
   if (splines && (rc = jxlhip_set_splines(c, splines.get()))) return rc;
-  if ((rc = jxlhip_decode_frame(c, out, out_stride, out_plane_stride))) return rc;
+  if (fc.blend && (rc = jxlhip_set_blending(c, fc.blend))) return rc;
+  if ((rc = jxlhip_decode_frame(c, fc.out, fc.out_stride, fc.out_plane_stride))) return rc;
   if ((rc = jxlhip_sync(c))) return rc;
   clock.Mark(JXLHIP_PHASE_KERNELS);
   info.num_passes = np;
@@ -1047,6 +1060,188 @@ static int DecodeCodestreamImpl(jxlhip_ctx* c, jxlhip_parallel_runner runner, vo
   info.epf_iters = fh.lf.epf_iters;
   info.gab = fh.lf.gab;
   info.used_acs = used_acs;
-  if (info_out) *info_out = info;
+  if (end_bit_pos) *end_bit_pos = (base + (size_t)total) * 8;
   return JXLHIP_OK;
+}
+
+// ---- sequences of frames (jxlhip_codestream_sequence_info, jxlhip_decode_codestream_next) -----------------------------
+
+namespace {
+
+void FillSequenceInfo(Sequence& s, bool container, jxlhip_codestream_info* info, jxlhip_sequence_info* seq) {
+  ParsedHeaders& h = s.h;
+  for (const SeqFrame& f : s.frames)
+    if (f.displayed) {
+      h.fh = f.fh;
+      break;
+    }
+  FillInfo(h, container, info);
+  if (!seq) return;
+  memset(seq, 0, sizeof(*seq));
+  seq->have_animation = h.ih.have_animation;
+  if (h.ih.have_animation) {
+    seq->tps_numerator = h.ih.tps_numerator;
+    seq->tps_denominator = h.ih.tps_denominator;
+    seq->num_loops = h.ih.num_loops;
+    seq->have_timecodes = h.ih.have_timecodes;
+  }
+  seq->num_coded_frames = (uint32_t)s.frames.size();
+  seq->num_displayed_frames = s.displayed;
+  seq->why = "";
+}
+
+int SequenceNextImpl(jxlhip_ctx* c, jxlhip_parallel_runner runner, void* runner_opaque, const uint8_t* data, size_t size,
+                     uint64_t* cursor, uint32_t output_kind, const jxlhip_output_format* out_format, void* out, size_t out_stride,
+                     size_t out_plane_stride, jxlhip_codestream_info* info_out, jxlhip_sequence_frame* frame_out) {
+  const bool undo_orientation = (output_kind & JXLHIP_OUT_UNDO_ORIENTATION) != 0;
+  output_kind &= ~(uint32_t)JXLHIP_OUT_UNDO_ORIENTATION;
+  if (!c || !data || !out || !cursor || output_kind > JXLHIP_OUT_PACKED || (output_kind == JXLHIP_OUT_PACKED && !out_format))
+    return JXLHIP_ERR_INVALID_ARGUMENT;
+  JXLHIP_NO_MULTI(c);
+  if (*cursor != 0 && (!c->seq_open || *cursor != c->seq_expect)) {
+    return Fail(c, JXLHIP_ERR_STATE, c->seq_open ? "cursor %llu is not the one this context expects (%llu)"
+                                                 : "cursor %llu, but no sequence is open on this context (the last frame was decoded, or none was started)",
+                (unsigned long long)*cursor, (unsigned long long)c->seq_expect);
+  }
+  const bool start = *cursor == 0;
+  c->seq_open = false;  // (until this call has succeeded)
+  if (start) {  // one file's frames never reach the next
+    for (uint32_t slot = 0; slot < 4; slot++) {
+      const int cleared = jxlhip_set_reference_frame(c, slot, 0, 0, nullptr, 0, 0);
+      if (cleared) return cleared;
+    }
+  }
+  PhaseClock clock(c->cs_phase_ms);
+  const bool verbose = jxlhip_env::Get().codestream_verbose.load(std::memory_order_relaxed);
+  g_upload_wait_on.store(verbose);
+  std::vector<uint8_t> storage;
+  const uint8_t* cs = nullptr;
+  size_t n = 0;
+  bool container = false;
+  int rc = ExtractCodestream(data, size, &storage, &cs, &n, &container);
+  if (rc) return Fail(c, rc, "not a JPEG XL codestream or container");
+  Sequence s;
+  if ((rc = WalkSequence(cs, n, &s)))
+    return Fail(c, rc, rc == JXLHIP_ERR_UNSUPPORTED ? (s.h.why[0] ? s.h.why : "stream uses features outside the VarDCT back-end") : "invalid headers");
+  size_t i = 0;
+  if (!start) {
+    while (i < s.frames.size() && s.frames[i].header_bit / 8 != *cursor) i++;
+    if (i == s.frames.size()) return Fail(c, JXLHIP_ERR_STATE, "cursor %llu is no frame of these bytes", (unsigned long long)*cursor);
+  }
+  jxlhip_codestream_info info;
+  FillSequenceInfo(s, container, &info, nullptr);
+  const uint32_t W = s.h.ih.xsize, H = s.h.ih.ysize;
+  uint32_t coded = 0;
+  for (;; i++) {
+    SeqFrame& f = s.frames[i];
+    const jxlhip_frame_header& fh = f.fh;
+    coded++;
+    if (fh.frame_type == JXLHIP_FRAME_REFERENCE_ONLY) {
+      size_t pos = f.toc_bit;
+      if ((rc = ReadReferenceFrame(cs, n, fh, &pos, &s.h)))
+        return Fail(c, rc, rc == JXLHIP_ERR_UNSUPPORTED ? (s.h.why[0] ? s.h.why : "a reference frame outside the Modular front-end") : "invalid reference frame");
+      const ReferenceFrame& r = s.h.refs[fh.save_as_reference];
+      const size_t plane = (size_t)r.xsize * r.ysize;
+      const float* const planes[3] = {r.xyb.data(), r.xyb.data() + plane, r.xyb.data() + 2 * plane};
+      if ((rc = jxlhip_set_reference_frame(c, fh.save_as_reference, r.xsize, r.ysize, planes, r.xsize, 0))) return rc;
+      continue;
+    }
+    // a layer nothing reads and nobody sees leaves no trace
+    if (!f.displayed && !f.save) continue;
+    FrameCall fc;
+    fc.runner = runner;
+    fc.runner_opaque = runner_opaque;
+    fc.output_kind = output_kind;
+    fc.undo_orientation = undo_orientation;
+    fc.out_format = out_format;
+    fc.out = f.displayed ? out : nullptr;
+    fc.out_stride = out_stride;
+    fc.out_plane_stride = out_plane_stride;
+    fc.out_xsize = fh.custom_size_or_origin ? fh.coded_xsize : W;
+    fc.out_ysize = fh.custom_size_or_origin ? fh.coded_ysize : H;
+    fc.noise_visible = f.visible;
+    fc.noise_nonvisible = f.nonvisible;
+    jxlhip_blend_params b{};
+    if (f.blends || f.save) {
+      b.image_xsize = W;
+      b.image_ysize = H;
+      b.x0 = fh.custom_size_or_origin ? fh.x0 : 0;
+      b.y0 = fh.custom_size_or_origin ? fh.y0 : 0;
+      b.mode = fh.blend_mode;
+      b.clamp = fh.blend_clamp;
+      b.source = f.blends ? fh.blend_source : 0;
+      b.save_slot = f.save ? fh.save_as_reference : JXLHIP_BLEND_NO_SAVE;
+      if (b.source > 3 || (f.save && fh.save_as_reference > 3)) return Fail(c, JXLHIP_ERR_BAD_STREAM, "blend source / save slot out of range");
+      fc.blend = &b;
+    }
+    s.h.fh = fh;
+    if ((rc = DecodeFrameAt(c, cs, n, s.h, fh, f.toc_bit, fc, clock, verbose, &info, nullptr))) return rc;
+    if (f.displayed) break;
+  }
+  const SeqFrame& f = s.frames[i];
+  info.upsampling = f.fh.upsampling;
+  if (info_out) *info_out = info;
+  if (frame_out) {
+    memset(frame_out, 0, sizeof(*frame_out));
+    frame_out->index = f.display_index;
+    frame_out->duration = f.fh.duration;
+    frame_out->timecode = f.fh.timecode;
+    frame_out->is_last = f.fh.is_last;
+    frame_out->name_length = f.fh.name_length;
+    frame_out->have_crop = f.fh.custom_size_or_origin;
+    frame_out->x0 = f.fh.custom_size_or_origin ? f.fh.x0 : 0;
+    frame_out->y0 = f.fh.custom_size_or_origin ? f.fh.y0 : 0;
+    frame_out->xsize = f.fh.custom_size_or_origin ? f.fh.coded_xsize : W;
+    frame_out->ysize = f.fh.custom_size_or_origin ? f.fh.coded_ysize : H;
+    frame_out->blend_mode = f.fh.blend_mode;
+    frame_out->blend_source = f.fh.blend_source;
+    frame_out->blend_clamp = f.fh.blend_clamp;
+    frame_out->save_as_reference = f.fh.save_as_reference;
+    frame_out->coded_frames = coded;
+  }
+  *cursor = f.end_bit / 8;
+  c->seq_expect = *cursor;
+  c->seq_open = !f.fh.is_last;
+  return JXLHIP_OK;
+}
+
+}  // namespace
+
+int jxlhip_codestream_sequence_info(const uint8_t* data, size_t size, jxlhip_codestream_info* info, jxlhip_sequence_info* seq) {
+  if (!data || !info || !seq) return JXLHIP_ERR_INVALID_ARGUMENT;
+  try {
+    std::vector<uint8_t> storage;
+    const uint8_t* cs = nullptr;
+    size_t n = 0;
+    bool container = false;
+    int rc = ExtractCodestream(data, size, &storage, &cs, &n, &container);
+    if (rc) return rc;
+    Sequence s;
+    memset(seq, 0, sizeof(*seq));
+    seq->why = "";
+    if ((rc = WalkSequence(cs, n, &s))) {
+      if (rc == JXLHIP_ERR_UNSUPPORTED) seq->why = s.h.why[0] ? s.h.why : "stream uses features outside the VarDCT back-end";
+      return rc;
+    }
+    FillSequenceInfo(s, container, info, seq);
+    return JXLHIP_OK;
+  } catch (const std::bad_alloc&) {
+    return JXLHIP_ERR_OUT_OF_MEMORY;
+  }
+}
+
+int jxlhip_decode_codestream_next(jxlhip_ctx* c, jxlhip_parallel_runner runner, void* runner_opaque, const uint8_t* data,
+                                  size_t size, uint64_t* cursor, uint32_t output_kind, const jxlhip_output_format* out_format,
+                                  void* out, size_t out_stride, size_t out_plane_stride, jxlhip_codestream_info* info_out,
+                                  jxlhip_sequence_frame* frame_out) {
+  try {
+    const int rc = SequenceNextImpl(c, runner, runner_opaque, data, size, cursor, output_kind, out_format, out, out_stride,
+                                    out_plane_stride, info_out, frame_out);
+    // an early return may leave uploads of a frame queued: nothing of it may still be in flight when the caller frees
+    // its buffers
+    if (rc != JXLHIP_OK && c && !c->multi && c->stream) (void)hipStreamSynchronize(c->stream);
+    return rc;
+  } catch (const std::bad_alloc&) {
+    return c ? Fail(c, JXLHIP_ERR_OUT_OF_MEMORY, "host allocation failed while decoding the codestream") : JXLHIP_ERR_OUT_OF_MEMORY;
+  }
 }

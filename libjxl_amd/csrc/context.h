@@ -301,6 +301,18 @@ struct jxlhip_ctx {
   // ups_ysize; ups_planes = the filtered frame as planar XYB at CODED size (kernels_upsample.hip; noise_buf then holds
   // the upsampled planes + the random planes at output size), ups_weights = the factor's kernels (UpsampleKernels),
   // ups_weights_host the copy their upload reads
+  // jxlhip_set_blending: the current frame is blended over a canvas and / or saved (frame_begin resets blend_on).
+  // canvas[s] = the canvas of slot s: interleaved float RGB in the output's transfer function, CanvasStride(canvas_w)
+  // floats per row (rows padded to four pixels: k_blend's 16-byte vectors), canvas_w x canvas_h (0: none); a slot holds
+  // either this or ref_planes.  blend_stage = the frame's own output in front of k_blend (DecodeFrameBlended).
+  bool blend_on = false;
+  jxlhip_blend_params blend{};
+  DevBuf<float> canvas[4];
+  uint32_t canvas_w[4] = {0, 0, 0, 0}, canvas_h[4] = {0, 0, 0, 0};
+  DevBuf<float> blend_stage;
+  // jxlhip_decode_codestream_next: a sequence is open and this is the cursor the next call must bring
+  bool seq_open = false;
+  uint64_t seq_expect = 0;
   uint32_t ups_factor = 1, ups_xsize = 0, ups_ysize = 0;
   DevBuf<float> ups_planes;
   DevBuf<float> ups_weights;
@@ -344,6 +356,9 @@ inline size_t OutPixelBytes(const jxlhip_ctx* c) {
 // size an upsampled frame (jxlhip_set_upsampling: whole frames only) comes out at
 inline size_t OutCols(const jxlhip_ctx* c) { return c->ups_factor > 1 ? c->ups_xsize : c->f.xsize; }
 inline size_t OutRows(const jxlhip_ctx* c) { return c->ups_factor > 1 ? c->ups_ysize : c->f.y1 - c->f.y0; }
+// ... and of what the caller's buffer holds: the image when the frame is blended (jxlhip_set_blending)
+inline size_t BufCols(const jxlhip_ctx* c) { return c->blend_on ? c->blend.image_xsize : OutCols(c); }
+inline size_t BufRows(const jxlhip_ctx* c) { return c->blend_on ? c->blend.image_ysize : OutRows(c); }
 
 // context.hip
 jxlhip_ctx* NewCtx(const JxlMemoryManagerHip* mm);

@@ -354,6 +354,7 @@ int jxlhip_frame_begin(jxlhip_ctx* c, const jxlhip_frame_params* p) {
   c->splines_on = false;
   c->patches_on = false;
   c->ups_factor = 1;
+  c->blend_on = false;
   return JXLHIP_OK;
 }
 
@@ -414,6 +415,7 @@ int jxlhip_set_alpha(jxlhip_ctx* c, const float* host_plane, size_t stride_float
   if (!c->have_frame) return Fail(c, JXLHIP_ERR_STATE, "set_alpha before frame_begin");
   if (c->ups_factor > 1) return Fail(c, JXLHIP_ERR_UNSUPPORTED, "alpha on an upsampled frame");
   if (c->patches_on) return Fail(c, JXLHIP_ERR_UNSUPPORTED, "alpha on a frame with patches (they would have to blend it)");
+  if (c->blend_on) return Fail(c, JXLHIP_ERR_UNSUPPORTED, "alpha on a blended frame (blending extra channels is not in the back-end)");
   if (c->multi) {  // every stripe takes its own rows of the plane
     for (MultiChild& k : c->multi->kids) {
       const int rc = jxlhip_set_alpha(k.ctx, host_plane, stride_floats);
@@ -559,6 +561,8 @@ int jxlhip_set_reference_frame(jxlhip_ctx* c, uint32_t slot, uint32_t xsize, uin
   if (!c || slot > 3) return JXLHIP_ERR_INVALID_ARGUMENT;
   if (c->multi) return Fail(c, JXLHIP_ERR_UNSUPPORTED, "reference frames on a multi-device context");
   c->ref_serial++;  // (an uploaded dictionary points into the slots: DecodeFrameFeatures refuses it from here on)
+  c->seq_open = false;  // (a sequence of jxlhip_decode_codestream_next must not go on over slots emptied behind its back)
+  c->canvas_w[slot] = c->canvas_h[slot] = 0;  // (a slot holds one kind: an XYB frame drops the canvas)
   if (xsize == 0 || ysize == 0) {  // cleared; the memory stays for the next frame of the slot
     c->ref_w[slot] = c->ref_h[slot] = 0;
     return JXLHIP_OK;
@@ -613,6 +617,8 @@ int jxlhip_set_patches(jxlhip_ctx* c, const jxlhip_patches* s) {
   std::vector<uint32_t> count(tiles + 1, 0);
   for (uint32_t i = 0; i < n; i++) {
     const jxlhip_patch& p = list[i];
+    if (p.ref <= 3 && c->canvas_w[p.ref] != 0)
+      return Fail(c, JXLHIP_ERR_INVALID_ARGUMENT, "patch %u: slot %u holds a frame saved after the colour transform", i, p.ref);
     if (p.ref > 3 || c->ref_w[p.ref] == 0)
       return Fail(c, JXLHIP_ERR_INVALID_ARGUMENT, "patch %u: reference slot %u is empty", i, p.ref);
     const uint32_t rw = c->ref_w[p.ref], rh = c->ref_h[p.ref];
@@ -713,6 +719,45 @@ int jxlhip_set_upsampling(jxlhip_ctx* c, uint32_t factor, const float* weights, 
   c->ups_factor = factor;
   c->ups_xsize = out_xsize;
   c->ups_ysize = out_ysize;
+  return JXLHIP_OK;
+}
+
+// Blending of the current frame (FrameHeader::blending_info, frame_origin, save_as_reference): recorded here, carried
+// out by DecodeFrameBlended; frame_begin resets to "not blended".
+int jxlhip_set_blending(jxlhip_ctx* c, const jxlhip_blend_params* b) {
+  if (!c) return JXLHIP_ERR_INVALID_ARGUMENT;
+  if (c->multi) return Fail(c, JXLHIP_ERR_UNSUPPORTED, "blending on a multi-device context");
+  if (!c->have_frame) return Fail(c, JXLHIP_ERR_STATE, "set_blending before frame_begin");
+  c->blend_on = false;
+  if (!b) return JXLHIP_OK;
+  if (c->f.group_y0 != 0 || c->f.group_rows != c->f.ysg) return Fail(c, JXLHIP_ERR_UNSUPPORTED, "blending with stripes");
+  if (c->p.undo_orientation > 1)
+    return Fail(c, JXLHIP_ERR_UNSUPPORTED, "blending with undo_orientation %u", c->p.undo_orientation);
+  if (c->p.output_kind == JXLHIP_OUT_XYB_PLANAR)
+    return Fail(c, JXLHIP_ERR_UNSUPPORTED, "blending with planar XYB output (canvases are frames saved after the colour transform)");
+  if (c->fp.alpha) return Fail(c, JXLHIP_ERR_UNSUPPORTED, "blending on a frame with alpha (blending extra channels is not in the back-end)");
+  if (b->image_xsize == 0 || b->image_ysize == 0 || b->image_xsize > (1u << 19) || b->image_ysize > (1u << 19))
+    return Fail(c, JXLHIP_ERR_INVALID_ARGUMENT, "image size %ux%u out of range", b->image_xsize, b->image_ysize);
+  if (b->x0 < -(1 << 30) || b->x0 > (1 << 30) || b->y0 < -(1 << 30) || b->y0 > (1 << 30))
+    return Fail(c, JXLHIP_ERR_INVALID_ARGUMENT, "frame origin (%d, %d) out of range", b->x0, b->y0);
+  if (b->mode > JXLHIP_BLEND_MUL) return Fail(c, JXLHIP_ERR_INVALID_ARGUMENT, "blend mode %u", b->mode);
+  if (b->source > 3 || (b->save_slot > 3 && b->save_slot != JXLHIP_BLEND_NO_SAVE))
+    return Fail(c, JXLHIP_ERR_INVALID_ARGUMENT, "blend source slot %u / save slot %u", b->source, b->save_slot);
+  c->blend = *b;
+  c->blend_on = true;
+  return JXLHIP_OK;
+}
+
+int jxlhip_canvas_read(jxlhip_ctx* c, uint32_t slot, float* dev_out, size_t stride_floats, uint32_t* w, uint32_t* h) {
+  if (!c || slot > 3 || !w || !h) return JXLHIP_ERR_INVALID_ARGUMENT;
+  if (c->multi) return Fail(c, JXLHIP_ERR_UNSUPPORTED, "canvases on a multi-device context");
+  *w = c->canvas_w[slot];
+  *h = c->canvas_h[slot];
+  if (!dev_out || *w == 0) return JXLHIP_OK;
+  if (stride_floats < 3 * (size_t)*w) return Fail(c, JXLHIP_ERR_INVALID_ARGUMENT, "canvas stride %zu < 3 * %u", stride_floats, *w);
+  HIPCHK(c, hipSetDevice(c->device));
+  HIPCHK(c, hipMemcpy2DAsync(dev_out, stride_floats * sizeof(float), c->canvas[slot], CanvasStride(*w) * sizeof(float),
+                             3 * (size_t)*w * sizeof(float), *h, hipMemcpyDeviceToDevice, c->stream));
   return JXLHIP_OK;
 }
 
@@ -1104,6 +1149,7 @@ int jxlhip_decode_filters_rows(jxlhip_ctx* c, void* out, size_t out_stride, size
     return Fail(c, JXLHIP_ERR_UNSUPPORTED, "patches with the split calls (jxlhip_decode_frame takes them)");
   if (c->ups_factor > 1)
     return Fail(c, JXLHIP_ERR_UNSUPPORTED, "upsampling with the split calls (jxlhip_decode_frame takes it)");
+  if (c->blend_on) return Fail(c, JXLHIP_ERR_UNSUPPORTED, "blending with the split calls (jxlhip_decode_frame takes it)");
   int rc = CheckOutArgs(c, out, out_stride, out_plane_stride, c->f.xsize, c->f.y1 - c->f.y0);
   if (rc) return rc;
   HIPCHK(c, hipSetDevice(c->device));
@@ -1154,11 +1200,13 @@ int jxlhip_stripe_finish(jxlhip_ctx* c, const float* recv_up, const float* recv_
 // Both phases, each over the whole stripe.
 static int DecodeFrameCoded(jxlhip_ctx* c, void* out, size_t out_stride, size_t out_plane_stride);
 static int DecodeFrameFeatures(jxlhip_ctx* c, void* out, size_t out_stride, size_t out_plane_stride);
+static int DecodeFrameBlended(jxlhip_ctx* c, void* out, size_t out_stride);
 
 int jxlhip_decode_frame(jxlhip_ctx* c, void* out, size_t out_stride, size_t out_plane_stride) {
   if (!c) return JXLHIP_ERR_INVALID_ARGUMENT;
   if (c->multi) return out ? MultiDecodeFrame(c, out, nullptr, out_stride, out_plane_stride) : JXLHIP_ERR_INVALID_ARGUMENT;
   if (!c->have_frame) return Fail(c, JXLHIP_ERR_STATE, "decode needs frame_begin + inputs");
+  if (c->blend_on) return DecodeFrameBlended(c, out, out_stride);
   if (c->noise_on || c->splines_on || c->patches_on || c->ups_factor > 1) return DecodeFrameFeatures(c, out, out_stride, out_plane_stride);
   if (c->p.undo_orientation <= 1) return DecodeFrameCoded(c, out, out_stride, out_plane_stride);
   // undo_orientation: coded orientation into a staging frame, k_orient into the caller's buffer
@@ -1330,6 +1378,139 @@ static int DecodeFrameFeatures(jxlhip_ctx* c, void* out, size_t out_stride, size
   return JXLHIP_OK;
 }
 
+// A blended frame (jxlhip_set_blending): the frame's whole path -- DecodeFrameCoded or DecodeFrameFeatures, whatever it
+// would take without blending -- writes packed float RGB in the caller's transfer function into blend_stage, and
+// k_blend (kernels_blend.hip) blends that over the source canvas into the save slot and / or the caller's buffer,
+// which is image-sized.  The canvas never leaves the device.
+static int DecodeFrameBlended(jxlhip_ctx* c, void* out, size_t out_stride) {
+  const jxlhip_blend_params& b = c->blend;
+  const DevFrame& f = c->f;
+  // (set_blending has checked these; set_alpha, set_upsampling .. may have been called since)
+  if (f.group_y0 != 0 || f.group_rows != f.ysg || c->p.undo_orientation > 1 || c->p.output_kind == JXLHIP_OUT_XYB_PLANAR)
+    return Fail(c, JXLHIP_ERR_UNSUPPORTED, "blending needs a whole frame in coded orientation and an interleaved output");
+  if (c->fp.alpha) return Fail(c, JXLHIP_ERR_UNSUPPORTED, "blending on a frame with alpha");
+  const uint32_t W = b.image_xsize, H = b.image_ysize;
+  const bool save = b.save_slot != JXLHIP_BLEND_NO_SAVE;
+  if (!out && !save) return Fail(c, JXLHIP_ERR_INVALID_ARGUMENT, "null output and no save slot");
+  int rc;
+  if (out && (rc = CheckOutArgs(c, out, out_stride, 0, W, H))) return rc;
+  if (Capturing(c->stream))  // (canvas and staging memory may have to grow: a synchronise and an allocation)
+    return Fail(c, JXLHIP_ERR_UNSUPPORTED, "blending while the stream is being captured");
+  const int64_t fw = (int64_t)OutCols(c), fh = (int64_t)OutRows(c);
+  const uint32_t op = b.mode == JXLHIP_BLEND_MUL ? (b.clamp ? kPatchOpMulClamp : kPatchOpMul)
+                      : (b.mode == JXLHIP_BLEND_ADD || b.mode == JXLHIP_BLEND_ALPHA_WEIGHTED_ADD) ? kPatchOpAdd
+                                                                                                 : kPatchOpReplace;
+  const bool full = b.x0 == 0 && b.y0 == 0 && fw == W && fh == H;
+  // a full frame that replaces never reads its source: whatever the slot holds is no concern of this frame
+  const bool bg_dead = full && op == kPatchOpReplace;
+  if (!bg_dead && c->ref_w[b.source] != 0)
+    return Fail(c, JXLHIP_ERR_INVALID_ARGUMENT, "blend source slot %u holds an XYB reference frame", b.source);
+  const bool have_src = !bg_dead && c->canvas_w[b.source] != 0;
+  if (have_src && (c->canvas_w[b.source] < W || c->canvas_h[b.source] < H))
+    return Fail(c, JXLHIP_ERR_INVALID_ARGUMENT, "the %ux%u canvas of slot %u is smaller than the %ux%u image",
+                c->canvas_w[b.source], c->canvas_h[b.source], b.source, W, H);
+  const bool in_place = save && have_src && b.save_slot == b.source;
+  if (in_place && (c->canvas_w[b.source] != W || c->canvas_h[b.source] != H))
+    return Fail(c, JXLHIP_ERR_INVALID_ARGUMENT, "save_slot == source with a %ux%u canvas and a %ux%u image",
+                c->canvas_w[b.source], c->canvas_h[b.source], W, H);
+  // a full frame that replaces and is not saved: today's path and launches, nothing else
+  if (full && op == kPatchOpReplace && !save) {
+    return c->noise_on || c->splines_on || c->patches_on || c->ups_factor > 1 ? DecodeFrameFeatures(c, out, out_stride, 0)
+                                                                             : DecodeFrameCoded(c, out, out_stride, 0);
+  }
+  HIPCHK(c, hipSetDevice(c->device));
+  BlendArgs A{};
+  A.W = W;
+  A.H = H;
+  A.rx0 = (int32_t)std::max<int64_t>(b.x0, 0);
+  A.ry0 = (int32_t)std::max<int64_t>(b.y0, 0);
+  A.rx1 = (int32_t)std::min<int64_t>((int64_t)b.x0 + fw, W);
+  A.ry1 = (int32_t)std::min<int64_t>((int64_t)b.y0 + fh, H);
+  const bool empty = A.rx1 <= A.rx0 || A.ry1 <= A.ry0;
+  if (empty) A.rx0 = A.rx1 = A.ry0 = A.ry1 = 0;
+  A.op = op;
+  // the frame itself, staged: (x0 mod 4) pixels into rows padded to four pixels (see kernels_blend.hip).  A frame that
+  // lies wholly outside the image is still decoded: its stream errors must surface as they do without blending.
+  const int32_t xa = b.x0 & ~3;  // (rounds down, also below zero)
+  const size_t lead = (size_t)(b.x0 - xa);
+  const size_t stage_stride = CanvasStride((uint32_t)(lead + (size_t)fw));
+  if ((rc = c->blend_stage.Reserve(c, (size_t)fh * stage_stride))) return rc;
+  {
+    const jxlhip_frame_params keep_p = c->p;
+    const FilterParams keep_fp = c->fp;
+    if (c->p.output_kind == JXLHIP_OUT_PACKED) {  // float RGB in the caller's transfer function: no dither, no alpha
+      jxlhip_output_format& o = c->p.out_format;
+      o.sample_type = JXLHIP_SAMPLE_F32;
+      o.num_channels = 3;
+      o.swap_endianness = 0;
+      c->fp.fmt = o;
+      c->fp.sample_mul = 1.0f;
+    }
+    float* stage_out = c->blend_stage + 3 * lead;
+    rc = c->noise_on || c->splines_on || c->patches_on || c->ups_factor > 1
+             ? DecodeFrameFeatures(c, stage_out, stage_stride * sizeof(float), 0)
+             : DecodeFrameCoded(c, stage_out, stage_stride * sizeof(float), 0);
+    c->p = keep_p;
+    c->fp = keep_fp;
+    if (rc) return rc;
+  }
+  A.fg = c->blend_stage;
+  A.fg_xa = xa;
+  A.fg_y0 = b.y0;
+  A.fg_stride = stage_stride;
+  if (have_src) {
+    A.src = c->canvas[b.source];
+    A.src_stride = CanvasStride(c->canvas_w[b.source]);
+  }
+  if (save) {
+    const uint32_t s = b.save_slot;
+    if (!in_place) {
+      const size_t need = (size_t)H * CanvasStride(W);
+      if (need > c->canvas[s].n) HIPCHK(c, hipStreamSynchronize(c->stream));  // an earlier launch may still read the slot
+      if ((rc = c->canvas[s].Reserve(c, need))) return rc;
+    }
+    A.dst = c->canvas[s];
+    A.dst_stride = CanvasStride(W);
+    A.dst_all = in_place ? 0u : 1u;
+  }
+  // the caller's buffer or another slot is written everywhere; a frame blended into its own source slot only under
+  // its rectangle
+  if (out || (save && !in_place)) {
+    A.gx0 = 0;
+    A.gx1 = (W + 3) / 4;
+    A.y0 = 0;
+    A.y1 = H;
+  } else {
+    A.gx0 = (uint32_t)A.rx0 / 4;
+    A.gx1 = ((uint32_t)A.rx1 + 3) / 4;
+    A.y0 = (uint32_t)A.ry0;
+    A.y1 = (uint32_t)A.ry1;
+  }
+  FilterParams fp = c->fp;
+  fp.fmt.transfer = JXLHIP_TF_LINEAR;  // the samples are encoded already: neither the HLG OOTF nor the curve runs twice
+  fp.out = out;
+  fp.out_stride = out_stride;
+  fp.out_plane_stride = 0;
+  // (a layer wholly outside the image that is blended into its own source slot visits nothing: no launch, no span)
+  if (A.gx1 > A.gx0 && A.y1 > A.y0) {
+    ProfBegin(c);
+    if (!LaunchBlend(A, fp, out ? (int)c->p.output_kind : 0, c->stream))
+      return Fail(c, JXLHIP_ERR_INVALID_ARGUMENT, "blend launch arguments");
+    ProfMark(c, JXLHIP_KERNEL_BLEND);
+    HIPCHK(c, hipGetLastError());
+  }
+  if (save) {
+    const uint32_t s = b.save_slot;
+    c->canvas_w[s] = W;
+    c->canvas_h[s] = H;
+    if (c->ref_w[s] != 0) {  // (a slot holds one kind: the canvas drops the XYB frame, and a dictionary that points into it)
+      c->ref_w[s] = c->ref_h[s] = 0;
+      c->ref_serial++;
+    }
+  }
+  return JXLHIP_OK;
+}
+
 // The boundary handing over a HOST buffer (what JxlDecoderSetImageOutBuffer gives libjxl): both phases
 // into a context-owned device frame, one strided device-to-host copy, synchronised.
 int jxlhip_decode_frame_host(jxlhip_ctx* c, void* host_out, size_t out_stride, size_t out_plane_stride) {
@@ -1341,8 +1522,8 @@ int jxlhip_decode_frame_host(jxlhip_ctx* c, void* host_out, size_t out_stride, s
   if (!c->have_frame) return Fail(c, JXLHIP_ERR_STATE, "decode needs frame_begin + inputs");
   const DevFrame& f = c->f;
   const bool transposed = c->p.undo_orientation >= 5;  // the oriented frame is ysize wide, xsize high
-  const size_t rows = transposed ? f.xsize : OutRows(c);  // (an upsampled frame is never transposed)
-  const size_t cols = transposed ? f.ysize : OutCols(c);
+  const size_t rows = transposed ? f.xsize : BufRows(c);  // (an upsampled or blended frame is never transposed)
+  const size_t cols = transposed ? f.ysize : BufCols(c);
   const bool planar = c->p.output_kind == JXLHIP_OUT_XYB_PLANAR;
   const size_t row_bytes = cols * (planar ? 4 : OutPixelBytes(c));
   const size_t host_row = planar ? out_stride * 4 : out_stride;
@@ -1366,8 +1547,8 @@ int jxlhip_decode_frame_pinned(jxlhip_ctx* c, const void** host_frame, size_t* s
   const jxlhip_frame_params& p = c->p;
   if (p.output_kind == JXLHIP_OUT_XYB_PLANAR) return Fail(c, JXLHIP_ERR_UNSUPPORTED, "pinned frames are interleaved outputs");
   const bool transposed = p.undo_orientation >= 5;
-  const size_t rows = transposed ? p.xsize : (c->ups_factor > 1 ? c->ups_ysize : p.ysize);
-  const size_t cols = transposed ? p.ysize : (c->ups_factor > 1 ? c->ups_xsize : p.xsize);
+  const size_t rows = transposed ? p.xsize : (c->blend_on ? c->blend.image_ysize : c->ups_factor > 1 ? c->ups_ysize : p.ysize);
+  const size_t cols = transposed ? p.ysize : (c->blend_on ? c->blend.image_xsize : c->ups_factor > 1 ? c->ups_xsize : p.xsize);
   const size_t row_bytes = cols * OutPixelBytes(c);
   const size_t pitch = (row_bytes + 63) & ~(size_t)63;
   if (rows * pitch > c->pinned_frame.bytes) {

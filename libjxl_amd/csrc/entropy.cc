@@ -1723,6 +1723,13 @@ int jxlhip_frame_header_decode(const uint8_t* data, size_t size, size_t* bit_pos
         Blending e;
         if ((rc = ReadBlending(&r, num_ec, is_partial, &e))) return rc;
         replace_all &= e.mode == 0;
+        if (e.mode != 0) h->ec_blend_any = 1;
+        if (i < 4) {
+          h->ec_blend_mode[i] = e.mode;
+          h->ec_blend_alpha_channel[i] = e.alpha_channel;
+          h->ec_blend_clamp[i] = e.clamp;
+          h->ec_blend_source[i] = e.source;
+        }
         if (!br.Healthy()) return kBad;
       }
       if (im->is_preview && (!replace_all || h->custom_size_or_origin)) return kBad;

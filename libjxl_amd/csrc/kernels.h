@@ -197,6 +197,28 @@ constexpr uint32_t kPatchBatch = 128;
 // active tiles back into A.xyb_out (planar XYB, for the launches that follow).  False for a bad output kind.
 bool LaunchPatches(const PatchArgs& A, const FilterParams& p, int output_kind, bool in_place, hipStream_t st);
 
+// Blending (kernels_blend.hip).  Canvases are interleaved float RGB, rows padded to four pixels (CanvasStride); a
+// thread takes one group of four pixels.
+inline size_t CanvasStride(uint32_t xsize) { return 3 * (((size_t)xsize + 3) & ~(size_t)3); }  // floats per row
+struct BlendArgs {
+  uint32_t W, H;               // the canvas = the image
+  int32_t rx0, ry0, rx1, ry1;  // the frame's rectangle clipped to the canvas, [rx0, rx1) x [ry0, ry1) (may be empty)
+  uint32_t gx0, gx1, y0, y1;   // what the launch visits: 4-pixel groups [gx0, gx1) of rows [y0, y1)
+  uint32_t op;                 // kPatchOp*: what PerformBlending's colour mode comes to without an alpha channel
+  uint32_t dst_all;            // write dst in every visited group (else only in those that touch the rectangle)
+  const float* fg;             // the staged frame: canvas pixel (x, y) is at fg + (y - fg_y0) * fg_stride + 3 * (x - fg_xa)
+  int32_t fg_xa, fg_y0;        // fg_xa = the frame's x origin rounded DOWN to a multiple of 4, fg_y0 its y origin
+  size_t fg_stride;            // floats per staged row, a multiple of 12; fg is 16-byte aligned
+  const float* src;            // the source canvas (src_stride floats per row), nullptr = zeroes
+  size_t src_stride;
+  float* dst;                  // the slot saved into (may be src), nullptr = none
+  size_t dst_stride;
+};
+// k_blend: output_kind 0 = the caller's output is not written, else JXLHIP_OUT_LINEAR_RGB_F32 / JXLHIP_OUT_PACKED into
+// p.out at canvas coordinates (p.fmt.transfer must be the identity: the samples are encoded already).  False for a bad
+// kind, op or region.
+bool LaunchBlend(const BlendArgs& A, const FilterParams& p, int output_kind, hipStream_t st);
+
 // Upsampling (kernels_upsample.hip).  The coded frame is cut into 64 x 16 tiles; every coded pixel gives n x n output
 // pixels, each a 25-tap sum over its 5 x 5 neighbourhood clamped to the neighbourhood's range.
 struct UpsampleArgs {

@@ -56,6 +56,7 @@ class VarDctDecoder:
             params = abi.make_params(params)
         self.params = params
         self.out_size = None  # (xsize, ysize) of an upsampled frame's output: set_upsampling
+        self.image_size = None  # (xsize, ysize) of the image a blended frame is written at: set_blending
         _check(self.L, self.ctx, self.L.jxlhip_frame_begin(self.ctx, C.byref(params)), "frame_begin")
 
     def default_dequant_tables(self):
@@ -107,6 +108,8 @@ class VarDctDecoder:
         oh, ow = (p.xsize, p.ysize) if p.undo_orientation >= 5 else (y1 - y0, p.xsize)
         if self.out_size is not None:  # an upsampled frame (whole frames, coded orientation)
             ow, oh = self.out_size
+        if self.image_size is not None:  # a blended frame: the caller's buffer is the image
+            ow, oh = self.image_size
         if p.output_kind == 1:
             return torch.empty((oh, ow, 3), dtype=torch.float32, device=dev)
         if p.output_kind == 2:  # packed RGB(A): dtype of the sample type (F16 as raw uint16 bits)
@@ -208,6 +211,34 @@ class VarDctDecoder:
         _check(self.L, self.ctx, self.L.jxlhip_set_upsampling(self.ctx, int(factor), w, ox, oy), "set_upsampling")
         self.out_size = (ox, oy) if int(factor) > 1 else None
 
+    def set_blending(self, image_size, origin=(0, 0), mode=abi.BLEND_REPLACE, clamp=False, source=0, save_slot=None):
+        """Blending of the current frame, jxlhip_set_blending: the frame's own output is blended at `origin` = (x0, y0)
+        (signed) over the canvas of slot `source` with BlendMode `mode` (abi.BLEND_*), written at image_size =
+        (xsize, ysize) and saved into save_slot (0..3; None = not saved).  decode_frame() then allocates an
+        image-sized tensor; decode_frame(out=False) only saves.  None instead of image_size switches blending off;
+        begin_frame resets."""
+        if image_size is None:
+            _check(self.L, self.ctx, self.L.jxlhip_set_blending(self.ctx, None), "set_blending")
+            self.image_size = None
+            return
+        b = abi.BlendParams(int(image_size[0]), int(image_size[1]), int(origin[0]), int(origin[1]), int(mode), int(bool(clamp)),
+                            int(source), abi.BLEND_NO_SAVE if save_slot is None else int(save_slot))
+        _check(self.L, self.ctx, self.L.jxlhip_set_blending(self.ctx, C.byref(b)), "set_blending")
+        self.image_size = (b.image_xsize, b.image_ysize)
+
+    def read_canvas(self, slot):
+        """The canvas of slot 0..3 (a frame saved by set_blending's save_slot) as a float32 CUDA tensor [ysize, xsize, 3]
+        in the transfer function of the frames that made it; None when the slot holds no canvas."""
+        w, h = C.c_uint32(), C.c_uint32()
+        _check(self.L, self.ctx, self.L.jxlhip_canvas_read(self.ctx, int(slot), None, 0, C.byref(w), C.byref(h)), "canvas_read")
+        if w.value == 0:
+            return None
+        t = torch.empty((h.value, w.value, 3), dtype=torch.float32, device=f"cuda:{self.device}")
+        _check(self.L, self.ctx, self.L.jxlhip_canvas_read(self.ctx, int(slot), C.c_void_p(t.data_ptr()), 3 * w.value,
+                                                          C.byref(w), C.byref(h)), "canvas_read")
+        self.sync()
+        return t
+
     # -- decode ----------------------------------------------------------------
     def decode_blocks(self):
         _check(self.L, self.ctx, self.L.jxlhip_decode_blocks(self.ctx), "decode_blocks")
@@ -222,6 +253,9 @@ class VarDctDecoder:
             _check(self.L, self.ctx, self.L.jxlhip_decode_filters_rows(self.ctx, *a, int(rows[0]), int(rows[1])), "decode_filters_rows")
 
     def decode_frame(self, out=None):
+        if out is False:  # a blended frame that is only saved (set_blending with a save_slot)
+            _check(self.L, self.ctx, self.L.jxlhip_decode_frame(self.ctx, None, 0, 0), "decode_frame")
+            return None
         if out is None:
             out = self.alloc_output()
         a = self._out_args(out)

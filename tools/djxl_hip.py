@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""djxl_hip.py IN.jxl OUT.{pfm,npy,ppm,pam} [--threads N] [--reps K]
+"""djxl_hip.py IN.jxl OUT.{pfm,npy,ppm,pam} [--threads N] [--reps K] [--frames]
 
 Decodes a .jxl file (container or bare codestream, one VarDCT still frame) on an MI355X through
 jxlhip_decode_codestream (include/jxl_hip_codestream.h) and writes the pixels the way djxl does for these
@@ -12,7 +12,10 @@ extensions (tools/djxl_main.cc, lib/extras/enc/pnm.cc):
 Photon noise (kNoise frames), splines (kSplines) and patches (kPatches behind their kReferenceOnly frames: what cjxl
 writes for screenshots and text) are rendered on the device.  Streams outside the back-end (Modular frames, animation
 ...) exit with status 3 and the error text so that a
-wrapper can fall back to libjxl's djxl.  Prints Mpx/s of the decode call like djxl's SpeedStats."""
+wrapper can fall back to libjxl's djxl.  Prints Mpx/s of the decode call like djxl's SpeedStats.
+--frames: animations, layers, cropped and blended frames through jxlhip_decode_codestream_next: one file per DISPLAYED
+frame, OUT-000.ext, OUT-001.ext ... (coalesced, like djxl); the frames are blended on the device in the encoding of the
+output: the original's for .ppm (what the reference blends in), linear light for .pfm / .npy.  No alpha (.pam)."""
 import argparse
 import ctypes as C
 import os
@@ -24,19 +27,45 @@ import numpy as np
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
 
+def write(path, ext, px, w, h):
+    if ext == ".npy":
+        np.save(path, px)
+    elif ext == ".pfm":
+        with open(path, "wb") as f:
+            f.write(b"PF\n%d %d\n-1.0\n" % (w, h))
+            f.write(np.ascontiguousarray(px[::-1]).astype("<f4").tobytes())
+    elif ext == ".ppm":
+        with open(path, "wb") as f:
+            f.write(b"P6\n%d %d\n255\n" % (w, h))
+            f.write(px.tobytes())
+    elif ext == ".pam":
+        with open(path, "wb") as f:
+            f.write(b"P7\nWIDTH %d\nHEIGHT %d\nDEPTH 4\nMAXVAL 255\nTUPLTYPE RGB_ALPHA\nENDHDR\n" % (w, h))
+            f.write(px.tobytes())
+    else:
+        sys.exit("output must be .pfm, .npy, .ppm or .pam")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("input")
     ap.add_argument("output")
     ap.add_argument("--threads", type=int, default=16)
     ap.add_argument("--reps", type=int, default=1)
+    ap.add_argument("--frames", action="store_true")
     a = ap.parse_args()
+    if a.frames and os.path.splitext(a.output)[1].lower() == ".pam":
+        sys.exit("--frames writes .pfm, .npy or .ppm")
     import torch
     from libjxl_amd import VarDctDecoder, abi
     L = abi.load_library()
     blob = open(a.input, "rb").read()
     info = abi.CodestreamInfo()
-    rc = L.jxlhip_codestream_basic_info(blob, len(blob), C.byref(info))
+    seq = abi.SequenceInfo()
+    if a.frames:
+        rc = L.jxlhip_codestream_sequence_info(blob, len(blob), C.byref(info), C.byref(seq))
+    else:
+        rc = L.jxlhip_codestream_basic_info(blob, len(blob), C.byref(info))
     if rc:
         sys.stderr.write(f"djxl_hip: {a.input}: {L.jxlhip_status_string(rc).decode()}\n")
         sys.exit(3 if rc == -7 else 1)
@@ -68,6 +97,25 @@ def main():
     else:
         out = torch.empty((h, w, 3), dtype=torch.float32, device="cuda")
         args = (1 | UNDO, None, out.data_ptr(), w * 12, 0)
+    if a.frames:
+        stem, cursor, t0 = os.path.splitext(a.output)[0], C.c_uint64(0), time.perf_counter()
+        for k in range(seq.num_displayed_frames):
+            fr = abi.SequenceFrame()
+            rc = L.jxlhip_decode_codestream_next(dec.ctx, runner, pool, blob, len(blob), C.byref(cursor), *args, C.byref(info),
+                                                 C.byref(fr))
+            if rc:
+                sys.stderr.write(f"djxl_hip: {a.input}: frame {k}: {L.jxlhip_status_string(rc).decode()}: "
+                                 f"{L.jxlhip_last_error(dec.ctx).decode()}\n")
+                sys.exit(3 if rc == -7 else 1)
+            write(f"{stem}-{k:03d}{ext}", ext, out.cpu().numpy(), w, h)
+            print(f"frame {k}: duration {fr.duration} tick(s), {fr.coded_frames} coded frame(s)" + (" (last)" if fr.is_last else ""))
+        dt = time.perf_counter() - t0
+        print(f"{w} x {h}, {seq.num_displayed_frames} frame(s) of {seq.num_coded_frames} coded, "
+              f"{w * h * seq.num_displayed_frames / dt / 1e6:.1f} MP/s [{a.threads} threads]")
+        dec.close()
+        if pool:
+            R.JxlThreadParallelRunnerDestroy(pool)
+        return
     best = None
     for _ in range(max(1, a.reps)):
         t0 = time.perf_counter()
@@ -78,23 +126,7 @@ def main():
                              f"{L.jxlhip_last_error(dec.ctx).decode()}\n")
             sys.exit(3 if rc == -7 else 1)
         best = dt if best is None else min(best, dt)
-    px = out.cpu().numpy()
-    if ext == ".npy":
-        np.save(a.output, px)
-    elif ext == ".pfm":
-        with open(a.output, "wb") as f:
-            f.write(b"PF\n%d %d\n-1.0\n" % (w, h))
-            f.write(np.ascontiguousarray(px[::-1]).astype("<f4").tobytes())
-    elif ext == ".ppm":
-        with open(a.output, "wb") as f:
-            f.write(b"P6\n%d %d\n255\n" % (w, h))
-            f.write(px.tobytes())
-    elif ext == ".pam":
-        with open(a.output, "wb") as f:
-            f.write(b"P7\nWIDTH %d\nHEIGHT %d\nDEPTH 4\nMAXVAL 255\nTUPLTYPE RGB_ALPHA\nENDHDR\n" % (w, h))
-            f.write(px.tobytes())
-    else:
-        sys.exit("output must be .pfm, .npy, .ppm or .pam")
+    write(a.output, ext, out.cpu().numpy(), w, h)
     print(f"{w} x {h}, {w * h / best / 1e6:.1f} MP/s [{a.reps} reps, {a.threads} threads], "
           f"{info.num_groups} groups, {info.num_passes} pass(es), coefficients "
           f"{'int16' if info.coeff_type == 0 else 'int32'}, epf_iters {info.epf_iters} gab {info.gab}")
