@@ -228,3 +228,61 @@ def make_param_case(xsize, ysize, name, revert=(), dequant=None, mix=None, gab=N
     if dequant is None:
         dequant = oracle.default_dequant_tables()
     return params, t, oracle_frame(params, t, dequant)
+
+
+# ---- the per-channel bar of the GPU tiers (test_gpu_frame_params.py, test_gpu_spectrum.py) ---------------------------
+TIGHT = 2e-5
+
+
+def per_channel_err(got, want, axis):
+    """max|got_c - want_c| / max(max|want_c|, 1e-3) for each channel c along `axis`."""
+    g = np.moveaxis(np.asarray(got, np.float64), axis, 0).reshape(3, -1)
+    w = np.moveaxis(np.asarray(want, np.float64), axis, 0).reshape(3, -1)
+    return np.abs(g - w).max(axis=1) / np.maximum(np.abs(w).max(axis=1), 1e-3)
+
+
+def check_channels(path, name, got, want, axis):
+    assert got.shape == want.shape
+    err = per_channel_err(got, want, axis)
+    print("WORST %s %s %.3e %.3e %.3e" % (path, name, *err))
+    assert (err <= TIGHT).all(), (path, name, err.tolist())
+
+
+# ---- bytes -> device: the hand-over scaffolding of the GPU tiers ------------------------------------------------------
+def entropy_decode_submit(dec, t, dequant_host, fr, threads, histo_sets=2):
+    """The frame `fr` (an oracle.Frame over the CPU tensors `t`) handed to the decoder `dec`, which has begun the
+    frame, as a front end does it: side info uploaded, the AC streams written by the REFERENCE's entropy encoder,
+    jxlhip_ac_group_decode_submit for the groups in any order on `threads` host threads (the JxlParallelRunner's
+    role).  Returns the pass handle: the caller destroys it (jxlhip_ac_pass_destroy) once it has decoded."""
+    import threading
+    glob, groups, used_acs, _ = fr.encode_ac_ref(histo_sets=histo_sets)
+    L = dec.L
+    npy = {k: ([x.numpy() for x in v] if isinstance(v, list) else v.numpy()) for k, v in t.items()}
+    dc3 = (C.c_void_p * 3)(*[x.ctypes.data for x in npy["dc"]])
+    assert L.jxlhip_upload_side_info(dec.ctx, npy["ac_strategy"].ctypes.data, npy["raw_quant"].ctypes.data,
+                                     npy["epf_sharpness"].ctypes.data, npy["ytox_map"].ctypes.data,
+                                     npy["ytob_map"].ctypes.data, dc3, dequant_host.ctypes.data) == 0
+    g = np.frombuffer(glob, np.uint8)
+    pos, h = C.c_size_t(0), C.c_void_p()
+    assert L.jxlhip_ac_pass_decode(g.ctypes.data, len(g), C.byref(pos), used_acs, histo_sets, None, C.byref(h)) == 0
+    assert L.jxlhip_ac_pass_max_num_bits(h) < 16  # int16 coefficients, as the frame was set up
+    ng = len(groups)
+    errs = []
+
+    def worker(tid, nthreads):
+        for gi in range(tid, ng, nthreads):
+            d = np.frombuffer(groups[gi], np.uint8)
+            gp = C.c_size_t(0)
+            rc = L.jxlhip_ac_group_decode_submit(dec.ctx, h, gi, npy["ac_strategy"].ctypes.data,
+                                                 npy["raw_quant"].ctypes.data, None, d.ctypes.data, len(d),
+                                                 C.byref(gp))
+            if rc != 0:
+                errs.append((gi, rc))
+
+    pool = [threading.Thread(target=worker, args=(i, threads)) for i in range(threads)]
+    for th in pool:
+        th.start()
+    for th in pool:
+        th.join()
+    assert not errs, errs
+    return h

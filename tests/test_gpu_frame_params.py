@@ -13,10 +13,11 @@ import pytest
 import torch
 
 import frames
+from frames import check_channels, per_channel_err  # noqa: F401  (shared with test_gpu_spectrum.py)
 
 pytestmark = pytest.mark.gpu
 
-TIGHT = 2e-5
+TIGHT = frames.TIGHT
 THREADS = min(16, os.cpu_count() or 1)
 SIZE = (520, 300)
 SETS = sorted(frames.PARAM_SETS)
@@ -37,20 +38,6 @@ def to_dev(t):
 
 def reference(ref, params, t):
     return frames.oracle_frame(params, t, ref.ref_default_dequant_tables()).decode_ref(threads=THREADS)
-
-
-def per_channel_err(got, want, axis):
-    """max|got_c - want_c| / max(max|want_c|, 1e-3) for each channel c along `axis`."""
-    g = np.moveaxis(np.asarray(got, np.float64), axis, 0).reshape(3, -1)
-    w = np.moveaxis(np.asarray(want, np.float64), axis, 0).reshape(3, -1)
-    return np.abs(g - w).max(axis=1) / np.maximum(np.abs(w).max(axis=1), 1e-3)
-
-
-def check_channels(path, name, got, want, axis):
-    assert got.shape == want.shape
-    err = per_channel_err(got, want, axis)
-    print("WORST %s %s %.3e %.3e %.3e" % (path, name, *err))
-    assert (err <= TIGHT).all(), (path, name, err.tolist())
 
 
 def decode(params, t, env, monkeypatch):

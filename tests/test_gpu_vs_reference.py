@@ -326,7 +326,6 @@ def test_entropy_decode_submit_end_to_end(dec, ref, sparse, monkeypatch):
     bit for bit -- and a later frame that is handed over DENSELY (jxlhip_submit_group) in the same context must not
     see the earlier frame's sparse groups."""
     import ctypes as C
-    import threading
     monkeypatch.setenv("JXLHIP_SPARSE_UPLOAD", sparse)
     xs, ys = 1000, 700
     params, t, fr = frames.make_case(xs, ys, mix=synth.MIX_D1, gab=True, epf_iters=1, seed=77)
@@ -336,39 +335,11 @@ def test_entropy_decode_submit_end_to_end(dec, ref, sparse, monkeypatch):
     want = dec.decode_frame().clone()
     dec.sync()
 
-    glob, groups, used_acs, _ = fr.encode_ac_ref(histo_sets=2)
     d2 = VarDctDecoder(0)
     d2.begin_frame(params)
     L = d2.L
-    npy = {k: ([x.numpy() for x in v] if isinstance(v, list) else v.numpy()) for k, v in t.items()}
     dqh = dq.cpu().numpy()
-    dc3 = (C.c_void_p * 3)(*[x.ctypes.data for x in npy["dc"]])
-    assert L.jxlhip_upload_side_info(d2.ctx, npy["ac_strategy"].ctypes.data, npy["raw_quant"].ctypes.data,
-                                     npy["epf_sharpness"].ctypes.data, npy["ytox_map"].ctypes.data,
-                                     npy["ytob_map"].ctypes.data, dc3, dqh.ctypes.data) == 0
-    g = np.frombuffer(glob, np.uint8)
-    pos, h = C.c_size_t(0), C.c_void_p()
-    assert L.jxlhip_ac_pass_decode(g.ctypes.data, len(g), C.byref(pos), used_acs, 2, None, C.byref(h)) == 0
-    assert L.jxlhip_ac_pass_max_num_bits(h) < 16  # int16 coefficients, as the frame was set up
-    ng = len(groups)
-    errs = []
-
-    def worker(tid, nthreads):  # the JxlParallelRunner's role: groups in any order, concurrently
-        for gi in range(tid, ng, nthreads):
-            d = np.frombuffer(groups[gi], np.uint8)
-            gp = C.c_size_t(0)
-            rc = L.jxlhip_ac_group_decode_submit(d2.ctx, h, gi, npy["ac_strategy"].ctypes.data,
-                                                 npy["raw_quant"].ctypes.data, None, d.ctypes.data, len(d),
-                                                 C.byref(gp))
-            if rc != 0:
-                errs.append((gi, rc))
-
-    threads = [threading.Thread(target=worker, args=(i, 12)) for i in range(12)]  # more threads than staging slots
-    for th in threads:
-        th.start()
-    for th in threads:
-        th.join()
-    assert not errs, errs
+    h = frames.entropy_decode_submit(d2, t, dqh, fr, threads=12)  # more threads than staging slots
     got = d2.decode_frame()
     d2.sync()
     L.jxlhip_ac_pass_destroy(h)
@@ -388,7 +359,7 @@ def test_entropy_decode_submit_end_to_end(dec, ref, sparse, monkeypatch):
     assert L.jxlhip_upload_side_info(d2.ctx, npy2["ac_strategy"].ctypes.data, npy2["raw_quant"].ctypes.data,
                                      npy2["epf_sharpness"].ctypes.data, npy2["ytox_map"].ctypes.data,
                                      npy2["ytob_map"].ctypes.data, dc3b, dqh.ctypes.data) == 0
-    for gi in range(ng):
+    for gi in range(((xs + 255) // 256) * ((ys + 255) // 256)):
         ptrs = (C.c_void_p * 3)(*[npy2["coeffs"][c][gi * 65536:].ctypes.data for c in range(3)])
         assert L.jxlhip_submit_group(d2.ctx, gi, ptrs, 65536) == 0
     got2 = d2.decode_frame()
