@@ -397,6 +397,41 @@ JXLHIP_EXPORT int jxlhip_set_blending(jxlhip_ctx* ctx, const jxlhip_blend_params
  * written when the slot holds no canvas. */
 JXLHIP_EXPORT int jxlhip_canvas_read(jxlhip_ctx* ctx, uint32_t slot, float* dev_out, size_t stride_floats, uint32_t* w,
                                      uint32_t* h);
+/* ---- tone mapping: a PQ original on a display dimmer than its mastering peak ----
+ * jxlhip_set_tone_mapping: the current frame is tone-mapped from orig_intensity_target to desired_intensity_target nits
+ * as the reference does behind JxlDecoderSetDesiredIntensityTarget: ToneMappingStage between the XYB stage and
+ * FromLinearStage (render_pipeline/stage_tone_mapping.cc, dec_cache.cc:300-318) = the Rec.2408 tone mapper followed by
+ * GamutMap with preserve_saturation 0.1 (cms/tone_mapping-inl.h).  Call it after jxlhip_frame_begin, which resets it;
+ * NULL switches it off.  luminances = the Y row of the DESTINATION primaries' RGB -> XYZ matrix
+ * (OutputEncodingInfo::luminances; jxlhip_output_opsin_matrix reports them); orig_transfer = the ORIGINAL's transfer
+ * function (JXLHIP_TF_*).  The destination transfer function is the frame's out_format.transfer, or linear for
+ * JXLHIP_OUT_LINEAR_RGB_F32.  With tone mapping on, jxlhip_decode_frame / _host / _pinned run the frame's whole path
+ * (patches, splines, upsampling and noise included) into context memory as planar XYB at output size, and one more
+ * launch, k_tone_map (JXLHIP_KERNEL_TONE_MAP), writes the caller's output: every format, dither, alpha.
+ * When desired >= orig, or the original's transfer function is neither PQ nor HLG, the call succeeds and the frame
+ * takes exactly its plain path: the reference adds no stage there.  Frames that never call this are untouched.
+ * JXLHIP_ERR_UNSUPPORTED (jxlhip_last_error names the case): an HLG original (the HlgOOTF branch of the stage),
+ * JXLHIP_OUT_XYB_PLANAR, multi-device contexts, stripes, undo_orientation > 1, a frame with jxlhip_set_blending (the
+ * reference tone-maps behind the blend, in linear light again; jxlhip_set_blending refuses a tone-mapped frame in
+ * turn), and the split calls on a tone-mapped frame.  JXLHIP_ERR_INVALID_ARGUMENT: a target that is not positive and
+ * finite, non-finite luminances, an orig_transfer outside the enum. */
+typedef struct jxlhip_tone_mapping {
+  float orig_intensity_target;    /* ImageMetadata::tone_mapping.intensity_target, nits */
+  float desired_intensity_target; /* the display's peak, nits */
+  float luminances[3];            /* of the destination primaries */
+  uint32_t orig_transfer;         /* JXLHIP_TF_* of the original */
+} jxlhip_tone_mapping;
+JXLHIP_EXPORT int jxlhip_set_tone_mapping(jxlhip_ctx* ctx, const jxlhip_tone_mapping* params);
+/* Host-side check of the tone mapper's constants: what k_tone_map would get in its launch arguments for `params` and a
+ * destination transfer function dest_transfer (JXLHIP_TF_*), computed as ToneMappingStage's constructor and
+ * Rec2408ToneMapperBase's member initialisers do, into out[0 .. n): to_intensity_target,
+ * from_desired_intensity_target, source peak, target peak, luminances[3], pq_mastering_min, pq_mastering_range,
+ * inv_pq_mastering_range, min_lum, max_lum, ks, inv_one_minus_ks, normalizer, inv_target_peak, 1 - ks,
+ * preserve_saturation (n <= JXLHIP_TONE_MAPPING_CONSTANTS = 18).  No device needed.  JXLHIP_ERR_INVALID_ARGUMENT as
+ * jxlhip_set_tone_mapping, and for a pair the stage is not built for (an original that is not PQ, desired >= orig). */
+#define JXLHIP_TONE_MAPPING_CONSTANTS 18
+JXLHIP_EXPORT int jxlhip_tone_mapping_constants(const jxlhip_tone_mapping* params, uint32_t dest_transfer, float* out,
+                                                size_t n);
 /* Host-side check of the noise generator's jump: the state (s0_[i], s1_[i]) of the 8 lanes of
  * Xorshift128Plus(visible_frame_index, nonvisible_frame_index, x0, y0) (lib/jxl/xorshift128plus-inl.h:46-57) after
  * `fills` calls of Fill, computed as the kernel does (one jump-matrix product, then single steps) into state[2 * i],
@@ -530,7 +565,8 @@ enum {
    * JXLHIP_KERNEL_COUNT with them; size arrays with JXLHIP_KERNEL_COUNT_EX and read with jxlhip_profile_read_ex */
   JXLHIP_KERNEL_PATCHES = 8,  /* patches (jxlhip_set_patches): k_patches behind the frame's path, in front of the splines */
   JXLHIP_KERNEL_BLEND = 9,    /* blending (jxlhip_set_blending): k_blend behind the frame's whole path */
-  JXLHIP_KERNEL_COUNT_EX = 10 /* every slot; grows with each new one (new slots are appended here only) */
+  JXLHIP_KERNEL_TONE_MAP = 10, /* tone mapping (jxlhip_set_tone_mapping): k_tone_map behind the frame's whole path */
+  JXLHIP_KERNEL_COUNT_EX = 11 /* every slot; grows with each new one (new slots are appended here only) */
 };
 /* A hint, not a contract: `frames_in_flight` = how many contexts the caller keeps busy on this device at the same time
  * (a pool of decoders over a queue of images; 1 = this context runs alone, the default).  It only moves the frame size

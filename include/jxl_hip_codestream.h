@@ -90,6 +90,35 @@ typedef struct jxlhip_codestream_info {
  * JXLHIP_ERR_UNSUPPORTED as the decode call would return them for the header part. */
 JXLHIP_EXPORT int jxlhip_codestream_basic_info(const uint8_t* data, size_t size, jxlhip_codestream_info* info);
 
+/* ---- the display: peak luminance and output primaries ----
+ * jxlhip_codestream_set_display: what JxlDecoderSetDesiredIntensityTarget and JxlDecoderSetOutputColorProfile (with an
+ * enumerated encoding) do for an XYB image, sticky on the context and read by jxlhip_decode_codestream, _extra and
+ * _next.  NULL resets; with nothing set every call behaves as before.
+ *   display_nits            0 = no tone mapping.  Otherwise info->intensity_target reports it (decode.cc:2247) and the
+ *                           frames of a PQ original brighter than it are tone-mapped (jxlhip_set_tone_mapping with the
+ *                           header's intensity target); other originals and dimmer ones take their plain path.
+ *   primaries, white_point  0 = the original's.  Otherwise JXLHIP_PRIM_SRGB / _2100 / _P3 and JXLHIP_WP_D65 / _E / _DCI:
+ *                           the inverse opsin matrix and the luminances are re-derived for that space
+ *                           (jxlhip_output_opsin_matrix on a copy of the header whose colour encoding names it, as
+ *                           OutputEncodingInfo::SetColorEncoding does, dec_xyb.cc:180-249); info->primaries, white_point
+ *                           and luminances then describe the output.  Host-only; works without tone mapping as well.
+ * The transfer function stays the caller's (out_format).  JXLHIP_ERR_INVALID_ARGUMENT: a negative or non-finite
+ * display_nits, a value outside the enums.  JXLHIP_ERR_UNSUPPORTED, from the decode call with the reason in
+ * jxlhip_last_error (from jxlhip_codestream_display_info in *why): custom xy as the requested space (refused by the
+ * setter itself), an ICC or a grey original with any field set, an HLG original with display_nits set, and a sequence
+ * frame that needs blending while display_nits is set (a plain full-frame animation works). */
+typedef struct jxlhip_display {
+  float display_nits;
+  uint32_t primaries;   /* JXLHIP_PRIM_*, 0 = the original's */
+  uint32_t white_point; /* JXLHIP_WP_*, 0 = the original's */
+} jxlhip_display;
+JXLHIP_EXPORT int jxlhip_codestream_set_display(jxlhip_ctx* ctx, const jxlhip_display* display);
+/* jxlhip_codestream_basic_info as the decode calls of a context with this display would report it (no device needed:
+ * jxlhip_codestream_basic_info takes no context and cannot see the sticky state).  A file only the sequence calls
+ * take (an animation, layers) is read as jxlhip_codestream_sequence_info reads it.  *why (may be NULL) = a static string naming the case when the call returns JXLHIP_ERR_UNSUPPORTED, else "". */
+JXLHIP_EXPORT int jxlhip_codestream_display_info(const uint8_t* data, size_t size, const jxlhip_display* display,
+                                                 jxlhip_codestream_info* info, const char** why);
+
 /* The original's ICC profile (JxlDecoderGetColorAsICCProfile(JXL_COLOR_PROFILE_TARGET_ORIGINAL), decode.cc:2411-2430)
  * of a .jxl file or bare codestream.  *icc_size = its size, 0 for an image with an enumerated colour encoding;
  * icc_capacity 0 only asks for the size, a capacity below the size is JXLHIP_ERR_INVALID_ARGUMENT. */

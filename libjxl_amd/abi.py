@@ -9,9 +9,11 @@ _RUNNER_SO = os.path.join(_HERE, "csrc", "libjxl_threads_hip.so")
 
 KERNEL_COUNT = 8
 KERNEL_NAMES = ["prepare", "blocks", "filters", "fused", "epf0", "noise", "splines", "upsample"]
-# jxlhip_profile_read_ex: the slots above, then those added since (JXLHIP_KERNEL_PATCHES = 8, JXLHIP_KERNEL_BLEND = 9)
-KERNEL_COUNT_EX = 10
-KERNEL_NAMES_EX = KERNEL_NAMES + ["patches", "blend"]
+# jxlhip_profile_read_ex: the slots above, then those added since (JXLHIP_KERNEL_PATCHES = 8, JXLHIP_KERNEL_BLEND = 9,
+# JXLHIP_KERNEL_TONE_MAP = 10)
+KERNEL_COUNT_EX = 11
+KERNEL_NAMES_EX = KERNEL_NAMES + ["patches", "blend", "tone_map"]
+TONE_MAPPING_CONSTANTS = 18  # JXLHIP_TONE_MAPPING_CONSTANTS
 # BlendMode (JXLHIP_BLEND_*) and jxlhip_blend_params::save_slot's "none"
 BLEND_REPLACE, BLEND_ADD, BLEND_BLEND, BLEND_ALPHA_WEIGHTED_ADD, BLEND_MUL = range(5)
 BLEND_NO_SAVE = 0xFFFFFFFF
@@ -42,6 +44,19 @@ class OutputFormat(C.Structure):
                 ("luminances", C.c_float * 3)]
 
 
+class ToneMapping(C.Structure):
+    """jxlhip_tone_mapping"""
+    _fields_ = [("orig_intensity_target", C.c_float), ("desired_intensity_target", C.c_float),
+                ("luminances", C.c_float * 3), ("orig_transfer", C.c_uint32)]
+
+
+class Display(C.Structure):
+    """jxlhip_display (include/jxl_hip_codestream.h)"""
+    _fields_ = [("display_nits", C.c_float), ("primaries", C.c_uint32), ("white_point", C.c_uint32)]
+
+
+PRIM_SRGB, PRIM_CUSTOM, PRIM_2100, PRIM_P3 = 1, 2, 9, 11
+WP_D65, WP_CUSTOM, WP_E, WP_DCI = 1, 2, 10, 11
 OUT_XYB_PLANAR, OUT_LINEAR_RGB_F32, OUT_PACKED = 0, 1, 2
 TF_LINEAR, TF_SRGB, TF_PQ, TF_709, TF_GAMMA, TF_HLG = 0, 1, 2, 3, 4, 5
 SAMPLE_F32, SAMPLE_U8, SAMPLE_U16, SAMPLE_F16 = 0, 1, 2, 3
@@ -263,7 +278,7 @@ EXPORTS = [
     "jxlhip_dequant_table_offset", "jxlhip_status_string", "jxlhip_create", "jxlhip_create_ex", "jxlhip_create_multi",
     "jxlhip_destroy", "jxlhip_last_error", "jxlhip_debug_reload_env", "jxlhip_set_stream",
     "jxlhip_frame_begin", "jxlhip_frame_set_inputs", "jxlhip_upload_side_info",
-    "jxlhip_submit_group", "jxlhip_set_alpha", "jxlhip_set_noise", "jxlhip_noise_rng_state", "jxlhip_set_splines", "jxlhip_set_upsampling", "jxlhip_set_reference_frame", "jxlhip_set_patches", "jxlhip_set_blending", "jxlhip_canvas_read", "jxlhip_profile_read_ex", "jxlhip_alpha_staging", "jxlhip_decode_blocks", "jxlhip_halo_rows",
+    "jxlhip_submit_group", "jxlhip_set_alpha", "jxlhip_set_noise", "jxlhip_noise_rng_state", "jxlhip_set_splines", "jxlhip_set_upsampling", "jxlhip_set_reference_frame", "jxlhip_set_patches", "jxlhip_set_blending", "jxlhip_set_tone_mapping", "jxlhip_tone_mapping_constants", "jxlhip_canvas_read", "jxlhip_profile_read_ex", "jxlhip_alpha_staging", "jxlhip_decode_blocks", "jxlhip_halo_rows",
     "jxlhip_halo_export", "jxlhip_halo_import", "jxlhip_decode_filters", "jxlhip_decode_filters_rows", "jxlhip_stripe_begin",
     "jxlhip_stripe_finish", "jxlhip_decode_frame",
     "jxlhip_decode_frame_host", "jxlhip_decode_frame_pinned",
@@ -287,7 +302,7 @@ EXPORTS = [
     # include/jxl_hip_codestream.h
     "jxlhip_codestream_basic_info", "jxlhip_decode_codestream", "jxlhip_decode_codestream_extra",
     "jxlhip_codestream_icc_profile", "jxlhip_codestream_phase_ms", "jxlhip_codestream_sequence_info",
-    "jxlhip_decode_codestream_next",
+    "jxlhip_decode_codestream_next", "jxlhip_codestream_set_display", "jxlhip_codestream_display_info",
 ]
 
 
@@ -354,6 +369,8 @@ def load_library():
     L.jxlhip_set_reference_frame.argtypes = [vp, u32, u32, u32, vp, sz, i32]
     L.jxlhip_set_patches.argtypes = [vp, vp]
     L.jxlhip_set_blending.argtypes = [vp, C.POINTER(BlendParams)]
+    L.jxlhip_set_tone_mapping.argtypes = [vp, C.POINTER(ToneMapping)]
+    L.jxlhip_tone_mapping_constants.argtypes = [C.POINTER(ToneMapping), u32, C.POINTER(C.c_float), sz]
     L.jxlhip_canvas_read.argtypes = [vp, u32, vp, sz, C.POINTER(u32), C.POINTER(u32)]
     L.jxlhip_profile_read_ex.argtypes = [vp, C.POINTER(C.c_float), C.POINTER(u32), u32]
     L.jxlhip_splines_quantized.argtypes = [vp, C.POINTER(u32), C.POINTER(sz), C.POINTER(i32), vp, vp, vp, vp]
@@ -417,6 +434,8 @@ def load_library():
     L.jxlhip_codestream_sequence_info.argtypes = [vp, sz, C.POINTER(CodestreamInfo), C.POINTER(SequenceInfo)]
     L.jxlhip_decode_codestream_next.argtypes = [vp, vp, vp, vp, sz, C.POINTER(C.c_uint64), u32, vp, vp, sz, sz,
                                                 C.POINTER(CodestreamInfo), C.POINTER(SequenceFrame)]
+    L.jxlhip_codestream_set_display.argtypes = [vp, C.POINTER(Display)]
+    L.jxlhip_codestream_display_info.argtypes = [vp, sz, C.POINTER(Display), C.POINTER(CodestreamInfo), C.POINTER(C.c_char_p)]
     L.jxlhip_codestream_phase_ms.argtypes = [vp, C.POINTER(C.c_double)]
     L.jxlhip_decode_codestream_extra.argtypes = [vp, vp, vp, vp, sz, u32, vp, vp, sz, sz, C.POINTER(vp), u32, sz,
                                                  C.POINTER(CodestreamInfo)]

@@ -167,7 +167,7 @@ void FillInfo(const ParsedHeaders& h, bool container, jxlhip_codestream_info* in
   info->ysize = h.ih.ysize;
   info->container = container ? 1u : 0u;
   info->orientation = h.ih.orientation;
-  info->intensity_target = h.ih.intensity_target;
+  info->intensity_target = h.display_nits > 0.0f ? h.display_nits : h.ih.intensity_target;  // (decode.cc:2247)
   info->bits_per_sample = h.ih.bit_depth.bits_per_sample;
   info->transfer_function = h.ih.color_encoding.all_default ? 13u : h.ih.color_encoding.transfer_function;
   info->primaries = h.ih.color_encoding.all_default ? 1u : h.ih.color_encoding.primaries;
@@ -183,6 +183,54 @@ void FillInfo(const ParsedHeaders& h, bool container, jxlhip_codestream_info* in
     info->alpha_premultiplied = h.extra[h.alpha_index].alpha_associated;
   }
   info->upsampling = h.fh.upsampling;
+}
+
+// jxlhip_codestream_set_display applied to the parsed headers: the matrix and luminances of the requested space, the
+// header's colour encoding naming it (FillInfo then describes the output), the display's peak.  *why names a refusal.
+int CheckDisplay(const jxlhip_display& d) {
+  if (!(d.display_nits >= 0.0f) || !std::isfinite(d.display_nits)) return JXLHIP_ERR_INVALID_ARGUMENT;
+  if (d.primaries == JXLHIP_PRIM_CUSTOM || d.white_point == JXLHIP_WP_CUSTOM) return JXLHIP_ERR_UNSUPPORTED;
+  if (d.primaries != 0 && d.primaries != JXLHIP_PRIM_SRGB && d.primaries != JXLHIP_PRIM_2100 && d.primaries != JXLHIP_PRIM_P3)
+    return JXLHIP_ERR_INVALID_ARGUMENT;
+  if (d.white_point != 0 && d.white_point != JXLHIP_WP_D65 && d.white_point != JXLHIP_WP_E && d.white_point != JXLHIP_WP_DCI)
+    return JXLHIP_ERR_INVALID_ARGUMENT;
+  return JXLHIP_OK;
+}
+int ApplyDisplay(const jxlhip_display& d, ParsedHeaders* h, const char** why) {
+  *why = "";
+  if (d.display_nits == 0.0f && d.primaries == 0 && d.white_point == 0) return JXLHIP_OK;
+  int rc = CheckDisplay(d);
+  if (rc) {
+    if (rc == JXLHIP_ERR_UNSUPPORTED) *why = "custom xy as the requested output space";
+    return rc;
+  }
+  jxlhip_color_encoding& ce = h->ih.color_encoding;
+  if (ce.want_icc) return *why = "a display set for an ICC original (the reference needs a CMS there)", JXLHIP_ERR_UNSUPPORTED;
+  if (!ce.all_default && ce.color_space == JXLHIP_CS_GRAY) return *why = "a display set for a grey original", JXLHIP_ERR_UNSUPPORTED;
+  if (ce.all_default) {  // spell the defaults out: sRGB, D65, relative intent
+    ce.all_default = 0;
+    ce.color_space = JXLHIP_CS_RGB;
+    ce.white_point = JXLHIP_WP_D65;
+    ce.primaries = JXLHIP_PRIM_SRGB;
+    ce.have_gamma = 0;
+    ce.transfer_function = 13;
+    ce.rendering_intent = 1;
+  }
+  if (d.display_nits > 0.0f && !ce.have_gamma && ce.transfer_function == 18)
+    return *why = "display_nits set for an HLG original (the HlgOOTF branch is not in the back-end)", JXLHIP_ERR_UNSUPPORTED;
+  if (d.primaries != 0 || d.white_point != 0) {
+    if (d.primaries) ce.primaries = d.primaries;
+    if (d.white_point) ce.white_point = d.white_point;
+    if ((rc = jxlhip_output_opsin_matrix(&h->ih, h->inv_matrix, h->luminances))) return rc;
+  }
+  h->display_nits = d.display_nits;
+  return JXLHIP_OK;
+}
+int ApplyDisplay(jxlhip_ctx* c, ParsedHeaders* h) {
+  const jxlhip_display d{c->display_nits, c->display_primaries, c->display_white_point};
+  const char* why = "";
+  const int rc = ApplyDisplay(d, h, &why);
+  return rc ? Fail(c, rc, "%s", why[0] ? why : "the display cannot be applied to this image") : JXLHIP_OK;
 }
 
 // The Modular parts of the AC-group sections on the runner (extra channels; FrameDecoder::ProcessACGroup's second
@@ -463,6 +511,55 @@ int jxlhip_codestream_basic_info(const uint8_t* data, size_t size, jxlhip_codest
   return JXLHIP_OK;
 }
 
+int jxlhip_codestream_set_display(jxlhip_ctx* c, const jxlhip_display* d) {
+  if (!c) return JXLHIP_ERR_INVALID_ARGUMENT;
+  JXLHIP_NO_MULTI(c);
+  if (d) {
+    const int rc = CheckDisplay(*d);
+    if (rc == JXLHIP_ERR_UNSUPPORTED) return Fail(c, rc, "custom xy as the requested output space");
+    if (rc) return Fail(c, rc, "display: %g nits, primaries %u, white point %u", d->display_nits, d->primaries, d->white_point);
+  }
+  c->display_nits = d ? d->display_nits : 0.0f;
+  c->display_primaries = d ? d->primaries : 0;
+  c->display_white_point = d ? d->white_point : 0;
+  return JXLHIP_OK;
+}
+
+namespace {
+void FillSequenceInfo(Sequence& s, bool container, jxlhip_codestream_info* info, jxlhip_sequence_info* seq);
+}
+
+int jxlhip_codestream_display_info(const uint8_t* data, size_t size, const jxlhip_display* display, jxlhip_codestream_info* info,
+                                   const char** why_out) {
+  const char* why = "";
+  if (why_out) *why_out = why;
+  if (!data || !info) return JXLHIP_ERR_INVALID_ARGUMENT;
+  std::vector<uint8_t> storage;
+  const uint8_t* cs = nullptr;
+  size_t n = 0;
+  bool container = false;
+  int rc = ExtractCodestream(data, size, &storage, &cs, &n, &container);
+  if (rc) return rc;
+  // a single-frame file as jxlhip_codestream_basic_info reads it; what that refuses, as the walk of the sequence calls does
+  try {
+    ParsedHeaders h;
+    Sequence s;
+    rc = ParseHeaders(cs, n, &h);
+    const bool sequence = rc == JXLHIP_ERR_UNSUPPORTED;
+    if (sequence && (rc = WalkSequence(cs, n, &s)) == JXLHIP_ERR_UNSUPPORTED) why = s.h.why;
+    if (!rc && display) rc = ApplyDisplay(*display, sequence ? &s.h : &h, &why);
+    if (rc) {
+      if (why_out) *why_out = why;
+      return rc;
+    }
+    if (sequence) FillSequenceInfo(s, container, info, nullptr);
+    else FillInfo(h, container, info);
+  } catch (const std::bad_alloc&) {
+    return JXLHIP_ERR_OUT_OF_MEMORY;
+  }
+  return JXLHIP_OK;
+}
+
 int jxlhip_codestream_icc_profile(const uint8_t* data, size_t size, uint8_t* icc, size_t icc_capacity, size_t* icc_size) {
   if (!data || !icc_size || (icc_capacity && !icc)) return JXLHIP_ERR_INVALID_ARGUMENT;
   *icc_size = 0;
@@ -578,6 +675,7 @@ static int DecodeCodestreamImpl(jxlhip_ctx* c, jxlhip_parallel_runner runner, vo
   ParsedHeaders h;
   if ((rc = ParseHeaders(cs, n, &h)))
     return Fail(c, rc, rc == JXLHIP_ERR_UNSUPPORTED ? (h.why[0] ? h.why : "stream uses features outside the VarDCT back-end") : "invalid headers");
+  if ((rc = ApplyDisplay(c, &h))) return rc;
   for (uint32_t slot = 0; slot < 4; slot++) {
     const ReferenceFrame& r = h.refs[slot];
     if (r.xsize == 0) continue;
@@ -1051,6 +1149,17 @@ static int DecodeFrameAt(jxlhip_ctx* c, const uint8_t* cs, size_t n, const Parse
   if (patches && (rc = jxlhip_set_patches(c, patches.get()))) return rc;
   if (splines && (rc = jxlhip_set_splines(c, splines.get()))) return rc;
   if (fc.blend && (rc = jxlhip_set_blending(c, fc.blend))) return rc;
+  if (h.display_nits > 0.0f) {  // JxlDecoderSetDesiredIntensityTarget: the stage exists for a PQ original brighter than the display
+    const jxlhip_color_encoding& ce = ih.color_encoding;
+    jxlhip_tone_mapping tm{};
+    tm.orig_intensity_target = ih.intensity_target;
+    tm.desired_intensity_target = h.display_nits;
+    for (int i = 0; i < 3; i++) tm.luminances[i] = h.luminances[i];
+    tm.orig_transfer = (!ce.all_default && !ce.have_gamma && ce.transfer_function == 16) ? JXLHIP_TF_PQ
+                       : (!ce.all_default && !ce.have_gamma && ce.transfer_function == 18) ? JXLHIP_TF_HLG
+                                                                                            : JXLHIP_TF_SRGB;
+    if ((rc = jxlhip_set_tone_mapping(c, &tm))) return rc;
+  }
   if ((rc = jxlhip_decode_frame(c, fc.out, fc.out_stride, fc.out_plane_stride))) return rc;
   if ((rc = jxlhip_sync(c))) return rc;
   clock.Mark(JXLHIP_PHASE_KERNELS);
@@ -1123,6 +1232,7 @@ int SequenceNextImpl(jxlhip_ctx* c, jxlhip_parallel_runner runner, void* runner_
   Sequence s;
   if ((rc = WalkSequence(cs, n, &s)))
     return Fail(c, rc, rc == JXLHIP_ERR_UNSUPPORTED ? (s.h.why[0] ? s.h.why : "stream uses features outside the VarDCT back-end") : "invalid headers");
+  if ((rc = ApplyDisplay(c, &s.h))) return rc;
   size_t i = 0;
   if (!start) {
     while (i < s.frames.size() && s.frames[i].header_bit / 8 != *cursor) i++;
@@ -1173,6 +1283,8 @@ int SequenceNextImpl(jxlhip_ctx* c, jxlhip_parallel_runner runner, void* runner_
       b.save_slot = f.save ? fh.save_as_reference : JXLHIP_BLEND_NO_SAVE;
       if (b.source > 3 || (f.save && fh.save_as_reference > 3)) return Fail(c, JXLHIP_ERR_BAD_STREAM, "blend source / save slot out of range");
       fc.blend = &b;
+      if (s.h.display_nits > 0.0f)
+        return Fail(c, JXLHIP_ERR_UNSUPPORTED, "a sequence frame that needs blending while display_nits is set (tone mapping behind a blend is not in the back-end)");
     }
     s.h.fh = fh;
     if ((rc = DecodeFrameAt(c, cs, n, s.h, fh, f.toc_bit, fc, clock, verbose, &info, nullptr))) return rc;

@@ -310,6 +310,14 @@ struct jxlhip_ctx {
   DevBuf<float> canvas[4];
   uint32_t canvas_w[4] = {0, 0, 0, 0}, canvas_h[4] = {0, 0, 0, 0};
   DevBuf<float> blend_stage;
+  // jxlhip_set_tone_mapping: the current frame is tone-mapped (frame_begin resets tm_on); tm_k = k_tone_map's constants,
+  // tm_planes = the frame's own output as planar XYB at output size in front of it (DecodeFrameToneMapped)
+  bool tm_on = false;
+  ToneMapConstants tm_k{};
+  DevBuf<float> tm_planes;
+  // jxlhip_codestream_set_display: sticky on the context (0 = not set), read by the whole-file decode calls
+  float display_nits = 0.0f;
+  uint32_t display_primaries = 0, display_white_point = 0;
   // jxlhip_decode_codestream_next: a sequence is open and this is the cursor the next call must bring
   bool seq_open = false;
   uint64_t seq_expect = 0;

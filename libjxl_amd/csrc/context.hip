@@ -355,6 +355,7 @@ int jxlhip_frame_begin(jxlhip_ctx* c, const jxlhip_frame_params* p) {
   c->patches_on = false;
   c->ups_factor = 1;
   c->blend_on = false;
+  c->tm_on = false;
   return JXLHIP_OK;
 }
 
@@ -736,6 +737,7 @@ int jxlhip_set_blending(jxlhip_ctx* c, const jxlhip_blend_params* b) {
   if (c->p.output_kind == JXLHIP_OUT_XYB_PLANAR)
     return Fail(c, JXLHIP_ERR_UNSUPPORTED, "blending with planar XYB output (canvases are frames saved after the colour transform)");
   if (c->fp.alpha) return Fail(c, JXLHIP_ERR_UNSUPPORTED, "blending on a frame with alpha (blending extra channels is not in the back-end)");
+  if (c->tm_on) return Fail(c, JXLHIP_ERR_UNSUPPORTED, "blending on a tone-mapped frame (tone mapping behind a blend is not in the back-end)");
   if (b->image_xsize == 0 || b->image_ysize == 0 || b->image_xsize > (1u << 19) || b->image_ysize > (1u << 19))
     return Fail(c, JXLHIP_ERR_INVALID_ARGUMENT, "image size %ux%u out of range", b->image_xsize, b->image_ysize);
   if (b->x0 < -(1 << 30) || b->x0 > (1 << 30) || b->y0 < -(1 << 30) || b->y0 > (1 << 30))
@@ -758,6 +760,56 @@ int jxlhip_canvas_read(jxlhip_ctx* c, uint32_t slot, float* dev_out, size_t stri
   HIPCHK(c, hipSetDevice(c->device));
   HIPCHK(c, hipMemcpy2DAsync(dev_out, stride_floats * sizeof(float), c->canvas[slot], CanvasStride(*w) * sizeof(float),
                              3 * (size_t)*w * sizeof(float), *h, hipMemcpyDeviceToDevice, c->stream));
+  return JXLHIP_OK;
+}
+
+// ToneMappingStage's constructor for `t` (stage_tone_mapping.cc:33-64): 1 = the Rec.2408 tone mapper is built, 0 = no
+// stage (the frame's plain path), else the error (with its reason in c->err when c is given)
+static int ToneMappingKind(jxlhip_ctx* c, const jxlhip_tone_mapping* t) {
+  if (!(t->orig_intensity_target > 0.0f) || !(t->desired_intensity_target > 0.0f) || !std::isfinite(t->orig_intensity_target) ||
+      !std::isfinite(t->desired_intensity_target))
+    return Fail(c, JXLHIP_ERR_INVALID_ARGUMENT, "tone mapping: intensity targets %g -> %g", t->orig_intensity_target,
+                t->desired_intensity_target);
+  for (int i = 0; i < 3; i++)
+    if (!std::isfinite(t->luminances[i])) return Fail(c, JXLHIP_ERR_INVALID_ARGUMENT, "tone mapping: luminance %d is not finite", i);
+  if (t->orig_transfer > JXLHIP_TF_HLG) return Fail(c, JXLHIP_ERR_INVALID_ARGUMENT, "tone mapping: orig_transfer %u", t->orig_transfer);
+  if (t->desired_intensity_target == t->orig_intensity_target) return 0;
+  if (t->orig_transfer == JXLHIP_TF_PQ) return t->desired_intensity_target < t->orig_intensity_target ? 1 : 0;
+  if (t->orig_transfer == JXLHIP_TF_HLG)
+    return Fail(c, JXLHIP_ERR_UNSUPPORTED, "tone mapping of an HLG original (the HlgOOTF branch is not in the back-end)");
+  return 0;
+}
+
+// Tone mapping of the current frame (JxlDecoderSetDesiredIntensityTarget): recorded here, carried out by
+// DecodeFrameToneMapped; frame_begin resets to "not tone-mapped".
+int jxlhip_set_tone_mapping(jxlhip_ctx* c, const jxlhip_tone_mapping* t) {
+  if (!c) return JXLHIP_ERR_INVALID_ARGUMENT;
+  if (c->multi) return Fail(c, JXLHIP_ERR_UNSUPPORTED, "tone mapping on a multi-device context");
+  if (!c->have_frame) return Fail(c, JXLHIP_ERR_STATE, "set_tone_mapping before frame_begin");
+  c->tm_on = false;
+  if (!t) return JXLHIP_OK;
+  const int kind = ToneMappingKind(c, t);
+  if (kind <= 0) return kind;
+  if (c->f.group_y0 != 0 || c->f.group_rows != c->f.ysg) return Fail(c, JXLHIP_ERR_UNSUPPORTED, "tone mapping with stripes");
+  if (c->p.undo_orientation > 1)
+    return Fail(c, JXLHIP_ERR_UNSUPPORTED, "tone mapping with undo_orientation %u", c->p.undo_orientation);
+  if (c->p.output_kind == JXLHIP_OUT_XYB_PLANAR)
+    return Fail(c, JXLHIP_ERR_UNSUPPORTED, "tone mapping with planar XYB output (the stage works on linear RGB)");
+  if (c->blend_on)
+    return Fail(c, JXLHIP_ERR_UNSUPPORTED, "tone mapping on a blended frame (tone mapping behind a blend is not in the back-end)");
+  const bool dest_pq = c->p.output_kind == JXLHIP_OUT_PACKED && c->p.out_format.transfer == JXLHIP_TF_PQ;
+  ToneMapHostConstants(t->orig_intensity_target, t->desired_intensity_target, t->luminances, dest_pq, &c->tm_k);
+  c->tm_on = true;
+  return JXLHIP_OK;
+}
+
+int jxlhip_tone_mapping_constants(const jxlhip_tone_mapping* t, uint32_t dest_transfer, float* out, size_t n) {
+  if (!t || !out || n > kToneMapConstants || dest_transfer > JXLHIP_TF_HLG) return JXLHIP_ERR_INVALID_ARGUMENT;
+  const int kind = ToneMappingKind(nullptr, t);
+  if (kind != 1) return JXLHIP_ERR_INVALID_ARGUMENT;
+  ToneMapConstants k;
+  ToneMapHostConstants(t->orig_intensity_target, t->desired_intensity_target, t->luminances, dest_transfer == JXLHIP_TF_PQ, &k);
+  memcpy(out, &k, n * sizeof(float));
   return JXLHIP_OK;
 }
 
@@ -1054,7 +1106,8 @@ int jxlhip::PrepareAhead(jxlhip_ctx* c, bool render_stages) {
   // changes the output kind -- prepares again: correct, and one launch.
   const bool stripe = c->f.group_y0 != 0 || c->f.group_rows != c->f.ysg;
   const uint32_t kind = c->p.output_kind;
-  if (render_stages || c->noise_on || c->splines_on || c->patches_on || c->ups_factor > 1) c->p.output_kind = JXLHIP_OUT_XYB_PLANAR;  // as DecodeFrameFeatures
+  if (render_stages || c->noise_on || c->splines_on || c->patches_on || c->ups_factor > 1 || c->tm_on)
+    c->p.output_kind = JXLHIP_OUT_XYB_PLANAR;  // as DecodeFrameFeatures / DecodeFrameToneMapped
   const int fused = WantFused(c) ? (stripe ? 2 : 1) : 0;
   c->p.output_kind = kind;
   int block;
@@ -1150,6 +1203,7 @@ int jxlhip_decode_filters_rows(jxlhip_ctx* c, void* out, size_t out_stride, size
   if (c->ups_factor > 1)
     return Fail(c, JXLHIP_ERR_UNSUPPORTED, "upsampling with the split calls (jxlhip_decode_frame takes it)");
   if (c->blend_on) return Fail(c, JXLHIP_ERR_UNSUPPORTED, "blending with the split calls (jxlhip_decode_frame takes it)");
+  if (c->tm_on) return Fail(c, JXLHIP_ERR_UNSUPPORTED, "tone mapping with the split calls (jxlhip_decode_frame takes it)");
   int rc = CheckOutArgs(c, out, out_stride, out_plane_stride, c->f.xsize, c->f.y1 - c->f.y0);
   if (rc) return rc;
   HIPCHK(c, hipSetDevice(c->device));
@@ -1201,11 +1255,13 @@ int jxlhip_stripe_finish(jxlhip_ctx* c, const float* recv_up, const float* recv_
 static int DecodeFrameCoded(jxlhip_ctx* c, void* out, size_t out_stride, size_t out_plane_stride);
 static int DecodeFrameFeatures(jxlhip_ctx* c, void* out, size_t out_stride, size_t out_plane_stride);
 static int DecodeFrameBlended(jxlhip_ctx* c, void* out, size_t out_stride);
+static int DecodeFrameToneMapped(jxlhip_ctx* c, void* out, size_t out_stride);
 
 int jxlhip_decode_frame(jxlhip_ctx* c, void* out, size_t out_stride, size_t out_plane_stride) {
   if (!c) return JXLHIP_ERR_INVALID_ARGUMENT;
   if (c->multi) return out ? MultiDecodeFrame(c, out, nullptr, out_stride, out_plane_stride) : JXLHIP_ERR_INVALID_ARGUMENT;
   if (!c->have_frame) return Fail(c, JXLHIP_ERR_STATE, "decode needs frame_begin + inputs");
+  if (c->tm_on) return DecodeFrameToneMapped(c, out, out_stride);
   if (c->blend_on) return DecodeFrameBlended(c, out, out_stride);
   if (c->noise_on || c->splines_on || c->patches_on || c->ups_factor > 1) return DecodeFrameFeatures(c, out, out_stride, out_plane_stride);
   if (c->p.undo_orientation <= 1) return DecodeFrameCoded(c, out, out_stride, out_plane_stride);
@@ -1508,6 +1564,49 @@ static int DecodeFrameBlended(jxlhip_ctx* c, void* out, size_t out_stride) {
       c->ref_serial++;
     }
   }
+  return JXLHIP_OK;
+}
+
+// A tone-mapped frame (jxlhip_set_tone_mapping): the frame's whole path -- DecodeFrameCoded or DecodeFrameFeatures,
+// whatever it would take without tone mapping -- writes planar XYB at output size into tm_planes, and k_tone_map
+// (kernels_tonemap.hip) writes the caller's output from that.
+static int DecodeFrameToneMapped(jxlhip_ctx* c, void* out, size_t out_stride) {
+  const DevFrame& f = c->f;
+  // (set_tone_mapping has checked these; set_blending refuses a tone-mapped frame)
+  if (f.group_y0 != 0 || f.group_rows != f.ysg || c->p.undo_orientation > 1 || c->p.output_kind == JXLHIP_OUT_XYB_PLANAR || c->blend_on)
+    return Fail(c, JXLHIP_ERR_UNSUPPORTED, "tone mapping needs a whole unblended frame in coded orientation and an interleaved output");
+  const uint32_t W = (uint32_t)OutCols(c), H = (uint32_t)OutRows(c);
+  int rc = CheckOutArgs(c, out, out_stride, 0, W, H);
+  if (rc) return rc;
+  HIPCHK(c, hipSetDevice(c->device));
+  const uint32_t ns = (W + 63u) & ~63u;
+  const size_t nplane = (size_t)ns * H;
+  if (3 * nplane > 0xFFFFFFFFull)
+    return Fail(c, JXLHIP_ERR_UNSUPPORTED, "tone mapping of a frame whose three planes exceed 2^32 samples (k_tone_map indexes with 32 bits)");
+  if (3 * nplane > c->tm_planes.n && Capturing(c->stream))  // (a synchronise and an allocation)
+    return Fail(c, JXLHIP_ERR_UNSUPPORTED, "tone mapping while the stream is being captured and its planes have to grow");
+  if ((rc = c->tm_planes.Reserve(c, 3 * nplane))) return rc;
+  const uint32_t kind = c->p.output_kind;
+  c->p.output_kind = JXLHIP_OUT_XYB_PLANAR;
+  rc = c->noise_on || c->splines_on || c->patches_on || c->ups_factor > 1 ? DecodeFrameFeatures(c, c->tm_planes, ns, nplane)
+                                                                         : DecodeFrameCoded(c, c->tm_planes, ns, nplane);
+  c->p.output_kind = kind;
+  if (rc) return rc;
+  ToneMapArgs A{};
+  A.xsize = W;
+  A.ysize = H;
+  A.xyb = c->tm_planes;
+  A.ns = ns;
+  A.nplane = (uint32_t)nplane;
+  A.k = c->tm_k;
+  FilterParams fp = c->fp;
+  fp.out = out;
+  fp.out_stride = out_stride;
+  fp.out_plane_stride = 0;
+  ProfBegin(c);
+  if (!LaunchToneMap(A, fp, (int)kind, c->stream)) return Fail(c, JXLHIP_ERR_INVALID_ARGUMENT, "tone map launch arguments");
+  ProfMark(c, JXLHIP_KERNEL_TONE_MAP);
+  HIPCHK(c, hipGetLastError());
   return JXLHIP_OK;
 }
 

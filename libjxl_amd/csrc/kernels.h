@@ -219,6 +219,34 @@ struct BlendArgs {
 // kind, op or region.
 bool LaunchBlend(const BlendArgs& A, const FilterParams& p, int output_kind, hipStream_t st);
 
+// Tone mapping (kernels_tonemap.hip).  What ToneMappingStage's constructor and Rec2408ToneMapperBase's member
+// initialisers compute for a PQ original (stage_tone_mapping.cc:43-63, cms/tone_mapping.h:82-97), in the order
+// jxlhip_tone_mapping_constants reports them.
+struct ToneMapConstants {
+  float to_intensity_target, from_desired_intensity_target;  // 10000 / orig and desired / 10000 for a PQ destination, else 1
+  float source_peak, target_peak;                            // source_range_[1], target_range_[1]
+  float lum[3];                                              // the destination primaries' luminances
+  float pq_mastering_min, pq_mastering_range, inv_pq_mastering_range;
+  float min_lum, max_lum, ks, inv_one_minus_ks;
+  float normalizer, inv_target_peak;
+  float one_minus_ks;                                        // 1 - ks, which P evaluates per call
+  float preserve_saturation;                                 // GamutMap's default, 0.1
+};
+constexpr uint32_t kToneMapConstants = sizeof(ToneMapConstants) / sizeof(float);  // 18
+struct ToneMapArgs {
+  uint32_t xsize, ysize;  // the frame at output size
+  const float* xyb;       // 3 planes, ns floats per row (even, >= xsize rounded up to 2), nplane floats apart (even); 8-byte aligned
+  uint32_t ns;
+  uint32_t nplane;        // 3 * nplane < 2^32: the kernel indexes with 32 bits
+  ToneMapConstants k;
+};
+// host: the constants for a PQ original of `orig` nits shown at `desired` nits (desired < orig); dest_pq: the
+// destination transfer function is PQ
+void ToneMapHostConstants(float orig, float desired, const float luminances[3], bool dest_pq, ToneMapConstants* k);
+// k_tone_map: XYB -> linear RGB, the tone mapper, the gamut map and the output tail of `output_kind`
+// (JXLHIP_OUT_LINEAR_RGB_F32 / JXLHIP_OUT_PACKED) into p.out.  False for another kind or bad geometry.
+bool LaunchToneMap(const ToneMapArgs& A, const FilterParams& p, int output_kind, hipStream_t st);
+
 // Upsampling (kernels_upsample.hip).  The coded frame is cut into 64 x 16 tiles; every coded pixel gives n x n output
 // pixels, each a 25-tap sum over its 5 x 5 neighbourhood clamped to the neighbourhood's range.
 struct UpsampleArgs {

@@ -32,6 +32,7 @@ struct ParsedHeaders {
   float inv_matrix[9];   // inverse opsin matrix into the ORIGINAL colour space (unscaled), jxlhip_output_opsin_matrix
   float luminances[3];   // luminance weights of that space
   size_t icc_size;       // size of the original's ICC profile (0 = an enumerated colour encoding)
+  float display_nits = 0.0f;  // jxlhip_codestream_set_display: the display's peak when the frames are tone-mapped to it (0: not)
 };
 
 // the image header, the ICC profile, the extra channels' eligibility and the colour set-up; *pos_out = the first frame

@@ -226,6 +226,31 @@ class VarDctDecoder:
         _check(self.L, self.ctx, self.L.jxlhip_set_blending(self.ctx, C.byref(b)), "set_blending")
         self.image_size = (b.image_xsize, b.image_ysize)
 
+    def set_tone_mapping(self, orig_nits, desired_nits=None, luminances=(0.2126, 0.7152, 0.0722), orig_transfer=abi.TF_PQ):
+        """Tone mapping of the current frame, jxlhip_set_tone_mapping: an original mastered at orig_nits (transfer
+        function orig_transfer, abi.TF_*) shown on a display of desired_nits, luminances = those of the OUTPUT
+        primaries.  Call it after begin_frame, which resets it; None instead of orig_nits switches it off.  A display at
+        least as bright as the original leaves the frame on its plain path."""
+        if orig_nits is None:
+            _check(self.L, self.ctx, self.L.jxlhip_set_tone_mapping(self.ctx, None), "set_tone_mapping")
+            return
+        t = abi.ToneMapping(float(orig_nits), float(desired_nits), (C.c_float * 3)(*[float(v) for v in luminances]),
+                            int(orig_transfer))
+        _check(self.L, self.ctx, self.L.jxlhip_set_tone_mapping(self.ctx, C.byref(t)), "set_tone_mapping")
+
+    def set_display(self, display_nits=0.0, primaries=None, white_point=None):
+        """The display the whole-file decode calls render for, jxlhip_codestream_set_display (sticky on the context):
+        display_nits = its peak luminance (0: no tone mapping), primaries = "srgb" | "p3" | "rec2100" | abi.PRIM_* |
+        None (the original's), white_point = abi.WP_* | None (D65 when primaries are named, else the original's).
+        set_display() with nothing resets."""
+        prim = {None: 0, "srgb": abi.PRIM_SRGB, "p3": abi.PRIM_P3, "rec2100": abi.PRIM_2100}.get(primaries, primaries)
+        wp = int(white_point) if white_point else (abi.WP_D65 if prim else 0)
+        if not display_nits and not prim and not wp:
+            _check(self.L, self.ctx, self.L.jxlhip_codestream_set_display(self.ctx, None), "set_display")
+            return
+        d = abi.Display(float(display_nits), int(prim), wp)
+        _check(self.L, self.ctx, self.L.jxlhip_codestream_set_display(self.ctx, C.byref(d)), "set_display")
+
     def read_canvas(self, slot):
         """The canvas of slot 0..3 (a frame saved by set_blending's save_slot) as a float32 CUDA tensor [ysize, xsize, 3]
         in the transfer function of the frames that made it; None when the slot holds no canvas."""

@@ -1,5 +1,6 @@
 #!/usr/bin/env python3
-"""djxl_hip.py IN.jxl OUT.{pfm,npy,ppm,pam} [--threads N] [--reps K] [--frames]
+"""djxl_hip.py IN.jxl OUT.{pfm,npy,ppm,pam} [--threads N] [--reps K] [--frames] [--display_nits N]
+                                            [--output_primaries {srgb,p3,rec2100}]
 
 Decodes a .jxl file (container or bare codestream, one VarDCT still frame) on an MI355X through
 jxlhip_decode_codestream (include/jxl_hip_codestream.h) and writes the pixels the way djxl does for these
@@ -15,7 +16,12 @@ writes for screenshots and text) are rendered on the device.  Streams outside th
 wrapper can fall back to libjxl's djxl.  Prints Mpx/s of the decode call like djxl's SpeedStats.
 --frames: animations, layers, cropped and blended frames through jxlhip_decode_codestream_next: one file per DISPLAYED
 frame, OUT-000.ext, OUT-001.ext ... (coalesced, like djxl); the frames are blended on the device in the encoding of the
-output: the original's for .ppm (what the reference blends in), linear light for .pfm / .npy.  No alpha (.pam)."""
+output: the original's for .ppm (what the reference blends in), linear light for .pfm / .npy.  No alpha (.pam).
+--display_nits N: the display's peak luminance, djxl's flag of that name (JxlDecoderSetDesiredIntensityTarget): a PQ
+original mastered brighter is tone-mapped to it on the device (jxlhip_codestream_set_display).
+--output_primaries: the pixels in these primaries (D65) instead of the original's, as JxlDecoderSetOutputColorProfile
+with an enumerated encoding gives them; the transfer function stays the original's (its PQ curve keeps the
+original's intensity target, as the reference's does)."""
 import argparse
 import ctypes as C
 import os
@@ -53,6 +59,8 @@ def main():
     ap.add_argument("--threads", type=int, default=16)
     ap.add_argument("--reps", type=int, default=1)
     ap.add_argument("--frames", action="store_true")
+    ap.add_argument("--display_nits", type=float, default=0.0)
+    ap.add_argument("--output_primaries", choices=["srgb", "p3", "rec2100"])
     a = ap.parse_args()
     if a.frames and os.path.splitext(a.output)[1].lower() == ".pam":
         sys.exit("--frames writes .pfm, .npy or .ppm")
@@ -69,6 +77,16 @@ def main():
     if rc:
         sys.stderr.write(f"djxl_hip: {a.input}: {L.jxlhip_status_string(rc).decode()}\n")
         sys.exit(3 if rc == -7 else 1)
+    orig_nits = info.intensity_target  # (the PQ curve of the output keeps it, whatever the display's peak)
+    display = None
+    if a.display_nits or a.output_primaries:
+        display = abi.Display(a.display_nits, {None: 0, "srgb": 1, "rec2100": 9, "p3": 11}[a.output_primaries],
+                              1 if a.output_primaries else 0)
+        why = C.c_char_p()
+        rc = L.jxlhip_codestream_display_info(blob, len(blob), C.byref(display), C.byref(info), C.byref(why))
+        if rc:
+            sys.stderr.write(f"djxl_hip: {a.input}: {L.jxlhip_status_string(rc).decode()}: {(why.value or b'').decode()}\n")
+            sys.exit(3 if rc == -7 else 1)
     ext = os.path.splitext(a.output)[1].lower()
     packed = ext in (".ppm", ".pam")
     R = C.CDLL(abi.runner_library_path())
@@ -78,6 +96,8 @@ def main():
     pool = R.JxlThreadParallelRunnerCreate(None, a.threads) if a.threads else None
     runner = C.cast(R.JxlThreadParallelRunner, C.c_void_p) if a.threads else None
     dec = VarDctDecoder(0)
+    if display is not None:
+        dec.set_display(a.display_nits, a.output_primaries)
     w, h = info.xsize, info.ysize
     if info.orientation >= 5:  # display orientation like djxl (JXLHIP_OUT_UNDO_ORIENTATION): transposed frame
         w, h = h, w
@@ -89,8 +109,8 @@ def main():
         if info.gamma > 0:
             tf, par = 4, info.gamma
         else:
-            tf, par = {8: (0, 0.0), 13: (1, 0.0), 16: (2, info.intensity_target), 1: (3, 0.0), 17: (4, 1 / 2.6),
-                       18: (5, info.intensity_target)}.get(info.transfer_function, (1, 0.0))
+            tf, par = {8: (0, 0.0), 13: (1, 0.0), 16: (2, orig_nits), 1: (3, 0.0), 17: (4, 1 / 2.6),
+                       18: (5, orig_nits)}.get(info.transfer_function, (1, 0.0))
         fmt = abi.OutputFormat(tf, 1, nc, 8, 0, par, info.luminances)
         out = torch.empty((h, w, nc), dtype=torch.uint8, device="cuda")
         args = (2 | UNDO, C.byref(fmt), out.data_ptr(), w * nc, 0)
