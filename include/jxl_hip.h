@@ -370,8 +370,8 @@ JXLHIP_EXPORT int jxlhip_set_upsampling(jxlhip_ctx* ctx, uint32_t factor, const 
  * A full-size kReplace frame at the origin with no save slot launches exactly what it does without this call.
  * JXLHIP_ERR_UNSUPPORTED: multi-device contexts, stripes, undo_orientation > 1, JXLHIP_OUT_XYB_PLANAR, a stream that is
  * being captured into a graph (canvas and staging memory may have to grow), a frame with
- * jxlhip_set_alpha (blending and saving extra channels is not in the back-end; jxlhip_set_alpha refuses a blended
- * frame in turn), and the split calls on a blended frame.  JXLHIP_ERR_INVALID_ARGUMENT: a bad mode or slot, a source
+ * jxlhip_set_alpha (the extra channels of a blended frame go through jxlhip_set_blending_extra; jxlhip_set_alpha
+ * refuses a blended frame in turn), and the split calls on a blended frame.  JXLHIP_ERR_INVALID_ARGUMENT: a bad mode or slot, a source
  * slot that holds an XYB frame ("Trying to blend XYB reference frame"), a source canvas smaller than the image (neither
  * is looked at for a full-size kReplace frame at the origin, which never reads its source), and
  * save_slot == source with a source canvas of another size than the image. */
@@ -397,6 +397,59 @@ JXLHIP_EXPORT int jxlhip_set_blending(jxlhip_ctx* ctx, const jxlhip_blend_params
  * written when the slot holds no canvas. */
 JXLHIP_EXPORT int jxlhip_canvas_read(jxlhip_ctx* ctx, uint32_t slot, float* dev_out, size_t stride_floats, uint32_t* w,
                                      uint32_t* h);
+/* ---- blending on an image with extra channels (alpha, depth, ...) ----
+ * jxlhip_set_blending_extra: the frame named by the jxlhip_set_blending call in front of it belongs to an image with
+ * 1..4 extra channels.  They are blended beside the colour and saved with it: a canvas slot then also holds one planar
+ * float plane per extra channel, of the canvas's size, allocated, replaced and cleared with it (an XYB reference frame
+ * stored in the slot drops them too).  Per canvas pixel inside the frame's rectangle, in the reference's order
+ * (PerformBlending, blending.cc:42-190; alpha.cc:18-93): every extra channel is blended first, with its own mode,
+ * alpha_channel and clamp over the plane of its own `source` slot (zeroes when that slot has none), always from the
+ * alpha values of BEFORE the blend: kReplace fg, kAdd bg + fg, kMul bg * fg (fg clamped to [0, 1] with the flag), kBlend
+ * PerformAlphaBlending's single-channel form (a channel that is its own alpha channel becomes
+ * 1 - (1 - fa) * (1 - bga)), kAlphaWeightedAdd bg + fg * fa (its own alpha channel: bg unchanged).  Then the colour,
+ * with jxlhip_blend_params' mode, clamp and source and color_alpha_channel here: kBlend and kAlphaWeightedAdd use that
+ * channel's alpha (its background from that channel's own source slot), premultiplied or straight by that channel's
+ * alpha_associated; a new alpha <= 0 gives black; colour kBlend also writes the new alpha into that channel, over what
+ * the channel's own mode gave.  When no channel has is_alpha set, colour kBlend is fg and kAlphaWeightedAdd bg + fg, as
+ * without this call.  Outside the rectangle every channel is its own background.  Every operation is float32 in the
+ * reference's order, bit for bit.
+ * planes[i] = extra channel i of the frame at the FRAME's own size (jxlhip_frame_begin's xsize x ysize; what
+ * jxlhip_modular_extra_channel_f32 produces), host memory, stride_floats per row; they are uploaded by this call
+ * (like jxlhip_set_alpha's plane).  A 4-channel packed output takes its fourth sample from the blended plane of the
+ * first channel with is_alpha set (opaque without one).  jxlhip_frame_begin and every jxlhip_set_blending call reset
+ * it; a frame without it behaves exactly as before.
+ * JXLHIP_ERR_STATE without jxlhip_set_blending in force.  JXLHIP_ERR_INVALID_ARGUMENT: num_extra_channels outside
+ * 1..4, a mode above kMul, an alpha_channel or color_alpha_channel >= num_extra_channels, a source above 3, a NULL
+ * plane or a stride below the frame's width, a source slot that holds an XYB reference frame, a source canvas smaller
+ * than the image (neither is looked at for a full-size frame at the origin whose colour and extra channels all
+ * replace), and -- at jxlhip_decode_frame -- a save slot that is some channel's source with a canvas of another size
+ * or another number of extra channels.  JXLHIP_ERR_UNSUPPORTED: whatever jxlhip_set_blending refuses, a frame with
+ * jxlhip_set_alpha (neither needed nor allowed here), an upsampled frame, a frame with patches (extra channels of
+ * those stay outside the back-end), and a stream that is being captured when staging memory has to grow. */
+typedef struct jxlhip_blend_extra_channel {
+  uint32_t is_alpha;          /* ExtraChannelInfo::type == kAlpha */
+  uint32_t alpha_associated;  /* ExtraChannelInfo::alpha_associated: premultiplied */
+  uint32_t mode;              /* jxlhip_blend_mode: FrameHeader::extra_channel_blending_info[i].mode */
+  uint32_t alpha_channel;     /* ... .alpha_channel: index of the extra channel that is this one's alpha */
+  uint32_t clamp;             /* ... .clamp */
+  uint32_t source;            /* ... .source: slot 0..3 */
+} jxlhip_blend_extra_channel;
+typedef struct jxlhip_blend_extra_params {
+  uint32_t num_extra_channels;   /* 1..4 */
+  jxlhip_blend_extra_channel channel[4];
+  uint32_t color_alpha_channel;  /* FrameHeader::blending_info.alpha_channel */
+  const float* planes[4];        /* host planes of the frame's extra channels */
+  size_t stride_floats;
+} jxlhip_blend_extra_params;
+JXLHIP_EXPORT int jxlhip_set_blending_extra(jxlhip_ctx* ctx, const jxlhip_blend_extra_params* params);
+/* Reads plane `ec` (0..3) of the canvas of `slot` like jxlhip_canvas_read: device-to-device, stride_floats per row
+ * (>= width).  *w = *h = 0 and nothing written when the slot holds no canvas or its canvas no such plane. */
+JXLHIP_EXPORT int jxlhip_canvas_read_extra(jxlhip_ctx* ctx, uint32_t slot, uint32_t ec, float* dev_out, size_t stride_floats,
+                                           uint32_t* w, uint32_t* h);
+/* Reads the blended plane of extra channel `ec` of the current frame, at image size, after jxlhip_decode_frame with
+ * jxlhip_set_blending_extra in force: device-to-device, stride_floats per row (>= image_xsize), enqueued on the
+ * context's stream.  Valid until the next jxlhip_frame_begin; JXLHIP_ERR_STATE when the frame has no such plane. */
+JXLHIP_EXPORT int jxlhip_frame_extra_read(jxlhip_ctx* ctx, uint32_t ec, float* dev_out, size_t stride_floats);
 /* ---- tone mapping: a PQ original on a display dimmer than its mastering peak ----
  * jxlhip_set_tone_mapping: the current frame is tone-mapped from orig_intensity_target to desired_intensity_target nits
  * as the reference does behind JxlDecoderSetDesiredIntensityTarget: ToneMappingStage between the XYB stage and
@@ -566,7 +619,8 @@ enum {
   JXLHIP_KERNEL_PATCHES = 8,  /* patches (jxlhip_set_patches): k_patches behind the frame's path, in front of the splines */
   JXLHIP_KERNEL_BLEND = 9,    /* blending (jxlhip_set_blending): k_blend behind the frame's whole path */
   JXLHIP_KERNEL_TONE_MAP = 10, /* tone mapping (jxlhip_set_tone_mapping): k_tone_map behind the frame's whole path */
-  JXLHIP_KERNEL_COUNT_EX = 11 /* every slot; grows with each new one (new slots are appended here only) */
+  JXLHIP_KERNEL_BLEND_EC = 11, /* blending with extra channels (jxlhip_set_blending_extra): k_ec_blend in k_blend's place */
+  JXLHIP_KERNEL_COUNT_EX = 12 /* every slot; grows with each new one (new slots are appended here only) */
 };
 /* A hint, not a contract: `frames_in_flight` = how many contexts the caller keeps busy on this device at the same time
  * (a pool of decoders over a queue of images; 1 = this context runs alone, the default).  It only moves the frame size

@@ -29,7 +29,7 @@
  * jxlhip_decode_codestream_next below (blended on the device, jxlhip_set_blending); the single-frame calls refuse them.
  * Everything this front-end does not decode is refused with JXLHIP_ERR_UNSUPPORTED so that the caller can hand the
  * file to libjxl's CPU decoder: Modular-mode frames, animation / layers / any other sequence of frames (single-frame
- * calls; the sequence calls refuse frames that need blending on images with extra channels, VarDCT
+ * calls; the sequence calls blend images with extra channels too when asked to, and refuse VarDCT
  * reference-only frames, regular frames saved before the colour transform and kSkipProgressive), previews,
  * reference frames of more than one group or with an RCT, squeeze or delta palette, patches on images with extra channels,
  * a last frame that blends (blend_mode other than kReplace) behind a reference frame,
@@ -141,6 +141,10 @@ JXLHIP_EXPORT int jxlhip_codestream_icc_profile(const uint8_t* data, size_t size
  * inputs resident: jxlhip_decode_frame can re-render (another output format after a new jxlhip_frame_begin needs
  * the inputs again: call this function again). */
 #define JXLHIP_OUT_UNDO_ORIENTATION 0x100u
+/* jxlhip_decode_codestream_next only: output_kind | JXLHIP_OUT_BLEND_EXTRA_CHANNELS takes frames that need blending on an
+ * image with extra channels (see "sequences of frames" below); the other decode calls ignore the bit's meaning and
+ * refuse it as a bad output kind. */
+#define JXLHIP_OUT_BLEND_EXTRA_CHANNELS 0x200u
 JXLHIP_EXPORT int jxlhip_decode_codestream(jxlhip_ctx* ctx, jxlhip_parallel_runner runner, void* runner_opaque,
                                            const uint8_t* data, size_t size, uint32_t output_kind,
                                            const jxlhip_output_format* out_format, void* out, size_t out_stride,
@@ -187,11 +191,20 @@ JXLHIP_EXPORT int jxlhip_codestream_phase_ms(const jxlhip_ctx* ctx, double* ms);
  * is_last or duration > 0, blended over whatever its zero-duration layers and earlier frames left in its source slot.
  * Refused up front with JXLHIP_ERR_UNSUPPORTED and a named reason (jxlhip_last_error of the decode call): previews,
  * Modular regular frames, VarDCT kReferenceOnly frames, DC frames and kUseDcFrame, kSkipProgressive, regular frames
- * saved before the colour transform; on an image with extra channels a frame that NeedsBlending (blending.cc:23-40: a
- * crop, or a blend mode other than kReplace on the colour or on any extra channel) and a frame with patches -- the only
- * readers of a saved frame, so nothing is ever saved there (blending and saving extra channels, kBlend with real alpha
- * included, is not in the back-end; full-frame kReplace sequences with alpha are taken); and everything the
- * single-frame calls refuse per frame. */
+ * saved before the colour transform; on an image with extra channels a frame with patches, an upsampled frame and
+ * extra channels upsampled on their own; a frame that needs blending while display_nits is set; and everything the
+ * single-frame calls refuse per frame.
+ * Images with extra channels (alpha, depth, ...): the caller asks for them -- JXLHIP_SEQUENCE_EXTRA_CHANNELS to
+ * jxlhip_codestream_sequence_info_ex, JXLHIP_OUT_BLEND_EXTRA_CHANNELS in jxlhip_decode_codestream_next's output_kind.
+ * Without the flags both calls refuse a frame that NeedsBlending on such an image ("a frame that needs blending on an
+ * image with extra channels"), exactly as they did before the flags existed: the answers of the existing calls to
+ * existing arguments do not change.  With them a frame that
+ * NeedsBlending (blending.cc:23-40: a crop, or a blend
+ * mode other than kReplace on the colour or on any extra channel) or that a later frame reads has its extra channels
+ * decoded (Modular, host) and blended and saved beside the colour on the device (jxlhip_set_blending_extra): kBlend and
+ * kAlphaWeightedAdd with the real alpha, straight or premultiplied (alpha_premultiplied), every extra channel with its
+ * own mode and source slot.  A 4-channel packed `out` then carries the BLENDED alpha of the image's first alpha
+ * channel.  A plain full kReplace frame that nothing reads takes the single-frame path (jxlhip_set_alpha). */
 typedef struct jxlhip_sequence_info {
   uint32_t have_animation, tps_numerator, tps_denominator, num_loops, have_timecodes; /* AnimationHeader */
   uint32_t num_coded_frames;     /* every frame of the file, reference-only frames and layers included */
@@ -204,6 +217,12 @@ typedef struct jxlhip_sequence_info {
  * JXLHIP_ERR_UNSUPPORTED with seq->why naming the case (the other fields of *seq are then 0). */
 JXLHIP_EXPORT int jxlhip_codestream_sequence_info(const uint8_t* data, size_t size, jxlhip_codestream_info* info,
                                                   jxlhip_sequence_info* seq);
+/* The same with flags: JXLHIP_SEQUENCE_EXTRA_CHANNELS = frames that need blending on an image with extra channels are
+ * taken (decode them with JXLHIP_OUT_BLEND_EXTRA_CHANNELS).  flags == 0 is jxlhip_codestream_sequence_info; any other bit
+ * is JXLHIP_ERR_INVALID_ARGUMENT. */
+#define JXLHIP_SEQUENCE_EXTRA_CHANNELS 1u
+JXLHIP_EXPORT int jxlhip_codestream_sequence_info_ex(const uint8_t* data, size_t size, uint32_t flags,
+                                                     jxlhip_codestream_info* info, jxlhip_sequence_info* seq);
 
 typedef struct jxlhip_sequence_frame {
   uint32_t index;               /* of the displayed frame, from 0 */
@@ -226,7 +245,7 @@ typedef struct jxlhip_sequence_frame {
  * The context remembers the cursor it expects: any other non-zero value, and a call after the frame with is_last, is
  * JXLHIP_ERR_STATE.  Pass the same bytes to every call of a sequence.
  * A frame is saved only when a later frame of the file reads its slot before the slot is overwritten (it blends with
- * that source, or carries a patch dictionary): cjxl gives every frame of an animation save_as_reference = 1 whether it
+ * that source, colour or any extra channel, or carries a patch dictionary): cjxl gives every frame of an animation save_as_reference = 1 whether it
  * is used or not, and a plain full-frame animation takes exactly the single-frame path per frame.
  * Blending happens in the transfer function of out_format (jxlhip_set_blending): it matches the reference when that is
  * the original's (info->transfer_function).  Noise frames get the reference's seed counters (dec_frame.cc:160-168) as

@@ -10,13 +10,17 @@ _RUNNER_SO = os.path.join(_HERE, "csrc", "libjxl_threads_hip.so")
 KERNEL_COUNT = 8
 KERNEL_NAMES = ["prepare", "blocks", "filters", "fused", "epf0", "noise", "splines", "upsample"]
 # jxlhip_profile_read_ex: the slots above, then those added since (JXLHIP_KERNEL_PATCHES = 8, JXLHIP_KERNEL_BLEND = 9,
-# JXLHIP_KERNEL_TONE_MAP = 10)
-KERNEL_COUNT_EX = 11
-KERNEL_NAMES_EX = KERNEL_NAMES + ["patches", "blend", "tone_map"]
+# JXLHIP_KERNEL_TONE_MAP = 10, JXLHIP_KERNEL_BLEND_EC = 11)
+KERNEL_COUNT_EX = 12
+KERNEL_NAMES_EX = KERNEL_NAMES + ["patches", "blend", "tone_map", "blend_ec"]
 TONE_MAPPING_CONSTANTS = 18  # JXLHIP_TONE_MAPPING_CONSTANTS
 # BlendMode (JXLHIP_BLEND_*) and jxlhip_blend_params::save_slot's "none"
 BLEND_REPLACE, BLEND_ADD, BLEND_BLEND, BLEND_ALPHA_WEIGHTED_ADD, BLEND_MUL = range(5)
 BLEND_NO_SAVE = 0xFFFFFFFF
+# the sequence calls take frames that need blending on images with extra channels: JXLHIP_SEQUENCE_EXTRA_CHANNELS
+# (jxlhip_codestream_sequence_info_ex's flags), JXLHIP_OUT_BLEND_EXTRA_CHANNELS (jxlhip_decode_codestream_next's output_kind)
+SEQUENCE_EXTRA_CHANNELS = 1
+OUT_BLEND_EXTRA_CHANNELS = 0x200
 # PatchBlendMode (JXLHIP_PATCH_*)
 PATCH_NONE, PATCH_REPLACE, PATCH_ADD, PATCH_MUL, PATCH_BLEND_ABOVE, PATCH_BLEND_BELOW, PATCH_ALPHA_WEIGHTED_ADD_ABOVE, \
     PATCH_ALPHA_WEIGHTED_ADD_BELOW = range(8)
@@ -212,6 +216,18 @@ class FrameParams(C.Structure):
                 ("used_acs", C.c_uint32), ("undo_orientation", C.c_uint32)]
 
 
+class BlendExtraChannel(C.Structure):
+    """jxlhip_blend_extra_channel"""
+    _fields_ = [("is_alpha", C.c_uint32), ("alpha_associated", C.c_uint32), ("mode", C.c_uint32),
+                ("alpha_channel", C.c_uint32), ("clamp", C.c_uint32), ("source", C.c_uint32)]
+
+
+class BlendExtraParams(C.Structure):
+    """jxlhip_blend_extra_params"""
+    _fields_ = [("num_extra_channels", C.c_uint32), ("channel", BlendExtraChannel * 4), ("color_alpha_channel", C.c_uint32),
+                ("planes", C.c_void_p * 4), ("stride_floats", C.c_size_t)]
+
+
 class BlendParams(C.Structure):
     """jxlhip_blend_params"""
     _fields_ = [("image_xsize", C.c_uint32), ("image_ysize", C.c_uint32), ("x0", C.c_int32), ("y0", C.c_int32),
@@ -278,7 +294,7 @@ EXPORTS = [
     "jxlhip_dequant_table_offset", "jxlhip_status_string", "jxlhip_create", "jxlhip_create_ex", "jxlhip_create_multi",
     "jxlhip_destroy", "jxlhip_last_error", "jxlhip_debug_reload_env", "jxlhip_set_stream",
     "jxlhip_frame_begin", "jxlhip_frame_set_inputs", "jxlhip_upload_side_info",
-    "jxlhip_submit_group", "jxlhip_set_alpha", "jxlhip_set_noise", "jxlhip_noise_rng_state", "jxlhip_set_splines", "jxlhip_set_upsampling", "jxlhip_set_reference_frame", "jxlhip_set_patches", "jxlhip_set_blending", "jxlhip_set_tone_mapping", "jxlhip_tone_mapping_constants", "jxlhip_canvas_read", "jxlhip_profile_read_ex", "jxlhip_alpha_staging", "jxlhip_decode_blocks", "jxlhip_halo_rows",
+    "jxlhip_submit_group", "jxlhip_set_alpha", "jxlhip_set_noise", "jxlhip_noise_rng_state", "jxlhip_set_splines", "jxlhip_set_upsampling", "jxlhip_set_reference_frame", "jxlhip_set_patches", "jxlhip_set_blending", "jxlhip_set_tone_mapping", "jxlhip_tone_mapping_constants", "jxlhip_canvas_read", "jxlhip_set_blending_extra", "jxlhip_canvas_read_extra", "jxlhip_frame_extra_read", "jxlhip_profile_read_ex", "jxlhip_alpha_staging", "jxlhip_decode_blocks", "jxlhip_halo_rows",
     "jxlhip_halo_export", "jxlhip_halo_import", "jxlhip_decode_filters", "jxlhip_decode_filters_rows", "jxlhip_stripe_begin",
     "jxlhip_stripe_finish", "jxlhip_decode_frame",
     "jxlhip_decode_frame_host", "jxlhip_decode_frame_pinned",
@@ -301,7 +317,7 @@ EXPORTS = [
     "jxlhip_modular_extra_channel_rows_f32", "jxlhip_modular_ac_group_decode_f32_strided",
     # include/jxl_hip_codestream.h
     "jxlhip_codestream_basic_info", "jxlhip_decode_codestream", "jxlhip_decode_codestream_extra",
-    "jxlhip_codestream_icc_profile", "jxlhip_codestream_phase_ms", "jxlhip_codestream_sequence_info",
+    "jxlhip_codestream_icc_profile", "jxlhip_codestream_phase_ms", "jxlhip_codestream_sequence_info", "jxlhip_codestream_sequence_info_ex",
     "jxlhip_decode_codestream_next", "jxlhip_codestream_set_display", "jxlhip_codestream_display_info",
 ]
 
@@ -372,6 +388,9 @@ def load_library():
     L.jxlhip_set_tone_mapping.argtypes = [vp, C.POINTER(ToneMapping)]
     L.jxlhip_tone_mapping_constants.argtypes = [C.POINTER(ToneMapping), u32, C.POINTER(C.c_float), sz]
     L.jxlhip_canvas_read.argtypes = [vp, u32, vp, sz, C.POINTER(u32), C.POINTER(u32)]
+    L.jxlhip_set_blending_extra.argtypes = [vp, C.POINTER(BlendExtraParams)]
+    L.jxlhip_canvas_read_extra.argtypes = [vp, u32, u32, vp, sz, C.POINTER(u32), C.POINTER(u32)]
+    L.jxlhip_frame_extra_read.argtypes = [vp, u32, vp, sz]
     L.jxlhip_profile_read_ex.argtypes = [vp, C.POINTER(C.c_float), C.POINTER(u32), u32]
     L.jxlhip_splines_quantized.argtypes = [vp, C.POINTER(u32), C.POINTER(sz), C.POINTER(i32), vp, vp, vp, vp]
     L.jxlhip_modular_global_decode.argtypes = [vp, sz, C.POINTER(sz), C.POINTER(FrameHeader), C.POINTER(vp)]
@@ -432,6 +451,7 @@ def load_library():
     L.jxlhip_icc_decode.argtypes = [vp, sz, C.POINTER(sz), vp, sz, C.POINTER(sz)]
     L.jxlhip_decode_codestream.argtypes = [vp, vp, vp, vp, sz, u32, vp, vp, sz, sz, C.POINTER(CodestreamInfo)]
     L.jxlhip_codestream_sequence_info.argtypes = [vp, sz, C.POINTER(CodestreamInfo), C.POINTER(SequenceInfo)]
+    L.jxlhip_codestream_sequence_info_ex.argtypes = [vp, sz, u32, C.POINTER(CodestreamInfo), C.POINTER(SequenceInfo)]
     L.jxlhip_decode_codestream_next.argtypes = [vp, vp, vp, vp, sz, C.POINTER(C.c_uint64), u32, vp, vp, sz, sz,
                                                 C.POINTER(CodestreamInfo), C.POINTER(SequenceFrame)]
     L.jxlhip_codestream_set_display.argtypes = [vp, C.POINTER(Display)]

@@ -817,7 +817,9 @@ static int DecodeFrameAt(jxlhip_ctx* c, const uint8_t* cs, size_t n, const Parse
 
   // an alpha channel is decoded only when the output has room for it; its bytes sit behind the coefficients of
   // every AC-group section and are skipped otherwise
-  const bool want_alpha = h.alpha_index >= 0 && output_kind == JXLHIP_OUT_PACKED && out_format->num_channels == 4;
+  // (a frame that is blended or saved hands ALL its extra channels to jxlhip_set_blending_extra instead: below)
+  const bool blend_ec = fc.blend && ih.num_extra_channels != 0;
+  const bool want_alpha = !blend_ec && h.alpha_index >= 0 && output_kind == JXLHIP_OUT_PACKED && out_format->num_channels == 4;
   // the caller's host planes for the extra channels (jxlhip_decode_codestream_extra)
   float* user_plane[4] = {nullptr, nullptr, nullptr, nullptr};
   bool want_planes = false;
@@ -826,6 +828,17 @@ static int DecodeFrameAt(jxlhip_ctx* c, const uint8_t* cs, size_t n, const Parse
     want_planes |= user_plane[i] != nullptr;
   }
   if (want_planes && extra_stride < ih.xsize) return Fail(c, JXLHIP_ERR_INVALID_ARGUMENT, "extra_stride below the image width");
+  // the planes of a blended frame, at the FRAME's size (a cropped frame's channels are as small as its colour)
+  std::vector<float> blend_planes;
+  size_t plane_stride = extra_stride;
+  if (blend_ec) {
+    if (want_planes) return Fail(c, JXLHIP_ERR_UNSUPPORTED, "the caller's extra-channel planes on a blended frame");
+    const size_t plane = (size_t)fh.xsize * fh.ysize;
+    blend_planes.resize(ih.num_extra_channels * plane);
+    for (uint32_t i = 0; i < ih.num_extra_channels; i++) user_plane[i] = blend_planes.data() + i * plane;
+    plane_stride = fh.xsize;
+    want_planes = true;
+  }
   const bool want_modular = want_alpha || want_planes;
   std::vector<size_t> end_bits(want_modular ? (size_t)np * ng : 0, 0);
   std::vector<const uint8_t*> asec((size_t)np * ng);
@@ -1084,7 +1097,7 @@ static int DecodeFrameAt(jxlhip_ctx* c, const uint8_t* cs, size_t n, const Parse
       job.ec_bits[i] = i < ih.num_extra_channels ? h.extra[i].bit_depth.bits_per_sample : 8;
       const bool is_alpha = want_alpha && (int)i == h.alpha_index;
       job.planes[i] = is_alpha ? alpha : user_plane[i];
-      job.strides[i] = is_alpha ? astride : extra_stride;
+      job.strides[i] = is_alpha ? astride : plane_stride;
     }
     job.image_bits = ih.bit_depth.bits_per_sample;
     job.tree = tree.t;
@@ -1112,8 +1125,8 @@ static int DecodeFrameAt(jxlhip_ctx* c, const uint8_t* cs, size_t n, const Parse
       ExtraRowsJob rows;
       rows.tree = tree.t;
       rows.image_bits = job.image_bits;
-      rows.ysize = ih.ysize;
-      rows.tasks_per_channel = (ih.ysize + 63) / 64;
+      rows.ysize = fh.ysize;  // (the image's, except for a cropped frame of a sequence)
+      rows.tasks_per_channel = (fh.ysize + 63) / 64;
       for (uint32_t i = 0; i < 4; i++) {
         rows.ec_bits[i] = job.ec_bits[i];
         rows.planes[i] = i < ih.num_extra_channels ? job.planes[i] : nullptr;
@@ -1149,6 +1162,26 @@ static int DecodeFrameAt(jxlhip_ctx* c, const uint8_t* cs, size_t n, const Parse
   if (patches && (rc = jxlhip_set_patches(c, patches.get()))) return rc;
   if (splines && (rc = jxlhip_set_splines(c, splines.get()))) return rc;
   if (fc.blend && (rc = jxlhip_set_blending(c, fc.blend))) return rc;
+  if (blend_ec) {  // the extra channels are blended and saved beside the colour (ExtraChannelInfo, extra_channel_blending_info)
+    jxlhip_blend_extra_params e{};
+    e.num_extra_channels = ih.num_extra_channels;
+    e.color_alpha_channel = fh.blend_alpha_channel;
+    e.stride_floats = plane_stride;
+    for (uint32_t i = 0; i < ih.num_extra_channels; i++) {
+      e.channel[i].is_alpha = h.extra[i].type == JXLHIP_EC_ALPHA;
+      e.channel[i].alpha_associated = h.extra[i].alpha_associated;
+      e.channel[i].mode = fh.ec_blend_mode[i];
+      e.channel[i].alpha_channel = fh.ec_blend_alpha_channel[i];
+      e.channel[i].clamp = fh.ec_blend_clamp[i];
+      e.channel[i].source = fh.ec_blend_source[i];
+      e.planes[i] = user_plane[i];
+    }
+    if (e.color_alpha_channel >= e.num_extra_channels) return Fail(c, JXLHIP_ERR_BAD_STREAM, "the colour's alpha channel %u of %u extra channels", e.color_alpha_channel, e.num_extra_channels);
+    for (uint32_t i = 0; i < e.num_extra_channels; i++)
+      if (e.channel[i].alpha_channel >= e.num_extra_channels || e.channel[i].source > 3 || e.channel[i].mode > JXLHIP_BLEND_MUL)
+        return Fail(c, JXLHIP_ERR_BAD_STREAM, "blending info of extra channel %u out of range", i);
+    if ((rc = jxlhip_set_blending_extra(c, &e))) return rc;
+  }
   if (h.display_nits > 0.0f) {  // JxlDecoderSetDesiredIntensityTarget: the stage exists for a PQ original brighter than the display
     const jxlhip_color_encoding& ce = ih.color_encoding;
     jxlhip_tone_mapping tm{};
@@ -1203,7 +1236,8 @@ int SequenceNextImpl(jxlhip_ctx* c, jxlhip_parallel_runner runner, void* runner_
                      uint64_t* cursor, uint32_t output_kind, const jxlhip_output_format* out_format, void* out, size_t out_stride,
                      size_t out_plane_stride, jxlhip_codestream_info* info_out, jxlhip_sequence_frame* frame_out) {
   const bool undo_orientation = (output_kind & JXLHIP_OUT_UNDO_ORIENTATION) != 0;
-  output_kind &= ~(uint32_t)JXLHIP_OUT_UNDO_ORIENTATION;
+  const bool blend_extra = (output_kind & JXLHIP_OUT_BLEND_EXTRA_CHANNELS) != 0;
+  output_kind &= ~(uint32_t)(JXLHIP_OUT_UNDO_ORIENTATION | JXLHIP_OUT_BLEND_EXTRA_CHANNELS);
   if (!c || !data || !out || !cursor || output_kind > JXLHIP_OUT_PACKED || (output_kind == JXLHIP_OUT_PACKED && !out_format))
     return JXLHIP_ERR_INVALID_ARGUMENT;
   JXLHIP_NO_MULTI(c);
@@ -1230,7 +1264,7 @@ int SequenceNextImpl(jxlhip_ctx* c, jxlhip_parallel_runner runner, void* runner_
   int rc = ExtractCodestream(data, size, &storage, &cs, &n, &container);
   if (rc) return Fail(c, rc, "not a JPEG XL codestream or container");
   Sequence s;
-  if ((rc = WalkSequence(cs, n, &s)))
+  if ((rc = WalkSequence(cs, n, &s, blend_extra)))
     return Fail(c, rc, rc == JXLHIP_ERR_UNSUPPORTED ? (s.h.why[0] ? s.h.why : "stream uses features outside the VarDCT back-end") : "invalid headers");
   if ((rc = ApplyDisplay(c, &s.h))) return rc;
   size_t i = 0;
@@ -1320,7 +1354,12 @@ int SequenceNextImpl(jxlhip_ctx* c, jxlhip_parallel_runner runner, void* runner_
 }  // namespace
 
 int jxlhip_codestream_sequence_info(const uint8_t* data, size_t size, jxlhip_codestream_info* info, jxlhip_sequence_info* seq) {
-  if (!data || !info || !seq) return JXLHIP_ERR_INVALID_ARGUMENT;
+  return jxlhip_codestream_sequence_info_ex(data, size, 0, info, seq);
+}
+
+int jxlhip_codestream_sequence_info_ex(const uint8_t* data, size_t size, uint32_t flags, jxlhip_codestream_info* info,
+                                       jxlhip_sequence_info* seq) {
+  if (!data || !info || !seq || (flags & ~(uint32_t)JXLHIP_SEQUENCE_EXTRA_CHANNELS)) return JXLHIP_ERR_INVALID_ARGUMENT;
   try {
     std::vector<uint8_t> storage;
     const uint8_t* cs = nullptr;
@@ -1331,7 +1370,7 @@ int jxlhip_codestream_sequence_info(const uint8_t* data, size_t size, jxlhip_cod
     Sequence s;
     memset(seq, 0, sizeof(*seq));
     seq->why = "";
-    if ((rc = WalkSequence(cs, n, &s))) {
+    if ((rc = WalkSequence(cs, n, &s, (flags & JXLHIP_SEQUENCE_EXTRA_CHANNELS) != 0))) {
       if (rc == JXLHIP_ERR_UNSUPPORTED) seq->why = s.h.why[0] ? s.h.why : "stream uses features outside the VarDCT back-end";
       return rc;
     }

@@ -310,6 +310,22 @@ struct jxlhip_ctx {
   DevBuf<float> canvas[4];
   uint32_t canvas_w[4] = {0, 0, 0, 0}, canvas_h[4] = {0, 0, 0, 0};
   DevBuf<float> blend_stage;
+  // jxlhip_set_blending_extra: the current frame belongs to an image with extra channels, which are blended and saved
+  // with the colour (frame_begin and set_blending reset blend_ec_on).  canvas_ec[s] = the extra-channel planes of slot
+  // s's canvas: canvas_nec[s] planar float planes of canvas_h rows of EcStride(canvas_w) floats, one behind the other;
+  // they live and die with the canvas.  blend_ec_stage = the frame's own planes in front of k_ec_blend (uploaded by the
+  // call: blend_ec.num_extra_channels planes of f.ysize rows of blend_ec_stage_stride floats, the samples (x0 mod 4)
+  // floats in); frame_ec = the blended planes of a frame that is not saved.  frame_ec_planes = where the current
+  // frame's blended planes are (the save slot's or frame_ec; jxlhip_frame_extra_read), frame_ec_n of them, 0 = none.
+  bool blend_ec_on = false;
+  jxlhip_blend_extra_params blend_ec{};  // (its plane pointers are the caller's and not kept)
+  DevBuf<float> canvas_ec[4];
+  uint32_t canvas_nec[4] = {0, 0, 0, 0};
+  DevBuf<float> blend_ec_stage;
+  size_t blend_ec_stage_stride = 0;
+  DevBuf<float> frame_ec;
+  const float* frame_ec_planes = nullptr;
+  uint32_t frame_ec_n = 0, frame_ec_w = 0, frame_ec_h = 0;
   // jxlhip_set_tone_mapping: the current frame is tone-mapped (frame_begin resets tm_on); tm_k = k_tone_map's constants,
   // tm_planes = the frame's own output as planar XYB at output size in front of it (DecodeFrameToneMapped)
   bool tm_on = false;

@@ -355,6 +355,8 @@ int jxlhip_frame_begin(jxlhip_ctx* c, const jxlhip_frame_params* p) {
   c->patches_on = false;
   c->ups_factor = 1;
   c->blend_on = false;
+  c->blend_ec_on = false;
+  c->frame_ec_n = 0;
   c->tm_on = false;
   return JXLHIP_OK;
 }
@@ -564,6 +566,7 @@ int jxlhip_set_reference_frame(jxlhip_ctx* c, uint32_t slot, uint32_t xsize, uin
   c->ref_serial++;  // (an uploaded dictionary points into the slots: DecodeFrameFeatures refuses it from here on)
   c->seq_open = false;  // (a sequence of jxlhip_decode_codestream_next must not go on over slots emptied behind its back)
   c->canvas_w[slot] = c->canvas_h[slot] = 0;  // (a slot holds one kind: an XYB frame drops the canvas)
+  c->canvas_nec[slot] = 0;                     // (... and its extra-channel planes)
   if (xsize == 0 || ysize == 0) {  // cleared; the memory stays for the next frame of the slot
     c->ref_w[slot] = c->ref_h[slot] = 0;
     return JXLHIP_OK;
@@ -730,6 +733,7 @@ int jxlhip_set_blending(jxlhip_ctx* c, const jxlhip_blend_params* b) {
   if (c->multi) return Fail(c, JXLHIP_ERR_UNSUPPORTED, "blending on a multi-device context");
   if (!c->have_frame) return Fail(c, JXLHIP_ERR_STATE, "set_blending before frame_begin");
   c->blend_on = false;
+  c->blend_ec_on = false;
   if (!b) return JXLHIP_OK;
   if (c->f.group_y0 != 0 || c->f.group_rows != c->f.ysg) return Fail(c, JXLHIP_ERR_UNSUPPORTED, "blending with stripes");
   if (c->p.undo_orientation > 1)
@@ -760,6 +764,116 @@ int jxlhip_canvas_read(jxlhip_ctx* c, uint32_t slot, float* dev_out, size_t stri
   HIPCHK(c, hipSetDevice(c->device));
   HIPCHK(c, hipMemcpy2DAsync(dev_out, stride_floats * sizeof(float), c->canvas[slot], CanvasStride(*w) * sizeof(float),
                              3 * (size_t)*w * sizeof(float), *h, hipMemcpyDeviceToDevice, c->stream));
+  return JXLHIP_OK;
+}
+
+namespace {
+bool Capturing(hipStream_t st);  // (below, with the launches)
+}
+
+// What DecodeFrameBlended and jxlhip_set_blending_extra both need to know about a blended frame of an image with extra
+// channels: whether the colour's mode comes to "replace" (PerformBlending's copy(fg)), and whether nothing of any
+// source is read at all (a full-size frame at the origin whose colour and extra channels all replace).
+static bool EcHasAlpha(const jxlhip_blend_extra_params& e) {
+  for (uint32_t i = 0; i < e.num_extra_channels; i++)
+    if (e.channel[i].is_alpha) return true;
+  return false;
+}
+static bool EcSourcesDead(const jxlhip_ctx* c, const jxlhip_blend_extra_params& e) {
+  const jxlhip_blend_params& b = c->blend;
+  const bool full = b.x0 == 0 && b.y0 == 0 && OutCols(c) == b.image_xsize && OutRows(c) == b.image_ysize;
+  bool replaces = b.mode == JXLHIP_BLEND_REPLACE || (b.mode == JXLHIP_BLEND_BLEND && !EcHasAlpha(e));
+  for (uint32_t i = 0; i < e.num_extra_channels; i++) replaces = replaces && e.channel[i].mode == JXLHIP_BLEND_REPLACE;
+  return full && replaces;
+}
+// the source slots of the extra channels, as DecodeFrameBlended checks the colour's
+static int CheckEcSources(jxlhip_ctx* c, const jxlhip_blend_extra_params& e) {
+  if (EcSourcesDead(c, e)) return JXLHIP_OK;
+  const uint32_t W = c->blend.image_xsize, H = c->blend.image_ysize;
+  for (uint32_t i = 0; i < e.num_extra_channels; i++) {
+    const uint32_t s = e.channel[i].source;
+    if (c->ref_w[s] != 0)
+      return Fail(c, JXLHIP_ERR_INVALID_ARGUMENT, "blend source slot %u of extra channel %u holds an XYB reference frame", s, i);
+    if (c->canvas_w[s] != 0 && (c->canvas_w[s] < W || c->canvas_h[s] < H))
+      return Fail(c, JXLHIP_ERR_INVALID_ARGUMENT, "the %ux%u canvas of slot %u (extra channel %u) is smaller than the %ux%u image",
+                  c->canvas_w[s], c->canvas_h[s], s, i, W, H);
+  }
+  return JXLHIP_OK;
+}
+
+// The extra channels of the current blended frame (FrameHeader::extra_channel_blending_info, ExtraChannelInfo):
+// recorded and uploaded here, carried out by DecodeFrameBlended with k_ec_blend; frame_begin and set_blending reset.
+int jxlhip_set_blending_extra(jxlhip_ctx* c, const jxlhip_blend_extra_params* e) {
+  if (!c || !e) return JXLHIP_ERR_INVALID_ARGUMENT;
+  if (c->multi) return Fail(c, JXLHIP_ERR_UNSUPPORTED, "blending on a multi-device context");
+  if (!c->have_frame) return Fail(c, JXLHIP_ERR_STATE, "set_blending_extra before frame_begin");
+  c->blend_ec_on = false;
+  if (!c->blend_on) return Fail(c, JXLHIP_ERR_STATE, "set_blending_extra without set_blending on this frame");
+  if (c->fp.alpha) return Fail(c, JXLHIP_ERR_UNSUPPORTED, "set_blending_extra on a frame with set_alpha (the alpha channel is one of the planes here)");
+  if (c->ups_factor > 1) return Fail(c, JXLHIP_ERR_UNSUPPORTED, "extra channels of an upsampled frame");
+  if (c->patches_on) return Fail(c, JXLHIP_ERR_UNSUPPORTED, "extra channels of a frame with patches (they would have to blend them)");
+  const uint32_t n = e->num_extra_channels;
+  if (n == 0 || n > 4) return Fail(c, JXLHIP_ERR_INVALID_ARGUMENT, "%u extra channels (1..4)", n);
+  if (e->color_alpha_channel >= n) return Fail(c, JXLHIP_ERR_INVALID_ARGUMENT, "colour alpha channel %u of %u", e->color_alpha_channel, n);
+  const size_t fw = c->f.xsize, fh = c->f.ysize;
+  for (uint32_t i = 0; i < n; i++) {
+    const jxlhip_blend_extra_channel& ch = e->channel[i];
+    if (ch.mode > JXLHIP_BLEND_MUL) return Fail(c, JXLHIP_ERR_INVALID_ARGUMENT, "extra channel %u: blend mode %u", i, ch.mode);
+    if (ch.alpha_channel >= n) return Fail(c, JXLHIP_ERR_INVALID_ARGUMENT, "extra channel %u: alpha channel %u of %u", i, ch.alpha_channel, n);
+    if (ch.source > 3) return Fail(c, JXLHIP_ERR_INVALID_ARGUMENT, "extra channel %u: blend source slot %u", i, ch.source);
+    if (!e->planes[i]) return Fail(c, JXLHIP_ERR_INVALID_ARGUMENT, "extra channel %u: null plane", i);
+  }
+  if (e->stride_floats < fw) return Fail(c, JXLHIP_ERR_INVALID_ARGUMENT, "extra channel stride %zu < xsize", e->stride_floats);
+  int rc = CheckEcSources(c, *e);
+  if (rc) return rc;
+  HIPCHK(c, hipSetDevice(c->device));
+  // staged like the colour: (x0 mod 4) floats into rows padded to four pixels (kernels_blend_ec.hip)
+  const size_t lead = (size_t)(c->blend.x0 - (c->blend.x0 & ~3));
+  const size_t stride = EcStride((uint32_t)(lead + fw));
+  const size_t need = n * fh * stride;
+  if (need > c->blend_ec_stage.n) {
+    if (Capturing(c->stream)) return Fail(c, JXLHIP_ERR_UNSUPPORTED, "blending while the stream is being captured");
+    HIPCHK(c, hipStreamSynchronize(c->stream));  // an earlier launch may still read the planes
+    if ((rc = c->blend_ec_stage.Reserve(c, need))) return rc;
+    // (the padding is read, never used: zeroed once so that nothing reads memory nobody wrote)
+    HIPCHK(c, hipMemsetAsync(c->blend_ec_stage, 0, need * sizeof(float), c->stream));
+  }
+  for (uint32_t i = 0; i < n; i++)
+    HIPCHK(c, hipMemcpy2DAsync(c->blend_ec_stage + i * fh * stride + lead, stride * sizeof(float), e->planes[i],
+                               e->stride_floats * sizeof(float), fw * sizeof(float), fh, hipMemcpyHostToDevice, c->stream));
+  c->blend_ec_stage_stride = stride;
+  c->blend_ec = *e;
+  for (int i = 0; i < 4; i++) c->blend_ec.planes[i] = nullptr;
+  c->blend_ec_on = true;
+  return JXLHIP_OK;
+}
+
+int jxlhip_canvas_read_extra(jxlhip_ctx* c, uint32_t slot, uint32_t ec, float* dev_out, size_t stride_floats, uint32_t* w,
+                             uint32_t* h) {
+  if (!c || slot > 3 || ec > 3 || !w || !h) return JXLHIP_ERR_INVALID_ARGUMENT;
+  if (c->multi) return Fail(c, JXLHIP_ERR_UNSUPPORTED, "canvases on a multi-device context");
+  const bool have = c->canvas_w[slot] != 0 && ec < c->canvas_nec[slot];
+  *w = have ? c->canvas_w[slot] : 0;
+  *h = have ? c->canvas_h[slot] : 0;
+  if (!dev_out || !have) return JXLHIP_OK;
+  if (stride_floats < *w) return Fail(c, JXLHIP_ERR_INVALID_ARGUMENT, "plane stride %zu < %u", stride_floats, *w);
+  HIPCHK(c, hipSetDevice(c->device));
+  const size_t es = EcStride(*w);
+  HIPCHK(c, hipMemcpy2DAsync(dev_out, stride_floats * sizeof(float), c->canvas_ec[slot] + (size_t)ec * *h * es, es * sizeof(float),
+                             (size_t)*w * sizeof(float), *h, hipMemcpyDeviceToDevice, c->stream));
+  return JXLHIP_OK;
+}
+
+int jxlhip_frame_extra_read(jxlhip_ctx* c, uint32_t ec, float* dev_out, size_t stride_floats) {
+  if (!c || !dev_out || ec > 3) return JXLHIP_ERR_INVALID_ARGUMENT;
+  if (c->multi) return Fail(c, JXLHIP_ERR_UNSUPPORTED, "canvases on a multi-device context");
+  if (ec >= c->frame_ec_n) return Fail(c, JXLHIP_ERR_STATE, "the current frame has no blended plane of extra channel %u", ec);
+  const uint32_t w = c->frame_ec_w, h = c->frame_ec_h;
+  if (stride_floats < w) return Fail(c, JXLHIP_ERR_INVALID_ARGUMENT, "plane stride %zu < %u", stride_floats, w);
+  HIPCHK(c, hipSetDevice(c->device));
+  const size_t es = EcStride(w);
+  HIPCHK(c, hipMemcpy2DAsync(dev_out, stride_floats * sizeof(float), c->frame_ec_planes + (size_t)ec * h * es, es * sizeof(float),
+                             (size_t)w * sizeof(float), h, hipMemcpyDeviceToDevice, c->stream));
   return JXLHIP_OK;
 }
 
@@ -1437,7 +1551,8 @@ static int DecodeFrameFeatures(jxlhip_ctx* c, void* out, size_t out_stride, size
 // A blended frame (jxlhip_set_blending): the frame's whole path -- DecodeFrameCoded or DecodeFrameFeatures, whatever it
 // would take without blending -- writes packed float RGB in the caller's transfer function into blend_stage, and
 // k_blend (kernels_blend.hip) blends that over the source canvas into the save slot and / or the caller's buffer,
-// which is image-sized.  The canvas never leaves the device.
+// which is image-sized.  The canvas never leaves the device.  With jxlhip_set_blending_extra the launch is k_ec_blend
+// (kernels_blend_ec.hip), which blends and saves the image's extra channels beside the colour.
 static int DecodeFrameBlended(jxlhip_ctx* c, void* out, size_t out_stride) {
   const jxlhip_blend_params& b = c->blend;
   const DevFrame& f = c->f;
@@ -1445,6 +1560,11 @@ static int DecodeFrameBlended(jxlhip_ctx* c, void* out, size_t out_stride) {
   if (f.group_y0 != 0 || f.group_rows != f.ysg || c->p.undo_orientation > 1 || c->p.output_kind == JXLHIP_OUT_XYB_PLANAR)
     return Fail(c, JXLHIP_ERR_UNSUPPORTED, "blending needs a whole frame in coded orientation and an interleaved output");
   if (c->fp.alpha) return Fail(c, JXLHIP_ERR_UNSUPPORTED, "blending on a frame with alpha");
+  const bool ec = c->blend_ec_on;
+  const jxlhip_blend_extra_params& e = c->blend_ec;
+  const uint32_t nec = ec ? e.num_extra_channels : 0;
+  if (ec && (c->ups_factor > 1 || c->patches_on))
+    return Fail(c, JXLHIP_ERR_UNSUPPORTED, "extra channels of an upsampled frame or of a frame with patches");
   const uint32_t W = b.image_xsize, H = b.image_ysize;
   const bool save = b.save_slot != JXLHIP_BLEND_NO_SAVE;
   if (!out && !save) return Fail(c, JXLHIP_ERR_INVALID_ARGUMENT, "null output and no save slot");
@@ -1457,8 +1577,10 @@ static int DecodeFrameBlended(jxlhip_ctx* c, void* out, size_t out_stride) {
                       : (b.mode == JXLHIP_BLEND_ADD || b.mode == JXLHIP_BLEND_ALPHA_WEIGHTED_ADD) ? kPatchOpAdd
                                                                                                  : kPatchOpReplace;
   const bool full = b.x0 == 0 && b.y0 == 0 && fw == W && fh == H;
-  // a full frame that replaces never reads its source: whatever the slot holds is no concern of this frame
-  const bool bg_dead = full && op == kPatchOpReplace;
+  // a full frame that replaces never reads its source: whatever the slot holds is no concern of this frame.  (With
+  // extra channels "replaces" means the colour AND every channel: a full frame whose colour replaces while a channel
+  // blends has the colour's slot checked too although the colour does not read it, as BlendingStage's constructor does.)
+  const bool bg_dead = ec ? EcSourcesDead(c, e) : full && op == kPatchOpReplace;
   if (!bg_dead && c->ref_w[b.source] != 0)
     return Fail(c, JXLHIP_ERR_INVALID_ARGUMENT, "blend source slot %u holds an XYB reference frame", b.source);
   const bool have_src = !bg_dead && c->canvas_w[b.source] != 0;
@@ -1469,8 +1591,25 @@ static int DecodeFrameBlended(jxlhip_ctx* c, void* out, size_t out_stride) {
   if (in_place && (c->canvas_w[b.source] != W || c->canvas_h[b.source] != H))
     return Fail(c, JXLHIP_ERR_INVALID_ARGUMENT, "save_slot == source with a %ux%u canvas and a %ux%u image",
                 c->canvas_w[b.source], c->canvas_h[b.source], W, H);
+  // the extra channels: each from the plane of its own source slot (zeroes when the slot has none); a slot that is
+  // saved into while one of its planes is read must already have the layout it is given
+  bool ec_src[4] = {false, false, false, false};
+  bool ec_in_place = true;
+  if (ec) {
+    if ((rc = CheckEcSources(c, e))) return rc;
+    for (uint32_t i = 0; i < nec; i++) {
+      const uint32_t s = e.channel[i].source;
+      ec_src[i] = !bg_dead && c->canvas_w[s] != 0 && i < c->canvas_nec[s];
+      ec_in_place = ec_in_place && ec_src[i] && save && s == b.save_slot;
+      if (save && ec_src[i] && s == b.save_slot && (c->canvas_w[s] != W || c->canvas_h[s] != H || c->canvas_nec[s] != nec))
+        return Fail(c, JXLHIP_ERR_INVALID_ARGUMENT,
+                    "save_slot == source of extra channel %u with a %ux%u canvas of %u extra channels and a %ux%u image of %u", i,
+                    c->canvas_w[s], c->canvas_h[s], c->canvas_nec[s], W, H, nec);
+    }
+  }
+  const bool in_place_all = in_place && ec_in_place;  // (without extra channels: in_place)
   // a full frame that replaces and is not saved: today's path and launches, nothing else
-  if (full && op == kPatchOpReplace && !save) {
+  if (!ec && full && op == kPatchOpReplace && !save) {
     return c->noise_on || c->splines_on || c->patches_on || c->ups_factor > 1 ? DecodeFrameFeatures(c, out, out_stride, 0)
                                                                              : DecodeFrameCoded(c, out, out_stride, 0);
   }
@@ -1527,11 +1666,11 @@ static int DecodeFrameBlended(jxlhip_ctx* c, void* out, size_t out_stride) {
     }
     A.dst = c->canvas[s];
     A.dst_stride = CanvasStride(W);
-    A.dst_all = in_place ? 0u : 1u;
   }
-  // the caller's buffer or another slot is written everywhere; a frame blended into its own source slot only under
-  // its rectangle
-  if (out || (save && !in_place)) {
+  A.dst_all = in_place_all ? 0u : 1u;
+  // the caller's buffer or another slot is written everywhere; a frame blended into its own source slot -- the source of
+  // its colour and of every extra channel -- only under its rectangle
+  if (out || !in_place_all) {
     A.gx0 = 0;
     A.gx1 = (W + 3) / 4;
     A.y0 = 0;
@@ -1547,18 +1686,65 @@ static int DecodeFrameBlended(jxlhip_ctx* c, void* out, size_t out_stride) {
   fp.out = out;
   fp.out_stride = out_stride;
   fp.out_plane_stride = 0;
+  BlendEcArgs E{};
+  if (ec) {
+    const size_t es = EcStride(W), plane = (size_t)H * es;
+    // where the blended planes go: the save slot's, or the frame's own
+    DevBuf<float>& planes = save ? c->canvas_ec[b.save_slot] : c->frame_ec;
+    if ((size_t)nec * plane > planes.n) HIPCHK(c, hipStreamSynchronize(c->stream));  // an earlier launch may still read them
+    if ((rc = planes.Reserve(c, (size_t)nec * plane))) return rc;
+    E.num_ec = nec;
+    E.has_alpha = EcHasAlpha(e) ? 1u : 0u;
+    E.color_mode = b.mode;
+    E.color_clamp = b.clamp;
+    E.color_alpha = e.color_alpha_channel;
+    E.out_alpha = -1;
+    E.fg_stride = c->blend_ec_stage_stride;
+    E.dst_stride = es;
+    for (uint32_t i = 0; i < nec; i++) {
+      const jxlhip_blend_extra_channel& ch = e.channel[i];
+      E.mode[i] = ch.mode;
+      E.clamp[i] = ch.clamp;
+      E.alpha[i] = ch.alpha_channel;
+      E.premul[i] = ch.alpha_associated ? 1u : 0u;
+      if (ch.is_alpha && E.out_alpha < 0) E.out_alpha = (int32_t)i;
+      E.fg[i] = c->blend_ec_stage + (size_t)i * (size_t)fh * E.fg_stride;
+      if (ec_src[i]) {
+        const uint32_t s = ch.source;
+        E.src_stride[i] = EcStride(c->canvas_w[s]);
+        E.src[i] = c->canvas_ec[s] + (size_t)i * c->canvas_h[s] * E.src_stride[i];
+      }
+      E.dst[i] = planes + (size_t)i * plane;
+    }
+    if (E.out_alpha >= 0) {  // the fourth sample of a packed output: read back from the blended plane
+      fp.alpha = E.dst[E.out_alpha];
+      fp.alpha_stride = (uint32_t)es;
+    }
+    c->frame_ec_planes = planes;
+    c->frame_ec_n = nec;
+    c->frame_ec_w = W;
+    c->frame_ec_h = H;
+  }
   // (a layer wholly outside the image that is blended into its own source slot visits nothing: no launch, no span)
   if (A.gx1 > A.gx0 && A.y1 > A.y0) {
     ProfBegin(c);
-    if (!LaunchBlend(A, fp, out ? (int)c->p.output_kind : 0, c->stream))
-      return Fail(c, JXLHIP_ERR_INVALID_ARGUMENT, "blend launch arguments");
-    ProfMark(c, JXLHIP_KERNEL_BLEND);
+    if (ec) {
+      E.B = A;
+      if (!LaunchBlendEc(E, fp, out ? (int)c->p.output_kind : 0, c->stream))
+        return Fail(c, JXLHIP_ERR_INVALID_ARGUMENT, "blend launch arguments");
+      ProfMark(c, JXLHIP_KERNEL_BLEND_EC);
+    } else {
+      if (!LaunchBlend(A, fp, out ? (int)c->p.output_kind : 0, c->stream))
+        return Fail(c, JXLHIP_ERR_INVALID_ARGUMENT, "blend launch arguments");
+      ProfMark(c, JXLHIP_KERNEL_BLEND);
+    }
     HIPCHK(c, hipGetLastError());
   }
   if (save) {
     const uint32_t s = b.save_slot;
     c->canvas_w[s] = W;
     c->canvas_h[s] = H;
+    c->canvas_nec[s] = nec;
     if (c->ref_w[s] != 0) {  // (a slot holds one kind: the canvas drops the XYB frame, and a dictionary that points into it)
       c->ref_w[s] = c->ref_h[s] = 0;
       c->ref_serial++;

@@ -219,6 +219,29 @@ struct BlendArgs {
 // kind, op or region.
 bool LaunchBlend(const BlendArgs& A, const FilterParams& p, int output_kind, hipStream_t st);
 
+// Blending on an image with extra channels (kernels_blend_ec.hip).  The colour canvas is BlendArgs' (B.op is not read:
+// the colour's BlendMode is color_mode here); every extra channel is a planar float plane whose rows are padded to
+// four pixels (EcStride), in the staged frame (x0 mod 4) pixels in like the colour.
+inline size_t EcStride(uint32_t xsize) { return ((size_t)xsize + 3) & ~(size_t)3; }  // floats per row
+struct BlendEcArgs {
+  BlendArgs B;
+  uint32_t num_ec;                 // 1..4
+  uint32_t has_alpha;              // some extra channel is of type alpha (PerformBlending's has_alpha)
+  uint32_t color_mode, color_clamp, color_alpha;  // BlendingInfo of the colour: jxlhip_blend_mode, clamp, alpha_channel
+  uint32_t mode[4], clamp[4], alpha[4];           // ... of every extra channel
+  uint32_t premul[4];              // ExtraChannelInfo::alpha_associated of channel i (read where i is somebody's alpha channel)
+  int32_t out_alpha;               // the channel whose blended plane the packed tail reads back as alpha (p.alpha), -1: none
+  const float* fg[4];              // staged planes: canvas pixel (x, y) at fg[i] + (y - B.fg_y0) * fg_stride + (x - B.fg_xa)
+  size_t fg_stride;                // floats per staged row, a multiple of 4
+  const float* src[4];             // the plane of channel i in ITS source slot (src_stride[i] floats per row), nullptr = zeroes
+  size_t src_stride[4];
+  float* dst[4];                   // where the blended plane goes: the save slot's plane (may be any src) or the frame's own
+  size_t dst_stride;               // plane (jxlhip_frame_extra_read); never nullptr for i < num_ec
+};
+// k_ec_blend: as LaunchBlend.  With out_alpha >= 0 and a 4-channel packed output p.alpha must be dst[out_alpha]: a thread
+// stores its four blended alpha samples and the output stage reads them back.  False for a bad kind, mode or region.
+bool LaunchBlendEc(const BlendEcArgs& A, const FilterParams& p, int output_kind, hipStream_t st);
+
 // Tone mapping (kernels_tonemap.hip).  What ToneMappingStage's constructor and Rec2408ToneMapperBase's member
 // initialisers compute for a PQ original (stage_tone_mapping.cc:43-63, cms/tone_mapping.h:82-97), in the order
 // jxlhip_tone_mapping_constants reports them.

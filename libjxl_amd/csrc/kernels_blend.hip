@@ -3,7 +3,8 @@
 // blended frame saved for the frames that follow.
 //
 // Replaces (behaviour, not code): lib/jxl/render_pipeline/stage_blending.cc (ProcessRow, ProcessPaddingRow),
-// lib/jxl/blending.cc:42-190 (PerformBlending, the colour channels of an image without an alpha channel),
+// lib/jxl/blending.cc:42-190 (PerformBlending, the colour channels of an image without extra channels: a frame of an
+// image with alpha or other extra channels goes to k_ec_blend, kernels_blend_ec.hip, which has this kernel's geometry),
 // lib/jxl/alpha.cc:82-93 (PerformMulBlending) and the save of dec_frame.cc:870-885 for frames saved after the colour
 // transform.
 //

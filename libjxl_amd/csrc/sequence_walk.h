@@ -86,7 +86,7 @@ struct SeqFrame {
   size_t toc_bit = 0;     // first bit behind it
   size_t end_bit = 0;     // first bit behind the frame's sections
   bool displayed = false;
-  bool blends = false;    // NeedsBlending (blending.cc:23-40), as far as the colour channels say
+  bool blends = false;    // NeedsBlending (blending.cc:23-40)
   bool save = false;      // a later frame reads its slot before the slot is overwritten
   uint32_t visible = 0, nonvisible = 0;  // the reference's counters while it decodes this frame (dec_frame.cc:160-168)
   uint32_t display_index = 0;
@@ -105,7 +105,9 @@ inline bool CanBeReferenced(const jxlhip_frame_header& fh) {
 
 // Every frame of the file: header, TOC, skip the sections.  JXLHIP_ERR_UNSUPPORTED with s->h.why for what the sequence
 // calls refuse, JXLHIP_ERR_BAD_STREAM for a file that ends inside the walk.
-inline int WalkSequence(const uint8_t* cs, size_t n, Sequence* s) {
+// blend_extra: the caller takes frames that need blending on an image with extra channels (JXLHIP_SEQUENCE_EXTRA_CHANNELS
+// / JXLHIP_OUT_BLEND_EXTRA_CHANNELS); without it they are refused, as before those flags existed.
+inline int WalkSequence(const uint8_t* cs, size_t n, Sequence* s, bool blend_extra = false) {
   ParsedHeaders& h = s->h;
   size_t pos = 0;
   jxlhip_image_info info{};
@@ -146,7 +148,8 @@ inline int WalkSequence(const uint8_t* cs, size_t n, Sequence* s) {
       for (uint32_t i = 0; i < ih.num_extra_channels && i < 4; i++)
         if (fh.ec_upsampling[i] != 1) return refuse("extra channels upsampled on their own");
       f.blends = fh.custom_size_or_origin || fh.blend_mode != JXLHIP_BLEND_REPLACE || fh.ec_blend_any;  // NeedsBlending
-      if (f.blends && ih.num_extra_channels != 0) return refuse("a frame that needs blending on an image with extra channels");
+      if (f.blends && ih.num_extra_channels != 0 && !blend_extra)
+        return refuse("a frame that needs blending on an image with extra channels");
       f.displayed = fh.is_last || fh.duration > 0;
     }
     if (f.displayed) {
@@ -180,11 +183,15 @@ inline int WalkSequence(const uint8_t* cs, size_t n, Sequence* s) {
     const uint32_t slot = f.fh.save_as_reference;
     for (size_t j = i + 1; j < s->frames.size() && !f.save; j++) {
       const SeqFrame& g = s->frames[j];
-      if (g.fh.frame_type == JXLHIP_FRAME_REGULAR && ((g.blends && g.fh.blend_source == slot) || (g.fh.flags & JXLHIP_FLAG_PATCHES))) f.save = true;
+      if (g.fh.frame_type == JXLHIP_FRAME_REGULAR && g.blends) {
+        bool reads = g.fh.blend_source == slot;  // (... or an extra channel does: each has a source of its own)
+        for (uint32_t e = 0; e < ih.num_extra_channels && e < 4; e++) reads = reads || g.fh.ec_blend_source[e] == slot;
+        if (reads) f.save = true;
+      }
+      if (g.fh.frame_type == JXLHIP_FRAME_REGULAR && (g.fh.flags & JXLHIP_FLAG_PATCHES)) f.save = true;
       if (CanBeReferenced(g.fh) && g.fh.save_as_reference == slot) break;
     }
-    // (On an image with extra channels nothing is ever saved: the two kinds of reader, a frame that blends and a frame
-    // with patches, are refused above.  A canvas holds the colour channels only.)
+    // (A saved frame of an image with extra channels takes them into its slot: jxlhip_set_blending_extra.)
   }
   return JXLHIP_OK;
 }

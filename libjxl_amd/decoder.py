@@ -226,6 +226,25 @@ class VarDctDecoder:
         _check(self.L, self.ctx, self.L.jxlhip_set_blending(self.ctx, C.byref(b)), "set_blending")
         self.image_size = (b.image_xsize, b.image_ysize)
 
+    def set_blending_extra(self, planes, channels, color_alpha_channel=0):
+        """The extra channels of the current blended frame, jxlhip_set_blending_extra (after set_blending): planes =
+        float32 host array [n, ysize, xsize] at the frame's own size, channels = one dict per channel with is_alpha,
+        alpha_associated, mode (abi.BLEND_*), alpha_channel, clamp, source (each defaults to 0), color_alpha_channel =
+        the alpha channel of the colour's kBlend / kAlphaWeightedAdd.  begin_frame and set_blending reset it."""
+        import numpy as np
+        a = np.ascontiguousarray(planes, dtype=np.float32)
+        assert a.ndim == 3 and a.shape[0] == len(channels) and 1 <= len(channels) <= 4, (tuple(a.shape), len(channels))
+        e = abi.BlendExtraParams()
+        e.num_extra_channels = len(channels)
+        e.color_alpha_channel = int(color_alpha_channel)
+        e.stride_floats = int(a.shape[2])
+        for i, ch in enumerate(channels):
+            for k in ("is_alpha", "alpha_associated", "mode", "alpha_channel", "clamp", "source"):
+                setattr(e.channel[i], k, int(ch.get(k, 0)))
+            e.planes[i] = a[i].ctypes.data
+        _check(self.L, self.ctx, self.L.jxlhip_set_blending_extra(self.ctx, C.byref(e)), "set_blending_extra")
+        self.sync()  # (`a` may go away)
+
     def set_tone_mapping(self, orig_nits, desired_nits=None, luminances=(0.2126, 0.7152, 0.0722), orig_transfer=abi.TF_PQ):
         """Tone mapping of the current frame, jxlhip_set_tone_mapping: an original mastered at orig_nits (transfer
         function orig_transfer, abi.TF_*) shown on a display of desired_nits, luminances = those of the OUTPUT
@@ -261,6 +280,29 @@ class VarDctDecoder:
         t = torch.empty((h.value, w.value, 3), dtype=torch.float32, device=f"cuda:{self.device}")
         _check(self.L, self.ctx, self.L.jxlhip_canvas_read(self.ctx, int(slot), C.c_void_p(t.data_ptr()), 3 * w.value,
                                                           C.byref(w), C.byref(h)), "canvas_read")
+        self.sync()
+        return t
+
+    def read_canvas_extra(self, slot, ec):
+        """Plane `ec` of the canvas of slot 0..3 (jxlhip_canvas_read_extra) as a float32 CUDA tensor [ysize, xsize]; None
+        when the slot holds no canvas or its canvas no such plane."""
+        w, h = C.c_uint32(), C.c_uint32()
+        _check(self.L, self.ctx, self.L.jxlhip_canvas_read_extra(self.ctx, int(slot), int(ec), None, 0, C.byref(w), C.byref(h)),
+               "canvas_read_extra")
+        if w.value == 0:
+            return None
+        t = torch.empty((h.value, w.value), dtype=torch.float32, device=f"cuda:{self.device}")
+        _check(self.L, self.ctx, self.L.jxlhip_canvas_read_extra(self.ctx, int(slot), int(ec), C.c_void_p(t.data_ptr()), w.value,
+                                                                C.byref(w), C.byref(h)), "canvas_read_extra")
+        self.sync()
+        return t
+
+    def read_frame_extra(self, ec):
+        """The blended plane of extra channel `ec` of the frame just decoded with set_blending_extra
+        (jxlhip_frame_extra_read), at image size, as a float32 CUDA tensor [ysize, xsize]."""
+        w, h = self.image_size
+        t = torch.empty((h, w), dtype=torch.float32, device=f"cuda:{self.device}")
+        _check(self.L, self.ctx, self.L.jxlhip_frame_extra_read(self.ctx, int(ec), C.c_void_p(t.data_ptr()), w), "frame_extra_read")
         self.sync()
         return t
 

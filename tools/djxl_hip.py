@@ -16,7 +16,8 @@ writes for screenshots and text) are rendered on the device.  Streams outside th
 wrapper can fall back to libjxl's djxl.  Prints Mpx/s of the decode call like djxl's SpeedStats.
 --frames: animations, layers, cropped and blended frames through jxlhip_decode_codestream_next: one file per DISPLAYED
 frame, OUT-000.ext, OUT-001.ext ... (coalesced, like djxl); the frames are blended on the device in the encoding of the
-output: the original's for .ppm (what the reference blends in), linear light for .pfm / .npy.  No alpha (.pam).
+output: the original's for .ppm / .pam (what the reference blends in), linear light for .pfm / .npy.  .pam writes every
+displayed frame of an image with alpha as RGBA, its alpha blended with the colour (opaque without an alpha channel).
 --display_nits N: the display's peak luminance, djxl's flag of that name (JxlDecoderSetDesiredIntensityTarget): a PQ
 original mastered brighter is tone-mapped to it on the device (jxlhip_codestream_set_display).
 --output_primaries: the pixels in these primaries (D65) instead of the original's, as JxlDecoderSetOutputColorProfile
@@ -62,8 +63,6 @@ def main():
     ap.add_argument("--display_nits", type=float, default=0.0)
     ap.add_argument("--output_primaries", choices=["srgb", "p3", "rec2100"])
     a = ap.parse_args()
-    if a.frames and os.path.splitext(a.output)[1].lower() == ".pam":
-        sys.exit("--frames writes .pfm, .npy or .ppm")
     import torch
     from libjxl_amd import VarDctDecoder, abi
     L = abi.load_library()
@@ -71,7 +70,7 @@ def main():
     info = abi.CodestreamInfo()
     seq = abi.SequenceInfo()
     if a.frames:
-        rc = L.jxlhip_codestream_sequence_info(blob, len(blob), C.byref(info), C.byref(seq))
+        rc = L.jxlhip_codestream_sequence_info_ex(blob, len(blob), abi.SEQUENCE_EXTRA_CHANNELS, C.byref(info), C.byref(seq))
     else:
         rc = L.jxlhip_codestream_basic_info(blob, len(blob), C.byref(info))
     if rc:
@@ -118,6 +117,7 @@ def main():
         out = torch.empty((h, w, 3), dtype=torch.float32, device="cuda")
         args = (1 | UNDO, None, out.data_ptr(), w * 12, 0)
     if a.frames:
+        args = (args[0] | abi.OUT_BLEND_EXTRA_CHANNELS,) + args[1:]  # (layers of an image with alpha are composited with it)
         stem, cursor, t0 = os.path.splitext(a.output)[0], C.c_uint64(0), time.perf_counter()
         for k in range(seq.num_displayed_frames):
             fr = abi.SequenceFrame()
