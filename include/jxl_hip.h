@@ -58,7 +58,8 @@ typedef enum {
   JXLHIP_ERR_BAD_STREAM = -5,  /* side info violates a format constraint */
   JXLHIP_ERR_STATE = -6,       /* call sequence error */
   JXLHIP_ERR_UNSUPPORTED = -7, /* valid stream feature outside this back-end */
-  JXLHIP_ERR_RANGE = -8        /* a coefficient does not fit the 16-bit buffers: use JXLHIP_COEFF_I32 */
+  JXLHIP_ERR_RANGE = -8,       /* a coefficient does not fit the 16-bit buffers: use JXLHIP_COEFF_I32 */
+  JXLHIP_ERR_NEED_MORE_INPUT = -9 /* jxlhip_decode_codestream_partial: the bytes end before anything can be drawn */
 } jxlhip_status;
 
 /* ACType, lib/jxl/dct_util.h:23; chosen per frame at lib/jxl/dec_frame.cc:421-431 */
@@ -344,6 +345,23 @@ JXLHIP_EXPORT int jxlhip_set_patches(jxlhip_ctx* ctx, const struct jxlhip_patche
  * upsampled frames are outside the back-end); the split calls refuse an upsampled frame. */
 JXLHIP_EXPORT int jxlhip_set_upsampling(jxlhip_ctx* ctx, uint32_t factor, const float* weights, uint32_t out_xsize,
                                         uint32_t out_ysize);
+/* DC-only groups of the current frame: what FrameDecoder::Flush draws for an AC group none of whose passes has arrived
+ * (dec_frame.cc:737-797, dec_group.cc:730-792).  mask = one byte per AC group (num_groups of them, host memory, copied
+ * by the call), non-zero = the group has no AC: its 256 x 256 pixels of the three XYB planes are its DC samples
+ * upsampled 8x with the format's 25-tap upsampler (render_pipeline/stage_upsampling.cc:147-276; the 5 x 5
+ * neighbourhoods read the neighbouring groups' DC and are mirrored at the edges of the DC image only) instead of the
+ * inverse transforms of its coefficient slots, which the call's decode zeroes on the device when they are the
+ * context's upload buffers (caller-owned coefficients, jxlhip_frame_set_inputs, are read as they are and must be
+ * readable; what phase 1 makes of them is overwritten).  weights8 = the 210 coded weights of the 8x upsampler
+ * (jxlhip_image_header::upsampling8_weights where custom_weights_mask has bit 2), NULL = the format's defaults.
+ * A frame with a mask takes the two-phase route whatever its size; k_dc_upsample8 (JXLHIP_KERNEL_DC_UPSAMPLE) runs
+ * between phase 1 and the filter launch, and as the last launch of jxlhip_decode_blocks, so that jxlhip_export_xyb shows
+ * its output; Gaborish, EPF and the colour stages follow as usual.  NULL or an all-zero mask: the frame takes exactly
+ * the path it takes without this call.  Call it after jxlhip_frame_begin, which resets it.
+ * JXLHIP_ERR_UNSUPPORTED (jxlhip_last_error names the case): a multi-device context, a stripe, and a mask together with
+ * jxlhip_set_noise, _splines, _patches, _upsampling, _blending or _alpha, whichever comes second (the setters and
+ * jxlhip_decode_frame check). */
+JXLHIP_EXPORT int jxlhip_set_dc_only_groups(jxlhip_ctx* ctx, const uint8_t* mask, const float* weights8);
 /* ---- blending: frame sequences (animations, layers, cropped frames) ----
  * The four slots of jxlhip_set_reference_frame hold one of two things each: the XYB reference frame patches copy from
  * (a frame saved BEFORE the colour transform), or a CANVAS: a frame saved AFTER the colour transform, as float RGB in
@@ -620,7 +638,8 @@ enum {
   JXLHIP_KERNEL_BLEND = 9,    /* blending (jxlhip_set_blending): k_blend behind the frame's whole path */
   JXLHIP_KERNEL_TONE_MAP = 10, /* tone mapping (jxlhip_set_tone_mapping): k_tone_map behind the frame's whole path */
   JXLHIP_KERNEL_BLEND_EC = 11, /* blending with extra channels (jxlhip_set_blending_extra): k_ec_blend in k_blend's place */
-  JXLHIP_KERNEL_COUNT_EX = 12 /* every slot; grows with each new one (new slots are appended here only) */
+  JXLHIP_KERNEL_DC_UPSAMPLE = 12, /* DC-only groups (jxlhip_set_dc_only_groups): k_dc_upsample8 between phase 1 and the filters */
+  JXLHIP_KERNEL_COUNT_EX = 13 /* every slot; grows with each new one (new slots are appended here only) */
 };
 /* A hint, not a contract: `frames_in_flight` = how many contexts the caller keeps busy on this device at the same time
  * (a pool of decoders over a queue of images; 1 = this context runs alone, the default).  It only moves the frame size

@@ -25,6 +25,8 @@
  * one regular last frame whose flags may include kPatches (jxlhip_patches_decode, blended on the device,
  * jxlhip_set_patches), of images without extra channels.  The four reference slots of the context are cleared at the
  * start of every call; the info struct describes the visible frame.
+ * A file that has not arrived completely is rendered by jxlhip_decode_codestream_partial below (groups without AC from
+ * their DC, upsampled 8x on the device: jxlhip_set_dc_only_groups); the other calls refuse truncated input.
  * Animations, layers, cropped and blended frames go through jxlhip_codestream_sequence_info /
  * jxlhip_decode_codestream_next below (blended on the device, jxlhip_set_blending); the single-frame calls refuse them.
  * Everything this front-end does not decode is refused with JXLHIP_ERR_UNSUPPORTED so that the caller can hand the
@@ -181,6 +183,39 @@ enum {
   JXLHIP_CODESTREAM_PHASES = 7
 };
 JXLHIP_EXPORT int jxlhip_codestream_phase_ms(const jxlhip_ctx* ctx, double* ms);
+
+/* ---- partial files: what a viewer shows before all of a file has arrived --------------------------------------------
+ * jxlhip_decode_codestream_partial renders the picture JxlDecoderFlushImage gives for the first `size` bytes of a file
+ * (FrameDecoder::Flush, dec_frame.cc:737-797).  The picture is a function of the set of COMPLETE sections alone:
+ *   - a section counts only when all its bytes are inside `size`; one cut in the middle is ignored;
+ *   - pass p of an AC group counts only when passes 0 .. p-1 of that group do (dec_frame.cc:625-635);
+ *   - a group with k >= 1 passes is decoded from those k (jxlhip_ac_group_decode_submit_passes); a group with none --
+ *     every group when the AC-global section is missing -- is drawn from its DC upsampled 8x
+ *     (jxlhip_set_dc_only_groups, with the image header's upsampling8_weights when it carries custom ones);
+ *   - Gaborish, EPF and the colour stages run over everything as usual; every pixel is written.
+ * JXLHIP_ERR_NEED_MORE_INPUT where JxlDecoderFlushImage returns JXL_DEC_ERROR: the headers, the TOC, DC global or any
+ * DC group is incomplete, and always for a frame of one section that is not complete.  A complete file takes exactly
+ * the path of jxlhip_decode_codestream and gives the same bytes (info->complete = 1).  The sticky display state
+ * (jxlhip_codestream_set_display) is honoured.  Arguments as jxlhip_decode_codestream.
+ * JXLHIP_ERR_UNSUPPORTED with the reason in jxlhip_last_error: whatever jxlhip_decode_codestream refuses; for an
+ * incomplete file also frames with noise, splines, patches or upsampling, and a 4-channel output of an image with extra
+ * channels (a 3-channel output of such an image is fine: the extra channels' bytes are skipped).
+ * jxlhip_decode_codestream, _extra and _next keep answering truncated input as before (JXLHIP_ERR_BAD_STREAM). */
+typedef struct jxlhip_partial_info {
+  uint32_t complete;        /* every section present: the call did exactly what jxlhip_decode_codestream does */
+  uint32_t num_passes, num_groups;
+  uint32_t groups_complete, groups_partial /* 1..num_passes-1 passes */, groups_dc_only;
+  uint32_t have_ac_global;
+  uint64_t bytes_used;      /* end of the last complete section that was drawn (an offset into the codestream) */
+} jxlhip_partial_info;
+/* Host only, no device: what the decode call below would draw from these bytes.  info may be NULL. */
+JXLHIP_EXPORT int jxlhip_codestream_partial_info(const uint8_t* data, size_t size, jxlhip_codestream_info* info,
+                                                 jxlhip_partial_info* partial);
+JXLHIP_EXPORT int jxlhip_decode_codestream_partial(jxlhip_ctx* ctx, jxlhip_parallel_runner runner, void* runner_opaque,
+                                                   const uint8_t* data, size_t size, uint32_t output_kind,
+                                                   const jxlhip_output_format* out_format, void* out, size_t out_stride,
+                                                   size_t out_plane_stride, jxlhip_codestream_info* info,
+                                                   jxlhip_partial_info* partial);
 
 /* ---- sequences of frames: animations, layers, cropped and blended frames --------------------------------------------
  * jxlhip_codestream_basic_info and jxlhip_decode_codestream[_extra] above keep refusing every file with more than one

@@ -10,9 +10,10 @@ _RUNNER_SO = os.path.join(_HERE, "csrc", "libjxl_threads_hip.so")
 KERNEL_COUNT = 8
 KERNEL_NAMES = ["prepare", "blocks", "filters", "fused", "epf0", "noise", "splines", "upsample"]
 # jxlhip_profile_read_ex: the slots above, then those added since (JXLHIP_KERNEL_PATCHES = 8, JXLHIP_KERNEL_BLEND = 9,
-# JXLHIP_KERNEL_TONE_MAP = 10, JXLHIP_KERNEL_BLEND_EC = 11)
-KERNEL_COUNT_EX = 12
-KERNEL_NAMES_EX = KERNEL_NAMES + ["patches", "blend", "tone_map", "blend_ec"]
+# JXLHIP_KERNEL_TONE_MAP = 10, JXLHIP_KERNEL_BLEND_EC = 11, JXLHIP_KERNEL_DC_UPSAMPLE = 12)
+KERNEL_COUNT_EX = 13
+KERNEL_NAMES_EX = KERNEL_NAMES + ["patches", "blend", "tone_map", "blend_ec", "dc_upsample"]
+ERR_NEED_MORE_INPUT = -9  # JXLHIP_ERR_NEED_MORE_INPUT (jxlhip_decode_codestream_partial)
 TONE_MAPPING_CONSTANTS = 18  # JXLHIP_TONE_MAPPING_CONSTANTS
 # BlendMode (JXLHIP_BLEND_*) and jxlhip_blend_params::save_slot's "none"
 BLEND_REPLACE, BLEND_ADD, BLEND_BLEND, BLEND_ALPHA_WEIGHTED_ADD, BLEND_MUL = range(5)
@@ -185,6 +186,12 @@ class CodestreamInfo(C.Structure):
                 ("upsampling", C.c_uint32)]
 
 
+class PartialInfo(C.Structure):
+    """jxlhip_partial_info"""
+    _fields_ = [(n, C.c_uint32) for n in ("complete", "num_passes", "num_groups", "groups_complete", "groups_partial",
+                                          "groups_dc_only", "have_ac_global")] + [("bytes_used", C.c_uint64)]
+
+
 class SequenceInfo(C.Structure):
     """jxlhip_sequence_info"""
     _fields_ = [(n, C.c_uint32) for n in ("have_animation", "tps_numerator", "tps_denominator", "num_loops", "have_timecodes",
@@ -294,7 +301,7 @@ EXPORTS = [
     "jxlhip_dequant_table_offset", "jxlhip_status_string", "jxlhip_create", "jxlhip_create_ex", "jxlhip_create_multi",
     "jxlhip_destroy", "jxlhip_last_error", "jxlhip_debug_reload_env", "jxlhip_set_stream",
     "jxlhip_frame_begin", "jxlhip_frame_set_inputs", "jxlhip_upload_side_info",
-    "jxlhip_submit_group", "jxlhip_set_alpha", "jxlhip_set_noise", "jxlhip_noise_rng_state", "jxlhip_set_splines", "jxlhip_set_upsampling", "jxlhip_set_reference_frame", "jxlhip_set_patches", "jxlhip_set_blending", "jxlhip_set_tone_mapping", "jxlhip_tone_mapping_constants", "jxlhip_canvas_read", "jxlhip_set_blending_extra", "jxlhip_canvas_read_extra", "jxlhip_frame_extra_read", "jxlhip_profile_read_ex", "jxlhip_alpha_staging", "jxlhip_decode_blocks", "jxlhip_halo_rows",
+    "jxlhip_submit_group", "jxlhip_set_alpha", "jxlhip_set_noise", "jxlhip_noise_rng_state", "jxlhip_set_splines", "jxlhip_set_upsampling", "jxlhip_set_dc_only_groups", "jxlhip_set_reference_frame", "jxlhip_set_patches", "jxlhip_set_blending", "jxlhip_set_tone_mapping", "jxlhip_tone_mapping_constants", "jxlhip_canvas_read", "jxlhip_set_blending_extra", "jxlhip_canvas_read_extra", "jxlhip_frame_extra_read", "jxlhip_profile_read_ex", "jxlhip_alpha_staging", "jxlhip_decode_blocks", "jxlhip_halo_rows",
     "jxlhip_halo_export", "jxlhip_halo_import", "jxlhip_decode_filters", "jxlhip_decode_filters_rows", "jxlhip_stripe_begin",
     "jxlhip_stripe_finish", "jxlhip_decode_frame",
     "jxlhip_decode_frame_host", "jxlhip_decode_frame_pinned",
@@ -319,6 +326,7 @@ EXPORTS = [
     "jxlhip_codestream_basic_info", "jxlhip_decode_codestream", "jxlhip_decode_codestream_extra",
     "jxlhip_codestream_icc_profile", "jxlhip_codestream_phase_ms", "jxlhip_codestream_sequence_info", "jxlhip_codestream_sequence_info_ex",
     "jxlhip_decode_codestream_next", "jxlhip_codestream_set_display", "jxlhip_codestream_display_info",
+    "jxlhip_codestream_partial_info", "jxlhip_decode_codestream_partial",
 ]
 
 
@@ -376,6 +384,7 @@ def load_library():
     L.jxlhip_splines_segments.argtypes = [vp, u32, u32, C.c_float, C.c_float, vp, sz, C.POINTER(sz)]
     L.jxlhip_set_splines.argtypes = [vp, vp]
     L.jxlhip_set_upsampling.argtypes = [vp, u32, C.POINTER(C.c_float), u32, u32]
+    L.jxlhip_set_dc_only_groups.argtypes = [vp, vp, C.POINTER(C.c_float)]
     L.jxlhip_patches_decode.argtypes = [vp, sz, C.POINTER(sz), u32, u32, u32, vp, C.POINTER(vp)]
     L.jxlhip_patches_from_list.argtypes = [u32, vp, u32, vp, u32, u32, vp, C.POINTER(vp)]
     L.jxlhip_patches_list.argtypes = [vp, C.POINTER(u32), C.POINTER(u32), C.POINTER(u32), vp, vp]
@@ -457,6 +466,9 @@ def load_library():
     L.jxlhip_codestream_set_display.argtypes = [vp, C.POINTER(Display)]
     L.jxlhip_codestream_display_info.argtypes = [vp, sz, C.POINTER(Display), C.POINTER(CodestreamInfo), C.POINTER(C.c_char_p)]
     L.jxlhip_codestream_phase_ms.argtypes = [vp, C.POINTER(C.c_double)]
+    L.jxlhip_codestream_partial_info.argtypes = [vp, sz, C.POINTER(CodestreamInfo), C.POINTER(PartialInfo)]
+    L.jxlhip_decode_codestream_partial.argtypes = [vp, vp, vp, vp, sz, u32, vp, vp, sz, sz, C.POINTER(CodestreamInfo),
+                                                   C.POINTER(PartialInfo)]
     L.jxlhip_decode_codestream_extra.argtypes = [vp, vp, vp, vp, sz, u32, vp, vp, sz, sz, C.POINTER(vp), u32, sz,
                                                  C.POINTER(CodestreamInfo)]
     L.jxlhip_modular_ac_group_decode_f32_strided.argtypes = [vp, vp, u32, u32, vp, sz, C.POINTER(sz), vp, u32, vp, vp]

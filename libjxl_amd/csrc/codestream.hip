@@ -11,8 +11,10 @@ namespace {
 // ---- container (decode.cc:1639-1672 ParseBoxHeader, 1674-2020 HandleBoxes): the codestream is the
 // payload of the one jxlc box, or the concatenation of the jxlp payloads (4-byte big-endian index in
 // front of each, bit 31 = last) in index order.  Out-of-order jxlp boxes are put in order.
+// partial (jxlhip_decode_codestream_partial): the file may end anywhere -- a box cut short gives the payload that is there
+// and ends the walk, and bytes that are the beginning of a signature are JXLHIP_ERR_NEED_MORE_INPUT.
 int ExtractCodestream(const uint8_t* data, size_t size, std::vector<uint8_t>* storage, const uint8_t** cs,
-                      size_t* cs_size, bool* container) {
+                      size_t* cs_size, bool* container, bool partial = false) {
   static const uint8_t kSig[12] = {0, 0, 0, 0xC, 'J', 'X', 'L', ' ', 0xD, 0xA, 0x87, 0xA};
   *container = false;
   if (size >= 2 && data[0] == 0xFF && data[1] == 0x0A) {
@@ -20,6 +22,8 @@ int ExtractCodestream(const uint8_t* data, size_t size, std::vector<uint8_t>* st
     *cs_size = size;
     return JXLHIP_OK;
   }
+  if (partial && size < 12 && (size == 0 || (size == 1 && data[0] == 0xFF) || memcmp(data, kSig, size) == 0))
+    return JXLHIP_ERR_NEED_MORE_INPUT;
   if (size < 12 || memcmp(data, kSig, 12) != 0) return JXLHIP_ERR_BAD_STREAM;
   *container = true;
   struct Part {
@@ -30,27 +34,39 @@ int ExtractCodestream(const uint8_t* data, size_t size, std::vector<uint8_t>* st
   std::vector<Part> parts;
   bool have_jxlc = false, have_last = false;
   size_t pos = 0;
-  while (pos < size) {
-    if (size - pos < 8) return JXLHIP_ERR_BAD_STREAM;
+  bool cut = false;  // (partial) the box at hand ends behind the file
+  while (pos < size && !cut) {
+    if (size - pos < 8) {
+      if (partial) break;
+      return JXLHIP_ERR_BAD_STREAM;
+    }
     uint64_t box = ((uint64_t)data[pos] << 24) | ((uint64_t)data[pos + 1] << 16) | ((uint64_t)data[pos + 2] << 8) | data[pos + 3];
     const uint8_t* type = data + pos + 4;
     size_t header = 8;
     if (box == 1) {  // 64-bit size follows
-      if (size - pos < 16) return JXLHIP_ERR_BAD_STREAM;
+      if (size - pos < 16) {
+        if (partial) break;
+        return JXLHIP_ERR_BAD_STREAM;
+      }
       box = 0;
       for (int i = 0; i < 8; i++) box = (box << 8) | data[pos + 8 + i];
       header = 16;
     }
     uint64_t payload;
     if (box == 0) payload = size - pos - header;  // runs to the end of the file
-    else if (box < header || box - header > size - pos - header) return JXLHIP_ERR_BAD_STREAM;
-    else payload = box - header;
+    else if (box < header) return JXLHIP_ERR_BAD_STREAM;
+    else if (box - header > size - pos - header) {
+      if (!partial) return JXLHIP_ERR_BAD_STREAM;
+      payload = size - pos - header;
+      cut = true;
+    } else payload = box - header;
     const uint8_t* p = data + pos + header;
     if (!memcmp(type, "jxlc", 4)) {
       if (have_jxlc || !parts.empty()) return JXLHIP_ERR_BAD_STREAM;  // "there can only be one jxlc box"
       have_jxlc = true;
       parts.push_back({0u, p, (size_t)payload});
     } else if (!memcmp(type, "jxlp", 4)) {
+      if (cut && payload < 4) break;
       if (have_jxlc || payload < 4) return JXLHIP_ERR_BAD_STREAM;
       const uint32_t idx = ((uint32_t)p[0] << 24) | ((uint32_t)p[1] << 16) | ((uint32_t)p[2] << 8) | p[3];
       if (idx & 0x80000000u) {
@@ -62,7 +78,7 @@ int ExtractCodestream(const uint8_t* data, size_t size, std::vector<uint8_t>* st
     // ftyp, jxll, Exif, xml, jumb, brob, jbrd ...: not pixels
     pos += header + payload;
   }
-  if (parts.empty()) return JXLHIP_ERR_BAD_STREAM;
+  if (parts.empty()) return partial ? JXLHIP_ERR_NEED_MORE_INPUT : JXLHIP_ERR_BAD_STREAM;
   if (parts.size() == 1 && have_jxlc) {
     *cs = parts[0].p;
     *cs_size = parts[0].n;
@@ -266,6 +282,46 @@ void ModularGroupsFunc(void* opaque, uint32_t g, size_t) {
       j->status.compare_exchange_strong(expected, rc);
       return;
     }
+  }
+}
+
+// jxlhip_decode_codestream_partial: which sections of the frame are inside the bytes (PlanPartial)
+struct PartialPlan {
+  jxlhip_partial_info info{};
+  std::vector<uint8_t> passes_of;  // per AC group: how many leading passes are complete (0 = drawn from its DC)
+};
+
+// jxlhip_decode_codestream_partial: the AC groups of an incomplete frame, each with the passes the plan counts
+struct PartialGroupsJob {
+  jxlhip_ctx* c;
+  const PartialPlan* plan;
+  uint32_t num_groups;
+  jxlhip_ac_pass* const* passes;
+  const uint32_t* shifts;
+  const uint8_t* acs;
+  const int32_t* raw_quant;
+  const uint8_t* quant_dc;
+  const uint8_t* const* sections;
+  const size_t* sizes;
+  std::atomic<int> status{JXLHIP_OK};
+};
+void PartialGroupsFunc(void* opaque, uint32_t g, size_t) {
+  PartialGroupsJob* j = static_cast<PartialGroupsJob*>(opaque);
+  const uint32_t k = j->plan->passes_of[g];
+  if (k == 0 || j->status.load(std::memory_order_relaxed) != JXLHIP_OK) return;
+  const jxlhip_ac_pass* pp[11];
+  const uint8_t* data[11];
+  size_t sizes[11], pos[11];
+  for (uint32_t p = 0; p < k; p++) {
+    pp[p] = j->passes[p];
+    data[p] = j->sections[(size_t)p * j->num_groups + g];
+    sizes[p] = j->sizes[(size_t)p * j->num_groups + g];
+    pos[p] = 0;
+  }
+  const int rc = jxlhip_ac_group_decode_submit_passes(j->c, k, pp, j->shifts, g, j->acs, j->raw_quant, j->quant_dc, data, sizes, pos);
+  if (rc != JXLHIP_OK) {
+    int expected = JXLHIP_OK;
+    j->status.compare_exchange_strong(expected, rc);
   }
 }
 
@@ -644,6 +700,9 @@ struct FrameCall {
   uint32_t out_xsize = 0, out_ysize = 0;  // the size an upsampled frame comes out at: the image's, or a cropped frame's own
   uint32_t noise_visible = 1, noise_nonvisible = 0;  // PassesDecoderState::visible_frame_index / nonvisible_frame_index
   const jxlhip_blend_params* blend = nullptr;
+  // an incomplete file (a plain frame of more than one section): the sections the plan counts are decoded, the
+  // groups without AC are drawn from their DC (jxlhip_set_dc_only_groups); nullptr = every section is there
+  const PartialPlan* partial = nullptr;
 };
 static int DecodeFrameAt(jxlhip_ctx* c, const uint8_t* cs, size_t n, const ParsedHeaders& h, const jxlhip_frame_header& fh,
                          size_t frame_bit_pos, const FrameCall& fc, PhaseClock& clock, bool verbose, jxlhip_codestream_info* info_p,
@@ -743,8 +802,8 @@ static int DecodeFrameAt(jxlhip_ctx* c, const uint8_t* cs, size_t n, const Parse
   uint64_t total = 0;
   if ((rc = jxlhip_toc_decode(cs, n, &pos, ntoc, off.data(), sz.data(), &total))) return Fail(c, rc, "invalid TOC");
   const size_t base = pos / 8;
-  if (total > n - base) return Fail(c, JXLHIP_ERR_BAD_STREAM, "truncated frame: %llu section bytes, %zu present",
-                                    (unsigned long long)total, n - base);
+  if (total > n - base && !fc.partial) return Fail(c, JXLHIP_ERR_BAD_STREAM, "truncated frame: %llu section bytes, %zu present",
+                                                   (unsigned long long)total, n - base);
   auto sec = [&](uint32_t i) { return cs + base + off[i]; };
   const bool single = ntoc == 1;
 
@@ -896,7 +955,9 @@ static int DecodeFrameAt(jxlhip_ctx* c, const uint8_t* cs, size_t n, const Parse
       job.sizes = dsz.data();
       job.ctx_map = &dcg.block_ctx_map;
       job.qctx = qctx.data();
-      if (runner) {
+      if (runner && fc.partial) {  // the DC groups alone: AC global may not be there, and the AC groups follow the plan
+        if (runner(runner_opaque, &job, DcInit, DcFunc, 0, ndc) != 0) return Fail(c, JXLHIP_ERR_STATE, "parallel runner failed");
+      } else if (runner) {
         // (the AC-global section rides along as one more unit: DcJob)
         job.ag_data = sec(1 + ndc);
         job.ag_size = sz[1 + ndc];
@@ -1010,7 +1071,7 @@ static int DecodeFrameAt(jxlhip_ctx* c, const uint8_t* cs, size_t n, const Parse
   // ---- AC global: dequant encodings, histograms and coefficient orders of every pass (unless it rode along above)
   if (single) {
     rc = jxlhip_ac_global_decode_at(sec(0), sz[0], &spos, ng, np, used_acs, &dcg.block_ctx_map, enc, &num_hist, passes.p);
-  } else if (!ac_global_done) {
+  } else if (!ac_global_done && (!fc.partial || fc.partial->info.have_ac_global)) {
     size_t bits = 0;
     rc = jxlhip_ac_global_decode(sec(1 + ndc), sz[1 + ndc], ng, np, used_acs, &dcg.block_ctx_map, enc, &num_hist, passes.p, &bits);
   }
@@ -1050,16 +1111,41 @@ static int DecodeFrameAt(jxlhip_ctx* c, const uint8_t* cs, size_t n, const Parse
       const int smooth = !(fh.flags & JXLHIP_FLAG_SKIP_ADAPTIVE_DC_SMOOTHING);
       if ((rc = jxlhip_dequant_dc_groups(c, q3, d3, dcg.dc_quant, cfl_x, cfl_b, smooth, prec.data()))) return rc;
     }
-    if ((rc = jxlhip_dequant_tables(c, enc, (float*)in.dequant_table))) return rc;
+    // (without AC global no coefficient is dequantised: phase 1 runs over zeroes with the default tables)
+    const bool have_enc = !fc.partial || fc.partial->info.have_ac_global;
+    if ((rc = have_enc ? jxlhip_dequant_tables(c, enc, (float*)in.dequant_table) : jxlhip_default_dequant_tables(c, (float*)in.dequant_table))) return rc;
     ApplyInputs(c, &in);
     c->have_inputs = true;
     c->blocks_done = false;
     DropPrepared(c);  // (new maps, and used_acs above)
+    if (fc.partial) {  // in front of the prepare: a frame with DC-only groups is two-phase
+      std::vector<uint8_t> mask(ng);
+      for (uint32_t g = 0; g < ng; g++) mask[g] = fc.partial->passes_of[g] == 0;
+      if ((rc = jxlhip_set_dc_only_groups(c, mask.data(), (ih.custom_weights_mask & 4u) ? ih.upsampling8_weights : nullptr))) return rc;
+    }
     if ((rc = PrepareAhead(c, (fh.flags & JXLHIP_FLAG_NOISE) || splines || patches || fh.upsampling > 1))) return rc;  // under the AC groups' entropy decode instead of in front of the frame's kernels
     clock.Mark(JXLHIP_PHASE_SIDE_INFO);
     // AC groups on the runner: entropy decode into pinned staging slots + uploads
     if (ac_in_pipeline) {
       rc = JXLHIP_OK;  // (decoded and submitted inside the pipelined call)
+    } else if (fc.partial) {  // every group the passes it has
+      PartialGroupsJob pg;
+      pg.c = c;
+      pg.plan = fc.partial;
+      pg.num_groups = ng;
+      pg.passes = passes.p;
+      pg.shifts = shifts.data();
+      pg.acs = acs.data();
+      pg.raw_quant = raw_quant.data();
+      pg.quant_dc = qctx.data();
+      pg.sections = asec.data();
+      pg.sizes = asz.data();
+      if (runner) {
+        if (runner(runner_opaque, &pg, ModularGroupsInit, PartialGroupsFunc, 0, ng) != 0) return Fail(c, JXLHIP_ERR_STATE, "parallel runner failed");
+      } else {
+        for (uint32_t g = 0; g < ng; g++) PartialGroupsFunc(&pg, g, 0);
+      }
+      rc = pg.status.load();
     } else if (single) {
       const uint8_t* d1[11];
       size_t s1[11], b1[11];
@@ -1390,6 +1476,171 @@ int jxlhip_decode_codestream_next(jxlhip_ctx* c, jxlhip_parallel_runner runner, 
                                     out_plane_stride, info_out, frame_out);
     // an early return may leave uploads of a frame queued: nothing of it may still be in flight when the caller frees
     // its buffers
+    if (rc != JXLHIP_OK && c && !c->multi && c->stream) (void)hipStreamSynchronize(c->stream);
+    return rc;
+  } catch (const std::bad_alloc&) {
+    return c ? Fail(c, JXLHIP_ERR_OUT_OF_MEMORY, "host allocation failed while decoding the codestream") : JXLHIP_ERR_OUT_OF_MEMORY;
+  }
+}
+
+// ---- partial files (jxlhip_codestream_partial_info, jxlhip_decode_codestream_partial) --------------------------------
+
+namespace {
+
+// Which sections of the visible frame lie completely inside the n bytes (FrameDecoder::Flush's view of the file,
+// dec_frame.cc:737-797; a pass counts only behind the passes before it, :625-635).  JXLHIP_ERR_NEED_MORE_INPUT where the
+// reference's flush fails: the TOC, DC global or a DC group is incomplete, or the frame has one section and is not whole.
+int PlanPartial(const uint8_t* cs, size_t n, const ParsedHeaders& h, PartialPlan* plan) {
+  const jxlhip_frame_header& fh = h.fh;
+  if (fh.num_groups > (1u << 22) || fh.num_passes == 0 || fh.num_passes > 11) return JXLHIP_ERR_UNSUPPORTED;
+  const uint32_t ng = (uint32_t)fh.num_groups, ndc = (uint32_t)fh.num_dc_groups, np = fh.num_passes;
+  const uint32_t ntoc = (uint32_t)fh.num_toc_entries;
+  std::vector<uint64_t> off(ntoc);
+  std::vector<uint32_t> sz(ntoc);
+  uint64_t total = 0;
+  size_t pos = h.frame_bit_pos;
+  if (jxlhip_toc_decode(cs, n, &pos, ntoc, off.data(), sz.data(), &total)) return JXLHIP_ERR_NEED_MORE_INPUT;
+  const size_t base = pos / 8;
+  if (base > n) return JXLHIP_ERR_NEED_MORE_INPUT;
+  jxlhip_partial_info& pi = plan->info;
+  memset(&pi, 0, sizeof(pi));
+  pi.num_passes = np;
+  pi.num_groups = ng;
+  plan->passes_of.assign(ng, 0);
+  if (total <= n - base) {
+    pi.complete = 1;
+    pi.groups_complete = ng;
+    pi.have_ac_global = 1;
+    pi.bytes_used = base + total;
+    plan->passes_of.assign(ng, (uint8_t)np);
+    return JXLHIP_OK;
+  }
+  if (ntoc == 1) return JXLHIP_ERR_NEED_MORE_INPUT;
+  if (ntoc != 2 + ndc + (uint64_t)np * ng) return JXLHIP_ERR_BAD_STREAM;
+  uint64_t used = 0;
+  auto have = [&](uint32_t i) {
+    const uint64_t end = base + off[i] + sz[i];
+    if (end > n) return false;
+    used = std::max(used, end);
+    return true;
+  };
+  for (uint32_t i = 0; i <= ndc; i++)
+    if (!have(i)) return JXLHIP_ERR_NEED_MORE_INPUT;
+  pi.have_ac_global = have(1 + ndc) ? 1u : 0u;
+  for (uint32_t g = 0; g < ng; g++) {
+    uint32_t k = 0;
+    while (pi.have_ac_global && k < np && have(2 + ndc + k * ng + g)) k++;
+    plan->passes_of[g] = (uint8_t)k;
+    if (k == np) pi.groups_complete++;
+    else if (k) pi.groups_partial++;
+    else pi.groups_dc_only++;
+  }
+  pi.bytes_used = used;
+  return JXLHIP_OK;
+}
+
+// container, headers and the plan; *why names a refusal
+int ReadPartial(const uint8_t* data, size_t size, std::vector<uint8_t>* storage, const uint8_t** cs, size_t* n, bool* container,
+                ParsedHeaders* h, PartialPlan* plan, const char** why) {
+  *why = "";
+  int rc = ExtractCodestream(data, size, storage, cs, n, container, true);
+  if (rc) return rc;
+  // headers that end early do not parse: which of the two it is only more bytes can tell
+  rc = ParseHeaders(*cs, *n, h);
+  if (rc == JXLHIP_ERR_BAD_STREAM) return JXLHIP_ERR_NEED_MORE_INPUT;
+  if (rc == JXLHIP_ERR_UNSUPPORTED) *why = h->why[0] ? h->why : "stream uses features outside the VarDCT back-end";
+  if (rc) return rc;
+  if ((rc = PlanPartial(*cs, *n, *h, plan)) == JXLHIP_ERR_UNSUPPORTED) *why = "frame too large";
+  return rc;
+}
+
+}  // namespace
+
+int jxlhip_codestream_partial_info(const uint8_t* data, size_t size, jxlhip_codestream_info* info, jxlhip_partial_info* partial) {
+  if (!data || !partial) return JXLHIP_ERR_INVALID_ARGUMENT;
+  try {
+    std::vector<uint8_t> storage;
+    const uint8_t* cs = nullptr;
+    size_t n = 0;
+    bool container = false;
+    ParsedHeaders h;
+    PartialPlan plan;
+    const char* why;
+    const int rc = ReadPartial(data, size, &storage, &cs, &n, &container, &h, &plan, &why);
+    if (rc) return rc;
+    if (info) FillInfo(h, container, info);
+    *partial = plan.info;
+    return JXLHIP_OK;
+  } catch (const std::bad_alloc&) {
+    return JXLHIP_ERR_OUT_OF_MEMORY;
+  }
+}
+
+static int DecodePartialImpl(jxlhip_ctx* c, jxlhip_parallel_runner runner, void* runner_opaque, const uint8_t* data, size_t size,
+                             uint32_t output_kind, const jxlhip_output_format* out_format, void* out, size_t out_stride,
+                             size_t out_plane_stride, jxlhip_codestream_info* info_out, jxlhip_partial_info* partial_out) {
+  const bool undo_orientation = (output_kind & JXLHIP_OUT_UNDO_ORIENTATION) != 0;
+  const uint32_t kind = output_kind & ~(uint32_t)JXLHIP_OUT_UNDO_ORIENTATION;
+  if (!c || !data || !out || kind > JXLHIP_OUT_PACKED || (kind == JXLHIP_OUT_PACKED && !out_format)) return JXLHIP_ERR_INVALID_ARGUMENT;
+  JXLHIP_NO_MULTI(c);
+  std::vector<uint8_t> storage;
+  const uint8_t* cs = nullptr;
+  size_t n = 0;
+  bool container = false;
+  ParsedHeaders h;
+  PartialPlan plan;
+  const char* why;
+  int rc = ReadPartial(data, size, &storage, &cs, &n, &container, &h, &plan, &why);
+  if (rc == JXLHIP_ERR_NEED_MORE_INPUT) return Fail(c, rc, "the headers, the TOC, DC global or a DC group is incomplete");
+  if (rc) return Fail(c, rc, "%s", why[0] ? why : "not a JPEG XL codestream or container");
+  if (plan.info.complete) {  // exactly what jxlhip_decode_codestream does
+    if ((rc = jxlhip_decode_codestream(c, runner, runner_opaque, data, size, output_kind, out_format, out, out_stride, out_plane_stride, info_out)))
+      return rc;
+    if (partial_out) *partial_out = plan.info;
+    return JXLHIP_OK;
+  }
+  const jxlhip_frame_header& fh = h.fh;
+  // FrameDecoder::Flush draws none of these on a partial frame the way the whole frame has them: named follow-ups
+  if (fh.flags & JXLHIP_FLAG_NOISE) return Fail(c, JXLHIP_ERR_UNSUPPORTED, "a partial file of a frame with noise");
+  if (fh.flags & JXLHIP_FLAG_SPLINES) return Fail(c, JXLHIP_ERR_UNSUPPORTED, "a partial file of a frame with splines");
+  if (fh.flags & JXLHIP_FLAG_PATCHES) return Fail(c, JXLHIP_ERR_UNSUPPORTED, "a partial file of a frame with patches");
+  if (fh.upsampling != 1) return Fail(c, JXLHIP_ERR_UNSUPPORTED, "a partial file of an upsampled frame");
+  if (h.ih.num_extra_channels != 0 && kind == JXLHIP_OUT_PACKED && out_format->num_channels == 4)
+    return Fail(c, JXLHIP_ERR_UNSUPPORTED, "a partial file of an image with extra channels into a 4-channel output");
+  for (uint32_t slot = 0; slot < 4; slot++)
+    if ((rc = jxlhip_set_reference_frame(c, slot, 0, 0, nullptr, 0, 0))) return rc;
+  PhaseClock clock(c->cs_phase_ms);
+  const bool verbose = jxlhip_env::Get().codestream_verbose.load(std::memory_order_relaxed);
+  g_upload_wait_on.store(verbose);
+  if ((rc = ApplyDisplay(c, &h))) return rc;
+  jxlhip_codestream_info info;
+  FillInfo(h, container, &info);
+  FrameCall fc;
+  fc.runner = runner;
+  fc.runner_opaque = runner_opaque;
+  fc.output_kind = kind;
+  fc.undo_orientation = undo_orientation;
+  fc.out_format = out_format;
+  fc.out = out;
+  fc.out_stride = out_stride;
+  fc.out_plane_stride = out_plane_stride;
+  fc.out_xsize = h.ih.xsize;
+  fc.out_ysize = h.ih.ysize;
+  fc.partial = &plan;
+  if ((rc = DecodeFrameAt(c, cs, n, h, h.fh, h.frame_bit_pos, fc, clock, verbose, &info, nullptr))) return rc;
+  if (info_out) *info_out = info;
+  if (partial_out) *partial_out = plan.info;
+  return JXLHIP_OK;
+}
+
+int jxlhip_decode_codestream_partial(jxlhip_ctx* c, jxlhip_parallel_runner runner, void* runner_opaque, const uint8_t* data,
+                                     size_t size, uint32_t output_kind, const jxlhip_output_format* out_format, void* out,
+                                     size_t out_stride, size_t out_plane_stride, jxlhip_codestream_info* info_out,
+                                     jxlhip_partial_info* partial_out) {
+  try {
+    const int rc = DecodePartialImpl(c, runner, runner_opaque, data, size, output_kind, out_format, out, out_stride,
+                                     out_plane_stride, info_out, partial_out);
+    // (as jxlhip_decode_codestream_extra: nothing of an abandoned frame may still be in flight)
     if (rc != JXLHIP_OK && c && !c->multi && c->stream) (void)hipStreamSynchronize(c->stream);
     return rc;
   } catch (const std::bad_alloc&) {

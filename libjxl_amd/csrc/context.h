@@ -331,6 +331,13 @@ struct jxlhip_ctx {
   bool tm_on = false;
   ToneMapConstants tm_k{};
   DevBuf<float> tm_planes;
+  // jxlhip_set_dc_only_groups: the AC groups of the current frame that are drawn from their DC (frame_begin resets
+  // dc_only_on); dc_only_mask = one byte per group, dc_only_weights = the 8x kernels as k_dc_upsample8 loads them
+  // (DcUpsampleWeights), dc_only_host = the host copy of the mask (which coefficient slots DecodeBegin zeroes)
+  bool dc_only_on = false;
+  DevBuf<uint8_t> dc_only_mask;
+  DevBuf<float> dc_only_weights;
+  std::vector<uint8_t> dc_only_host;
   // jxlhip_codestream_set_display: sticky on the context (0 = not set), read by the whole-file decode calls
   float display_nits = 0.0f;
   uint32_t display_primaries = 0, display_white_point = 0;

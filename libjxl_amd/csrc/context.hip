@@ -86,6 +86,7 @@ const char* jxlhip_status_string(int status) {
     case JXLHIP_ERR_STATE: return "call sequence error";
     case JXLHIP_ERR_UNSUPPORTED: return "stream feature outside this back-end";
     case JXLHIP_ERR_RANGE: return "coefficient outside the 16-bit range: redo the frame with JXLHIP_COEFF_I32";
+    case JXLHIP_ERR_NEED_MORE_INPUT: return "the bytes end before anything can be drawn";
     default: return "unknown status";
   }
 }
@@ -358,6 +359,7 @@ int jxlhip_frame_begin(jxlhip_ctx* c, const jxlhip_frame_params* p) {
   c->blend_ec_on = false;
   c->frame_ec_n = 0;
   c->tm_on = false;
+  c->dc_only_on = false;
   return JXLHIP_OK;
 }
 
@@ -419,6 +421,7 @@ int jxlhip_set_alpha(jxlhip_ctx* c, const float* host_plane, size_t stride_float
   if (c->ups_factor > 1) return Fail(c, JXLHIP_ERR_UNSUPPORTED, "alpha on an upsampled frame");
   if (c->patches_on) return Fail(c, JXLHIP_ERR_UNSUPPORTED, "alpha on a frame with patches (they would have to blend it)");
   if (c->blend_on) return Fail(c, JXLHIP_ERR_UNSUPPORTED, "alpha on a blended frame (blending extra channels is not in the back-end)");
+  if (c->dc_only_on) return Fail(c, JXLHIP_ERR_UNSUPPORTED, "alpha on a frame with DC-only groups");
   if (c->multi) {  // every stripe takes its own rows of the plane
     for (MultiChild& k : c->multi->kids) {
       const int rc = jxlhip_set_alpha(k.ctx, host_plane, stride_floats);
@@ -448,6 +451,7 @@ int jxlhip_set_noise(jxlhip_ctx* c, const float lut[8], uint32_t visible_frame_i
   if (!c->have_frame) return Fail(c, JXLHIP_ERR_STATE, "set_noise before frame_begin");
   if (c->f.group_y0 != 0 || c->f.group_rows != c->f.ysg) return Fail(c, JXLHIP_ERR_UNSUPPORTED, "noise with stripes");
   if (c->p.undo_orientation > 1) return Fail(c, JXLHIP_ERR_UNSUPPORTED, "noise with undo_orientation %u", c->p.undo_orientation);
+  if (c->dc_only_on) return Fail(c, JXLHIP_ERR_UNSUPPORTED, "noise on a frame with DC-only groups");
   bool any = false;
   for (int i = 0; i < 8; i++) any = any || fabsf(lut[i]) > 1e-3f;
   c->noise_on = false;
@@ -484,6 +488,7 @@ int jxlhip_set_splines(jxlhip_ctx* c, const jxlhip_splines* s) {
     return Fail(c, JXLHIP_ERR_UNSUPPORTED, "splines with undo_orientation %u", c->p.undo_orientation);
   c->splines_on = false;
   if (!s) return JXLHIP_OK;
+  if (c->dc_only_on) return Fail(c, JXLHIP_ERR_UNSUPPORTED, "splines on a frame with DC-only groups");
   const uint32_t W = c->f.xsize, H = c->f.ysize;
   // an upsampled frame: the draw cache is made for the upsampled size (dec_frame.cc:304-308), the stage draws the
   // rows and columns of the coded frame
@@ -604,6 +609,7 @@ int jxlhip_set_patches(jxlhip_ctx* c, const jxlhip_patches* s) {
   int rc = jxlhip_patches_list(s, &n, &nec, &uses_ec, nullptr, nullptr);
   if (rc) return Fail(c, rc, "invalid patch dictionary");
   if (n == 0) return JXLHIP_OK;  // nothing reaches the frame: the plain path
+  if (c->dc_only_on) return Fail(c, JXLHIP_ERR_UNSUPPORTED, "patches on a frame with DC-only groups");
   if (uses_ec) return Fail(c, JXLHIP_ERR_UNSUPPORTED, "patches that blend extra channels");
   if (c->fp.alpha) return Fail(c, JXLHIP_ERR_UNSUPPORTED, "patches on a frame with alpha (they would have to blend it)");
   std::vector<jxlhip_patch> list(n);
@@ -708,6 +714,7 @@ int jxlhip_set_upsampling(jxlhip_ctx* c, uint32_t factor, const float* weights, 
     return Fail(c, JXLHIP_ERR_UNSUPPORTED, "upsampling with undo_orientation %u", c->p.undo_orientation);
   if (c->fp.alpha) return Fail(c, JXLHIP_ERR_UNSUPPORTED, "alpha on an upsampled frame");
   if (c->splines_on) return Fail(c, JXLHIP_ERR_STATE, "set_upsampling after set_splines (the draw list depends on it)");
+  if (c->dc_only_on) return Fail(c, JXLHIP_ERR_UNSUPPORTED, "upsampling on a frame with DC-only groups");
   if (out_xsize == 0 || out_ysize == 0 || (out_xsize + factor - 1) / factor != c->f.xsize ||
       (out_ysize + factor - 1) / factor != c->f.ysize)
     return Fail(c, JXLHIP_ERR_INVALID_ARGUMENT, "a %ux%u frame upsampled %ux does not give %ux%u", c->f.xsize, c->f.ysize,
@@ -726,6 +733,36 @@ int jxlhip_set_upsampling(jxlhip_ctx* c, uint32_t factor, const float* weights, 
   return JXLHIP_OK;
 }
 
+// DC-only groups of the current frame (FrameDecoder::Flush on a group without AC, dec_frame.cc:737-797): the mask and
+// the 8x kernels go up here; the decode calls zero the groups' coefficient slots and launch k_dc_upsample8 behind
+// phase 1 (LaunchDcOnly); frame_begin resets to "none".
+int jxlhip_set_dc_only_groups(jxlhip_ctx* c, const uint8_t* mask, const float* weights8) {
+  if (!c) return JXLHIP_ERR_INVALID_ARGUMENT;
+  if (c->multi) return Fail(c, JXLHIP_ERR_UNSUPPORTED, "DC-only groups on a multi-device context");
+  if (!c->have_frame) return Fail(c, JXLHIP_ERR_STATE, "set_dc_only_groups before frame_begin");
+  c->dc_only_on = false;
+  const size_t ng = (size_t)c->f.xsg * c->f.ysg;
+  bool any = false;
+  for (size_t g = 0; mask && g < ng; g++) any = any || mask[g] != 0;
+  if (!any) return JXLHIP_OK;  // the frame's own path, untouched
+  if (c->f.group_y0 != 0 || c->f.group_rows != c->f.ysg) return Fail(c, JXLHIP_ERR_UNSUPPORTED, "DC-only groups with stripes");
+  const char* other = c->noise_on ? "noise" : c->splines_on ? "splines" : c->patches_on ? "patches" : c->ups_factor > 1 ? "upsampling"
+                      : c->blend_on ? "blending" : c->fp.alpha ? "alpha" : nullptr;
+  if (other) return Fail(c, JXLHIP_ERR_UNSUPPORTED, "DC-only groups on a frame with %s", other);
+  HIPCHK(c, hipSetDevice(c->device));
+  int rc;
+  if ((rc = c->dc_only_mask.Reserve(c, ng)) || (rc = c->dc_only_weights.Reserve(c, 25 * 64))) return rc;
+  float kernels[64 * 25], tap_major[25 * 64];
+  UpsampleKernels(8, weights8 ? weights8 : kUpsampling8Weights, kernels);
+  DcUpsampleWeights(kernels, tap_major);
+  c->dc_only_host.assign(mask, mask + ng);
+  // (pageable sources: staged by the runtime when hipMemcpyAsync returns)
+  HIPCHK(c, hipMemcpyAsync(c->dc_only_mask, c->dc_only_host.data(), ng, hipMemcpyHostToDevice, c->stream));
+  HIPCHK(c, hipMemcpyAsync(c->dc_only_weights, tap_major, sizeof(tap_major), hipMemcpyHostToDevice, c->stream));
+  c->dc_only_on = true;
+  return JXLHIP_OK;
+}
+
 // Blending of the current frame (FrameHeader::blending_info, frame_origin, save_as_reference): recorded here, carried
 // out by DecodeFrameBlended; frame_begin resets to "not blended".
 int jxlhip_set_blending(jxlhip_ctx* c, const jxlhip_blend_params* b) {
@@ -735,6 +772,7 @@ int jxlhip_set_blending(jxlhip_ctx* c, const jxlhip_blend_params* b) {
   c->blend_on = false;
   c->blend_ec_on = false;
   if (!b) return JXLHIP_OK;
+  if (c->dc_only_on) return Fail(c, JXLHIP_ERR_UNSUPPORTED, "blending on a frame with DC-only groups");
   if (c->f.group_y0 != 0 || c->f.group_rows != c->f.ysg) return Fail(c, JXLHIP_ERR_UNSUPPORTED, "blending with stripes");
   if (c->p.undo_orientation > 1)
     return Fail(c, JXLHIP_ERR_UNSUPPORTED, "blending with undo_orientation %u", c->p.undo_orientation);
@@ -1140,6 +1178,7 @@ int LaunchFiltersRows(jxlhip_ctx* c, const FilterParams& fp, uint32_t fy0, uint3
 // (profiles/r03_packed_paths.txt).
 bool WantFused(const jxlhip_ctx* c) {
   const DevFrame& f = c->f;
+  if (c->dc_only_on) return false;  // (the fused kernel decodes DCT8 cells from the coefficient stream and never sees the planes)
   // alone a context fuses from 12 Mpx; with several frames in flight on the device (jxlhip_set_concurrency_hint) the
   // step is bound by HBM traffic and the fused path, which moves less, pays from 6 Mpx (profiles/r04_path_choice.txt)
   const uint64_t min_px = c->concurrency > 1 ? (6ull << 20) : (12ull << 20);
@@ -1191,6 +1230,35 @@ int BeginDecode(jxlhip_ctx* c) {
     c->sp_off_pending[par] = true;
     LaunchExpandSparse(c->sp_dev, c->sp_off_dev, (int16_t*)c->up_coeffs[0], c->f.group_y0 * c->f.xsg, c->f.group_rows * c->f.xsg, st);
   }
+  return JXLHIP_OK;
+}
+
+// jxlhip_set_dc_only_groups, in front of phase 1: the coefficient slots of the masked groups are zeroed (the context's
+// upload buffer only: nothing was submitted into them, and phase 1 must not read what an earlier frame left), runs of
+// neighbouring groups with one memset each
+int ZeroDcOnlySlots(jxlhip_ctx* c) {
+  if (!c->dc_only_on || c->f.coeffs[0] != c->up_coeffs[0] || !c->up_coeffs[0]) return JXLHIP_OK;
+  const size_t ng = (size_t)c->f.xsg * c->f.ysg, slot = 3 * (size_t)JXLHIP_GROUP_COEFFS * c->up_esz;
+  if (c->up_groups != ng) return Fail(c, JXLHIP_ERR_STATE, "the upload buffers were laid out for another frame");
+  for (size_t g = 0; g < ng;) {
+    if (!c->dc_only_host[g]) {
+      g++;
+      continue;
+    }
+    size_t e = g;
+    while (e < ng && c->dc_only_host[e]) e++;
+    HIPCHK(c, hipMemsetAsync((char*)c->up_coeffs[0] + g * slot, 0, (e - g) * slot, c->stream));
+    g = e;
+  }
+  return JXLHIP_OK;
+}
+// ... and behind it: k_dc_upsample8 writes the masked groups' tiles of the planes
+int LaunchDcOnly(jxlhip_ctx* c) {
+  if (!c->dc_only_on) return JXLHIP_OK;
+  if (!LaunchDcUpsample8(c->f, c->dc_only_mask, c->dc_only_weights, c->stream))
+    return Fail(c, JXLHIP_ERR_UNSUPPORTED, "DC-only groups: a stripe, or planes beyond 32-bit indices");
+  ProfMark(c, JXLHIP_KERNEL_DC_UPSAMPLE);
+  HIPCHK(c, hipGetLastError());
   return JXLHIP_OK;
 }
 
@@ -1256,8 +1324,10 @@ int jxlhip_decode_blocks(jxlhip_ctx* c) {
   // A whole frame through the split calls stays two-phase (the taps read the planes).
   const bool stripe = c->f.group_y0 != 0 || c->f.group_rows != c->f.ysg;
   c->blocks_fused = stripe && WantFused(c);
+  if ((rc = ZeroDcOnlySlots(c))) return rc;
   rc = LaunchPhase1(c, c->blocks_fused ? 2 : 0);
   if (rc) return rc;
+  if ((rc = LaunchDcOnly(c))) return rc;  // (the last launch of phase 1: jxlhip_export_xyb shows its output)
   c->blocks_done = true;
   return JXLHIP_OK;
 }
@@ -1413,7 +1483,7 @@ static int DecodeFrameCoded(jxlhip_ctx* c, void* out, size_t out_stride, size_t 
   // class kernel applies the opsin inverse and writes the pixels itself (kernels_mfma.hip, EMIT) -- no XYB planes,
   // no second kernel.  used_acs is the caller's promise; k_prepare reports any other strategy it meets.
   if (c->mfma != 0 && f.used_acs == (1u << 5) && c->p.lf.gab == 0 && c->p.lf.epf_iters == 0 &&
-      c->p.output_kind == JXLHIP_OUT_LINEAR_RGB_F32 && !c->generic_filters) {
+      c->p.output_kind == JXLHIP_OUT_LINEAR_RGB_F32 && !c->generic_filters && !c->dc_only_on) {
     rc = LaunchPhase1(c, 0, &fp);
     c->blocks_done = false;  // nothing in the planes
     return rc;
@@ -1429,7 +1499,10 @@ static int DecodeFrameCoded(jxlhip_ctx* c, void* out, size_t out_stride, size_t 
     c->blocks_done = false;  // the planes do not hold the whole frame
     return LaunchFiltersRows(c, fp, f.y0, f.y1, true);
   }
+  // (a frame with DC-only groups always comes here: WantFused; k_dc_upsample8 between phase 1 and the filters)
+  if ((rc = ZeroDcOnlySlots(c))) return rc;
   if ((rc = LaunchPhase1(c))) return rc;
+  if ((rc = LaunchDcOnly(c))) return rc;
   c->blocks_done = true;
   return LaunchFiltersRows(c, fp, f.y0, f.y1);
 }

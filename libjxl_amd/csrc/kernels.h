@@ -289,6 +289,14 @@ void UpsampleKernels(uint32_t n, const float* coded, float* kernels /* n * n * 2
 bool LaunchUpsample(const UpsampleArgs& U, const FilterParams& p, int output_kind, float* planes_out, uint32_t planes_ns,
                     size_t planes_nplane, hipStream_t st);
 
+// DC-only groups (kernels_dc_upsample.hip): the DC samples of the AC groups whose mask byte is set, upsampled 8x into
+// their 8 x 8 tiles of the three block-major XYB planes of f (whole frames only).
+// host: the 64 kernels of 25 taps (UpsampleKernels(8, ...)) in the order the kernel loads them: [tap][kernel]
+void DcUpsampleWeights(const float* kernels /* 64 * 25 */, float* tap_major /* 25 * 64 */);
+// k_dc_upsample8: mask = f.xsg * f.ysg bytes (device), weights = DcUpsampleWeights' table (device).  False for a stripe
+// and for planes beyond 32-bit float indices.
+bool LaunchDcUpsample8(const DevFrame& f, const uint8_t* mask, const float* weights, hipStream_t st);
+
 // block-major plane rows <-> dense row-major staging
 void LaunchZeroU32(uint32_t* p, uint32_t n, hipStream_t st);  // (kernels_tables.hip: a kernel, for captured graphs)
 void LaunchRowsCopy(const DevFrame& f, float* dense, int y_first, int nrows, int ncols,

@@ -211,6 +211,26 @@ class VarDctDecoder:
         _check(self.L, self.ctx, self.L.jxlhip_set_upsampling(self.ctx, int(factor), w, ox, oy), "set_upsampling")
         self.out_size = (ox, oy) if int(factor) > 1 else None
 
+    def set_dc_only_groups(self, mask, weights=None):
+        """The AC groups of the current frame that have no AC and are drawn from their DC upsampled 8x,
+        jxlhip_set_dc_only_groups: mask = one truth value per group (row-major over the frame's 256 x 256 groups),
+        weights = the 210 coded weights of the 8x upsampler, None = the format's defaults.  None or an all-zero mask
+        leaves the frame on its own path; begin_frame resets."""
+        import numpy as np
+        p = self.params
+        ng = ((p.xsize + 255) // 256) * ((p.ysize + 255) // 256)
+        m = None
+        if mask is not None:
+            m = np.ascontiguousarray(np.asarray(mask).reshape(-1) != 0, dtype=np.uint8)
+            assert m.size == ng, (m.size, ng)
+        w = None
+        if weights is not None:
+            vals = [float(v) for v in weights]
+            assert len(vals) == 210, len(vals)
+            w = (C.c_float * 210)(*vals)
+        _check(self.L, self.ctx, self.L.jxlhip_set_dc_only_groups(self.ctx, m.ctypes.data if m is not None else None, w),
+               "set_dc_only_groups")
+
     def set_blending(self, image_size, origin=(0, 0), mode=abi.BLEND_REPLACE, clamp=False, source=0, save_slot=None):
         """Blending of the current frame, jxlhip_set_blending: the frame's own output is blended at `origin` = (x0, y0)
         (signed) over the canvas of slot `source` with BlendMode `mode` (abi.BLEND_*), written at image_size =

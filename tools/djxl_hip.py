@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """djxl_hip.py IN.jxl OUT.{pfm,npy,ppm,pam} [--threads N] [--reps K] [--frames] [--display_nits N]
-                                            [--output_primaries {srgb,p3,rec2100}]
+                                            [--output_primaries {srgb,p3,rec2100}] [--allow_partial_files]
 
 Decodes a .jxl file (container or bare codestream, one VarDCT still frame) on an MI355X through
 jxlhip_decode_codestream (include/jxl_hip_codestream.h) and writes the pixels the way djxl does for these
@@ -22,7 +22,10 @@ displayed frame of an image with alpha as RGBA, its alpha blended with the colou
 original mastered brighter is tone-mapped to it on the device (jxlhip_codestream_set_display).
 --output_primaries: the pixels in these primaries (D65) instead of the original's, as JxlDecoderSetOutputColorProfile
 with an enumerated encoding gives them; the transfer function stays the original's (its PQ curve keeps the
-original's intensity target, as the reference's does)."""
+original's intensity target, as the reference's does).
+--allow_partial_files: djxl's flag of that name: a file that ends early is rendered from what has arrived
+(jxlhip_decode_codestream_partial: groups without AC from their DC, upsampled 8x on the device) and the three group
+counts are printed; a file that ends before its DC groups exits with status 4.  Not with --frames."""
 import argparse
 import ctypes as C
 import os
@@ -62,15 +65,24 @@ def main():
     ap.add_argument("--frames", action="store_true")
     ap.add_argument("--display_nits", type=float, default=0.0)
     ap.add_argument("--output_primaries", choices=["srgb", "p3", "rec2100"])
+    ap.add_argument("--allow_partial_files", action="store_true")
     a = ap.parse_args()
+    if a.allow_partial_files and a.frames:
+        sys.exit("--allow_partial_files renders single-frame files: not with --frames")
     import torch
     from libjxl_amd import VarDctDecoder, abi
     L = abi.load_library()
     blob = open(a.input, "rb").read()
     info = abi.CodestreamInfo()
     seq = abi.SequenceInfo()
+    part = abi.PartialInfo()
     if a.frames:
         rc = L.jxlhip_codestream_sequence_info_ex(blob, len(blob), abi.SEQUENCE_EXTRA_CHANNELS, C.byref(info), C.byref(seq))
+    elif a.allow_partial_files:
+        rc = L.jxlhip_codestream_partial_info(blob, len(blob), C.byref(info), C.byref(part))
+        if rc == abi.ERR_NEED_MORE_INPUT:
+            sys.stderr.write(f"djxl_hip: {a.input}: {L.jxlhip_status_string(rc).decode()}\n")
+            sys.exit(4)
     else:
         rc = L.jxlhip_codestream_basic_info(blob, len(blob), C.byref(info))
     if rc:
@@ -78,6 +90,8 @@ def main():
         sys.exit(3 if rc == -7 else 1)
     orig_nits = info.intensity_target  # (the PQ curve of the output keeps it, whatever the display's peak)
     display = None
+    if (a.display_nits or a.output_primaries) and a.allow_partial_files and not part.complete:
+        sys.exit("--display_nits / --output_primaries need the whole file")  # (jxlhip_codestream_display_info reads it all)
     if a.display_nits or a.output_primaries:
         display = abi.Display(a.display_nits, {None: 0, "srgb": 1, "rec2100": 9, "p3": 11}[a.output_primaries],
                               1 if a.output_primaries else 0)
@@ -139,7 +153,12 @@ def main():
     best = None
     for _ in range(max(1, a.reps)):
         t0 = time.perf_counter()
-        rc = L.jxlhip_decode_codestream(dec.ctx, runner, pool, blob, len(blob), *args, C.byref(info))
+        if a.allow_partial_files:
+            if ext == ".pam" and info.num_extra_channels and not part.complete:
+                sys.exit("a partial file of an image with extra channels: write .ppm, .pfm or .npy")
+            rc = L.jxlhip_decode_codestream_partial(dec.ctx, runner, pool, blob, len(blob), *args, C.byref(info), C.byref(part))
+        else:
+            rc = L.jxlhip_decode_codestream(dec.ctx, runner, pool, blob, len(blob), *args, C.byref(info))
         dt = time.perf_counter() - t0
         if rc:
             sys.stderr.write(f"djxl_hip: {a.input}: {L.jxlhip_status_string(rc).decode()}: "
@@ -150,6 +169,9 @@ def main():
     print(f"{w} x {h}, {w * h / best / 1e6:.1f} MP/s [{a.reps} reps, {a.threads} threads], "
           f"{info.num_groups} groups, {info.num_passes} pass(es), coefficients "
           f"{'int16' if info.coeff_type == 0 else 'int32'}, epf_iters {info.epf_iters} gab {info.gab}")
+    if a.allow_partial_files:
+        print(f"{'complete' if part.complete else 'partial'} file: {part.groups_complete} group(s) complete, "
+              f"{part.groups_partial} partial, {part.groups_dc_only} DC only; {part.bytes_used} of {len(blob)} bytes drawn")
     dec.close()
     if pool:
         R.JxlThreadParallelRunnerDestroy(pool)
