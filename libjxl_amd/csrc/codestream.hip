@@ -818,8 +818,8 @@ static int DecodeFrameAt(jxlhip_ctx* c, const uint8_t* cs, size_t n, const Parse
     // what the slots hold; a canvas (a sequence's saved frame) with its size, so that the dictionary decodes and
     // jxlhip_set_patches names the refusal ("saved after the colour transform")
     for (int slot = 0; slot < 4; slot++) {
-      ref_sizes[slot][0] = c->ref_w[slot] ? c->ref_w[slot] : c->canvas_w[slot];
-      ref_sizes[slot][1] = c->ref_h[slot] ? c->ref_h[slot] : c->canvas_h[slot];
+      ref_sizes[slot][0] = c->slots.ref_w[slot] ? c->slots.ref_w[slot] : c->slots.canvas_w[slot];
+      ref_sizes[slot][1] = c->slots.ref_h[slot] ? c->slots.ref_h[slot] : c->slots.canvas_h[slot];
     }
     jxlhip_patches* pt = nullptr;
     if ((rc = jxlhip_patches_decode(sec(0), sz[0], &spos, fh.xsize_blocks * 8, fh.ysize_blocks * 8, 0, ref_sizes, &pt)))

@@ -1,4 +1,4 @@
-// context.h -- what the host units (context.hip, handover.hip, multi.hip, codestream.hip) share: struct jxlhip_ctx, the
+// context.h -- what the host units (context.hip, render_stages.hip, handover.hip, multi.hip, codestream.hip) share: struct jxlhip_ctx, the
 // owner types of what it holds, Fail / HIPCHK, and the internal functions the units call across each other.  Not a
 // public header: nothing here is part of the C ABI.
 #pragma once
@@ -17,6 +17,7 @@
 #include "../../include/jxl_hip_codestream.h"
 #include "../../include/jxl_hip_entropy.h"
 #include "kernels.h"
+#include "tile_bins.h"
 #include "env_switches.h"  // (the switches themselves live in entropy.cc: that file is also built alone, by the fuzz harnesses)
 
 namespace jxlhip {
@@ -157,6 +158,148 @@ struct MultiState {
   std::vector<MultiChild> kids;
 };
 
+// What jxlhip_set_splines / jxlhip_set_patches keep around a tile-binned list (tile_bins.h).  The host copies -- `host`
+// and the stage's records, which go up in front of it on the same stream -- stay alive until `ev` says the upload is done.
+struct TileList {
+  DevBuf<uint32_t> dev;
+  TileBins host;
+  Event ev;
+  bool pending = false;
+  int WaitHostFree(jxlhip_ctx* c) {  // until the previous upload no longer reads the host copies
+    if (pending) HIPCHK(c, hipEventSynchronize(ev));
+    pending = false;
+    return JXLHIP_OK;
+  }
+  int Upload(jxlhip_ctx* c, hipStream_t st) {
+    if (const int rc = dev.Reserve(c, host.words.size())) return rc;
+    HIPCHK(c, hipMemcpyAsync(dev, host.words.data(), host.words.size() * sizeof(uint32_t), hipMemcpyHostToDevice, st));
+    HIPCHK(c, ev.Create());
+    HIPCHK(c, hipEventRecord(ev, st));
+    pending = true;
+    return JXLHIP_OK;
+  }
+  template <typename Args>  // SplineArgs / PatchArgs
+  void Fill(Args* a) const {
+    a->tiles_x = host.tiles_x;
+    a->num_active = host.num_active;
+    a->tile_start = dev;
+    a->tile_idx = dev + host.num_tiles + 1;
+    a->active = dev + host.num_tiles + 1 + host.entries;
+  }
+};
+
+// ---- the render stages of the current frame, one struct per stage (render_stages.hip).  `on`, ups.factor and
+// blend_ec.frame_n are per frame (StageState::ResetFrame); the buffers, host copies and events outlive frames.
+// jxlhip_set_noise: photon noise; buf = the filtered frame as planar XYB + the random planes (kernels_noise.hip),
+// jump = the generator's jump matrices (uploaded once)
+struct NoiseStage {
+  bool on = false;
+  float lut[8] = {0};
+  uint32_t visible = 0, nonvisible = 0;
+  DevBuf<float> buf;
+  DevBuf<uint32_t> jump;
+};
+// jxlhip_set_splines: the draw list, binned by 64 x 16 tile (kernels_splines.hip)
+struct SplineStage {
+  bool on = false;
+  DevBuf<SplineSeg> segs;
+  std::vector<SplineSeg> host_segs;
+  TileList tiles;
+};
+// jxlhip_set_patches: the dictionary, binned by 64 x 16 tile (kernels_patches.hip).  The records point into the
+// reference slots: ref_serial = SlotState::ref_serial at the dictionary's upload.
+struct PatchStage {
+  bool on = false;
+  uint64_t ref_serial = 0;
+  DevBuf<PatchRec> recs;
+  std::vector<PatchRec> host_recs;
+  TileList tiles;
+};
+// jxlhip_set_upsampling: the frame is upsampled by `factor` (1 = not) to xsize x ysize; planes = the filtered frame as
+// planar XYB at CODED size (kernels_upsample.hip; noise.buf then holds the upsampled planes + the random planes at
+// output size), weights = the factor's kernels (UpsampleKernels), weights_host the copy their upload reads
+struct UpsampleStage {
+  uint32_t factor = 1, xsize = 0, ysize = 0;
+  DevBuf<float> planes, weights;
+  float weights_host[64 * 25] = {0};
+};
+// jxlhip_set_dc_only_groups: the AC groups that are drawn from their DC; mask = one byte per group, weights = the 8x
+// kernels as k_dc_upsample8 loads them (DcUpsampleWeights), host = the host copy of the mask (which coefficient slots
+// ZeroDcOnlySlots zeroes)
+struct DcOnlyStage {
+  bool on = false;
+  DevBuf<uint8_t> mask;
+  DevBuf<float> weights;
+  std::vector<uint8_t> host;
+};
+// jxlhip_set_blending: the frame is blended over a canvas and / or saved; stage = the frame's own output in front of
+// k_blend (DecodeFrameBlended)
+struct BlendStage {
+  bool on = false;
+  jxlhip_blend_params p{};
+  DevBuf<float> stage;
+};
+// jxlhip_set_blending_extra: the frame's image has extra channels, which are blended and saved with the colour
+// (set_blending resets `on` as well).  stage = the frame's own planes in front of k_ec_blend (uploaded by the call:
+// p.num_extra_channels planes of f.ysize rows of stage_stride floats, the samples (x0 mod 4) floats in); frame_buf = the
+// blended planes of a frame that is not saved; frame_planes = where the current frame's blended planes are (the save
+// slot's or frame_buf; jxlhip_frame_extra_read), frame_n of them, 0 = none.
+struct BlendEcStage {
+  bool on = false;
+  jxlhip_blend_extra_params p{};  // (its plane pointers are the caller's and not kept)
+  DevBuf<float> stage, frame_buf;
+  size_t stage_stride = 0;
+  const float* frame_planes = nullptr;
+  uint32_t frame_n = 0, frame_w = 0, frame_h = 0;
+};
+// jxlhip_set_tone_mapping: k = k_tone_map's constants, planes = the frame's own output as planar XYB at output size in
+// front of it (DecodeFrameToneMapped)
+struct ToneMapStage {
+  bool on = false;
+  ToneMapConstants k{};
+  DevBuf<float> planes;
+};
+struct StageState {
+  NoiseStage noise;
+  SplineStage splines;
+  PatchStage patches;
+  UpsampleStage ups;
+  DcOnlyStage dc_only;
+  BlendStage blend;
+  BlendEcStage blend_ec;
+  ToneMapStage tone_map;
+  void ResetFrame() {  // jxlhip_frame_begin: no stage is on
+    noise.on = splines.on = patches.on = dc_only.on = blend.on = blend_ec.on = tone_map.on = false;
+    ups.factor = 1;
+    blend_ec.frame_n = 0;
+  }
+  // some stage between the loop filters and the XYB stage is on: the frame goes through DecodeFrameFeatures
+  bool RenderStagesOn() const { return noise.on || splines.on || patches.on || ups.factor > 1; }
+};
+
+// The four slots (jxlhip_set_reference_frame, DecodeFrameBlended's save_slot); a slot holds one kind.  ref_planes[s] =
+// a reference frame patches copy from: three dense XYB planes of ref_w x ref_h floats (0: empty); ref_serial =
+// set_reference_frame calls so far.  canvas[s] = a canvas: interleaved float RGB in the output's transfer function,
+// CanvasStride(canvas_w) floats per row (rows padded to four pixels: k_blend's 16-byte vectors), canvas_w x canvas_h (0:
+// none); canvas_ec[s] = its canvas_nec[s] extra channels: planar planes of canvas_h rows of EcStride(canvas_w) floats.
+struct SlotState {
+  DevBuf<float> ref_planes[4];
+  uint32_t ref_w[4] = {0, 0, 0, 0}, ref_h[4] = {0, 0, 0, 0};
+  uint64_t ref_serial = 0;
+  DevBuf<float> canvas[4];
+  uint32_t canvas_w[4] = {0, 0, 0, 0}, canvas_h[4] = {0, 0, 0, 0};
+  DevBuf<float> canvas_ec[4];
+  uint32_t canvas_nec[4] = {0, 0, 0, 0};
+};
+
+// Where and as what a decode path writes (never read from c->p): the output kind (JXLHIP_OUT_*), the packed format,
+// and the context's FilterParams with out, the strides, fmt and sample_mul of that.
+struct OutTarget {
+  uint32_t kind;
+  jxlhip_output_format fmt;
+  FilterParams fp;
+};
+
 }  // namespace jxlhip
 
 using namespace jxlhip;
@@ -261,93 +404,14 @@ struct jxlhip_ctx {
   DevBuf<float> alpha_dev;  // jxlhip_set_alpha: the frame's alpha plane (xsize floats per row)
   PinnedBuf alpha_host;  // jxlhip_alpha_staging: pinned plane the caller fills
   DevBuf<int32_t> qdc_dev;  // jxlhip_decode_codestream: the quantized DC planes on their way to jxlhip_dequant_dc_groups
-  // jxlhip_set_noise: photon noise of the current frame (frame_begin resets noise_on); noise_buf = the filtered frame as
-  // planar XYB + the random planes (kernels_noise.hip), noise_jump = the generator's jump matrices (uploaded once)
-  bool noise_on = false;
-  float noise_lut[8] = {0};
-  uint32_t noise_visible = 0, noise_nonvisible = 0;
-  DevBuf<float> noise_buf;
-  DevBuf<uint32_t> noise_jump;
-  // jxlhip_set_splines: the draw list of the current frame (frame_begin resets splines_on), binned by 64 x 16 tile
-  // (kernels_splines.hip); spl_tiles = tile_start (tiles + 1), tile_idx, active tiles.  The host copies stay alive
-  // until spl_ev says their upload is done.
-  bool splines_on = false;
-  DevBuf<SplineSeg> spl_segs;
-  DevBuf<uint32_t> spl_tiles;
-  uint32_t spl_tiles_x = 0, spl_num_tiles = 0, spl_num_active = 0;
-  size_t spl_entries = 0;
-  std::vector<SplineSeg> spl_host_segs;
-  std::vector<uint32_t> spl_host_tiles;
-  Event spl_ev;
-  bool spl_ev_pending = false;
-  // jxlhip_set_reference_frame: the four reference-frame slots patches copy from, each three dense XYB planes of
-  // ref_w x ref_h floats (0: empty); they outlive frames.  jxlhip_set_patches: the dictionary of the current frame
-  // (frame_begin resets patches_on), binned by 64 x 16 tile (kernels_patches.hip); pat_tiles = tile_start (tiles + 1),
-  // tile_idx, active tiles.  The records point into the slots.  The host copies stay alive until pat_ev says their
-  // upload is done.
-  DevBuf<float> ref_planes[4];
-  uint32_t ref_w[4] = {0, 0, 0, 0}, ref_h[4] = {0, 0, 0, 0};
-  bool patches_on = false;
-  uint64_t ref_serial = 0, pat_ref_serial = 0;  // set_reference_frame calls so far / at the dictionary's upload
-  DevBuf<PatchRec> pat_recs;
-  DevBuf<uint32_t> pat_tiles;
-  uint32_t pat_tiles_x = 0, pat_num_tiles = 0, pat_num_active = 0;
-  size_t pat_entries = 0;
-  std::vector<PatchRec> pat_host_recs;
-  std::vector<uint32_t> pat_host_tiles;
-  Event pat_ev;
-  bool pat_ev_pending = false;
-  // jxlhip_set_upsampling: the current frame is upsampled by ups_factor (1 = not; frame_begin resets) to ups_xsize x
-  // ups_ysize; ups_planes = the filtered frame as planar XYB at CODED size (kernels_upsample.hip; noise_buf then holds
-  // the upsampled planes + the random planes at output size), ups_weights = the factor's kernels (UpsampleKernels),
-  // ups_weights_host the copy their upload reads
-  // jxlhip_set_blending: the current frame is blended over a canvas and / or saved (frame_begin resets blend_on).
-  // canvas[s] = the canvas of slot s: interleaved float RGB in the output's transfer function, CanvasStride(canvas_w)
-  // floats per row (rows padded to four pixels: k_blend's 16-byte vectors), canvas_w x canvas_h (0: none); a slot holds
-  // either this or ref_planes.  blend_stage = the frame's own output in front of k_blend (DecodeFrameBlended).
-  bool blend_on = false;
-  jxlhip_blend_params blend{};
-  DevBuf<float> canvas[4];
-  uint32_t canvas_w[4] = {0, 0, 0, 0}, canvas_h[4] = {0, 0, 0, 0};
-  DevBuf<float> blend_stage;
-  // jxlhip_set_blending_extra: the current frame belongs to an image with extra channels, which are blended and saved
-  // with the colour (frame_begin and set_blending reset blend_ec_on).  canvas_ec[s] = the extra-channel planes of slot
-  // s's canvas: canvas_nec[s] planar float planes of canvas_h rows of EcStride(canvas_w) floats, one behind the other;
-  // they live and die with the canvas.  blend_ec_stage = the frame's own planes in front of k_ec_blend (uploaded by the
-  // call: blend_ec.num_extra_channels planes of f.ysize rows of blend_ec_stage_stride floats, the samples (x0 mod 4)
-  // floats in); frame_ec = the blended planes of a frame that is not saved.  frame_ec_planes = where the current
-  // frame's blended planes are (the save slot's or frame_ec; jxlhip_frame_extra_read), frame_ec_n of them, 0 = none.
-  bool blend_ec_on = false;
-  jxlhip_blend_extra_params blend_ec{};  // (its plane pointers are the caller's and not kept)
-  DevBuf<float> canvas_ec[4];
-  uint32_t canvas_nec[4] = {0, 0, 0, 0};
-  DevBuf<float> blend_ec_stage;
-  size_t blend_ec_stage_stride = 0;
-  DevBuf<float> frame_ec;
-  const float* frame_ec_planes = nullptr;
-  uint32_t frame_ec_n = 0, frame_ec_w = 0, frame_ec_h = 0;
-  // jxlhip_set_tone_mapping: the current frame is tone-mapped (frame_begin resets tm_on); tm_k = k_tone_map's constants,
-  // tm_planes = the frame's own output as planar XYB at output size in front of it (DecodeFrameToneMapped)
-  bool tm_on = false;
-  ToneMapConstants tm_k{};
-  DevBuf<float> tm_planes;
-  // jxlhip_set_dc_only_groups: the AC groups of the current frame that are drawn from their DC (frame_begin resets
-  // dc_only_on); dc_only_mask = one byte per group, dc_only_weights = the 8x kernels as k_dc_upsample8 loads them
-  // (DcUpsampleWeights), dc_only_host = the host copy of the mask (which coefficient slots DecodeBegin zeroes)
-  bool dc_only_on = false;
-  DevBuf<uint8_t> dc_only_mask;
-  DevBuf<float> dc_only_weights;
-  std::vector<uint8_t> dc_only_host;
+  StageState st;  // the render stages of the current frame (jxlhip_frame_begin: ResetFrame)
+  SlotState slots;  // the four reference / canvas slots: they outlive frames
   // jxlhip_codestream_set_display: sticky on the context (0 = not set), read by the whole-file decode calls
   float display_nits = 0.0f;
   uint32_t display_primaries = 0, display_white_point = 0;
   // jxlhip_decode_codestream_next: a sequence is open and this is the cursor the next call must bring
   bool seq_open = false;
   uint64_t seq_expect = 0;
-  uint32_t ups_factor = 1, ups_xsize = 0, ups_ysize = 0;
-  DevBuf<float> ups_planes;
-  DevBuf<float> ups_weights;
-  float ups_weights_host[64 * 25] = {0};
   bool generic_filters = false;  // JXLHIP_FILTERS=generic: LDS kernel for every stage list
   int mfma = -1;                 // DCT32X32 / DCT16X16 on the matrix cores (kernels_mfma.hip; the 16x16 rule is in
                                  // LaunchPhase1).  -1 (default): when the caller's
@@ -377,19 +441,37 @@ inline size_t OutSampleBytes(const jxlhip_output_format& o) {
   return o.sample_type == JXLHIP_SAMPLE_U8 ? 1 : (o.sample_type == JXLHIP_SAMPLE_F32 ? 4 : 2);
 }
 // bytes of one interleaved output pixel (0: planar XYB)
-inline size_t OutPixelBytes(const jxlhip_ctx* c) {
-  if (c->p.output_kind == JXLHIP_OUT_LINEAR_RGB_F32) return 12;
-  if (c->p.output_kind != JXLHIP_OUT_PACKED) return 0;
-  return (size_t)c->p.out_format.num_channels * OutSampleBytes(c->p.out_format);
+inline size_t OutPixelBytes(uint32_t kind, const jxlhip_output_format& o) {
+  if (kind == JXLHIP_OUT_LINEAR_RGB_F32) return 12;
+  return kind == JXLHIP_OUT_PACKED ? (size_t)o.num_channels * OutSampleBytes(o) : 0;
 }
+inline size_t OutPixelBytes(const jxlhip_ctx* c) { return OutPixelBytes(c->p.output_kind, c->p.out_format); }
 
 // columns / rows of what jxlhip_decode_frame writes in coded orientation: the context's stripe of the frame, or the
 // size an upsampled frame (jxlhip_set_upsampling: whole frames only) comes out at
-inline size_t OutCols(const jxlhip_ctx* c) { return c->ups_factor > 1 ? c->ups_xsize : c->f.xsize; }
-inline size_t OutRows(const jxlhip_ctx* c) { return c->ups_factor > 1 ? c->ups_ysize : c->f.y1 - c->f.y0; }
+inline size_t OutCols(const jxlhip_ctx* c) { return c->st.ups.factor > 1 ? c->st.ups.xsize : c->f.xsize; }
+inline size_t OutRows(const jxlhip_ctx* c) { return c->st.ups.factor > 1 ? c->st.ups.ysize : c->f.y1 - c->f.y0; }
 // ... and of what the caller's buffer holds: the image when the frame is blended (jxlhip_set_blending)
-inline size_t BufCols(const jxlhip_ctx* c) { return c->blend_on ? c->blend.image_xsize : OutCols(c); }
-inline size_t BufRows(const jxlhip_ctx* c) { return c->blend_on ? c->blend.image_ysize : OutRows(c); }
+inline size_t BufCols(const jxlhip_ctx* c) { return c->st.blend.on ? c->st.blend.p.image_xsize : OutCols(c); }
+inline size_t BufRows(const jxlhip_ctx* c) { return c->st.blend.on ? c->st.blend.p.image_ysize : OutRows(c); }
+
+// A target of `kind` and (packed) `fmt` at out; MakeTarget(c, out, ..): the one jxlhip_frame_begin was given.
+inline OutTarget MakeTarget(const jxlhip_ctx* c, uint32_t kind, const jxlhip_output_format& fmt, void* out, size_t out_stride,
+                            size_t out_plane_stride) {
+  OutTarget t{kind, fmt, c->fp};
+  t.fp.out = out;
+  t.fp.out_stride = out_stride;
+  t.fp.out_plane_stride = out_plane_stride;
+  if (kind == JXLHIP_OUT_PACKED) {  // (as jxlhip_frame_begin)
+    const bool is_int = fmt.sample_type == JXLHIP_SAMPLE_U8 || fmt.sample_type == JXLHIP_SAMPLE_U16;
+    t.fp.fmt = fmt;
+    t.fp.sample_mul = is_int ? (float)((1u << fmt.bits_per_sample) - 1u) : 1.0f;
+  }
+  return t;
+}
+inline OutTarget MakeTarget(const jxlhip_ctx* c, void* out, size_t out_stride, size_t out_plane_stride) {
+  return MakeTarget(c, c->p.output_kind, c->p.out_format, out, out_stride, out_plane_stride);
+}
 
 // context.hip
 jxlhip_ctx* NewCtx(const JxlMemoryManagerHip* mm);
@@ -405,6 +487,19 @@ inline void DropPrepared(jxlhip_ctx* c) {
 // context would decode it with now (jxlhip_upload_side_info, jxlhip_decode_codestream).  render_stages: the caller
 // knows that splines, upsampling or noise will be set for this frame (its own path then writes planar XYB).
 int PrepareAhead(jxlhip_ctx* c, bool render_stages = false);
+bool Capturing(hipStream_t st);
+void ProfBegin(jxlhip_ctx* c), ProfMark(jxlhip_ctx* c, int slot);
+// cols x rows: what the call writes -- the stripe at coded size, or an upsampled frame (OutCols / OutRows)
+int CheckOutArgs(jxlhip_ctx* c, const OutTarget& t, size_t cols, size_t rows);
+// both phases over the whole stripe at coded size, without any render stage
+int DecodeFrameCoded(jxlhip_ctx* c, const OutTarget& t);
+
+// render_stages.hip
+int ZeroDcOnlySlots(jxlhip_ctx* c), LaunchDcOnly(jxlhip_ctx* c);  // jxlhip_set_dc_only_groups: in front of phase 1, behind it
+// the frame's own path: DecodeFrameFeatures when a render stage is on (StageState::RenderStagesOn), else DecodeFrameCoded
+int DecodeFrameOwnPath(jxlhip_ctx* c, const OutTarget& t);
+int DecodeFrameBlended(jxlhip_ctx* c, void* out, size_t out_stride);
+int DecodeFrameToneMapped(jxlhip_ctx* c, void* out, size_t out_stride);
 
 // multi.hip
 void MultiDestroy(jxlhip_ctx* c);

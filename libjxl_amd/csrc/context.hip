@@ -2,7 +2,8 @@
 // two decode phases, halo regions, profiling.  Host code only;
 // kernels live in kernels_*.hip.  No CPU fallback: every entry point that needs
 // a device fails with JXLHIP_ERR_NO_DEVICE / JXLHIP_ERR_HIP when there is none.
-// The input hand-off is handover.hip, the multi-device parent multi.hip, the whole-file decoder codestream.hip.
+// The render stages (their setters and decode paths) are render_stages.hip, the input hand-off is handover.hip, the
+// multi-device parent multi.hip, the whole-file decoder codestream.hip.
 #include <math.h>
 #include <stdarg.h>
 #include <stdlib.h>
@@ -10,7 +11,6 @@
 
 #include "context.h"
 #include "dither_pattern.inc"
-#include "upsampling_constants.inc"
 
 extern "C" __attribute__((visibility("default"))) void jxlhip_debug_reload_env(void) {
   std::lock_guard<std::mutex> lock(jxlhip_env::g.mu);
@@ -41,18 +41,19 @@ void ProfPush(jxlhip_ctx* c) {
   (void)c->marks.back().ev.Create(hipEventDefault);
   (void)hipEventRecord(c->marks.back().ev, c->stream);
 }
-void ProfBegin(jxlhip_ctx* c) {
+
+}  // namespace
+
+void jxlhip::ProfBegin(jxlhip_ctx* c) {
   if (c->profiling) ProfPush(c);
 }
 // closes the span [previous mark, now) for `slot` and opens the next one (the last mark's slot_after stays -1: nothing
 // starts there)
-void ProfMark(jxlhip_ctx* c, int slot) {
+void jxlhip::ProfMark(jxlhip_ctx* c, int slot) {
   if (!c->profiling || c->marks.empty()) return;
   c->marks.back().slot_after = slot;
   ProfPush(c);
 }
-
-}  // namespace
 
 // ---- static helpers -------------------------------------------------------
 int jxlhip_covered_blocks_x(int s) {
@@ -351,15 +352,7 @@ int jxlhip_frame_begin(jxlhip_ctx* c, const jxlhip_frame_params* p) {
   c->have_frame = true;
   c->have_inputs = false;
   c->blocks_done = false;
-  c->noise_on = false;
-  c->splines_on = false;
-  c->patches_on = false;
-  c->ups_factor = 1;
-  c->blend_on = false;
-  c->blend_ec_on = false;
-  c->frame_ec_n = 0;
-  c->tm_on = false;
-  c->dc_only_on = false;
+  c->st.ResetFrame();
   return JXLHIP_OK;
 }
 
@@ -418,10 +411,10 @@ int jxlhip_alpha_staging(jxlhip_ctx* c, float** plane, size_t* stride_floats) {
 int jxlhip_set_alpha(jxlhip_ctx* c, const float* host_plane, size_t stride_floats) {
   if (!c || !host_plane) return JXLHIP_ERR_INVALID_ARGUMENT;
   if (!c->have_frame) return Fail(c, JXLHIP_ERR_STATE, "set_alpha before frame_begin");
-  if (c->ups_factor > 1) return Fail(c, JXLHIP_ERR_UNSUPPORTED, "alpha on an upsampled frame");
-  if (c->patches_on) return Fail(c, JXLHIP_ERR_UNSUPPORTED, "alpha on a frame with patches (they would have to blend it)");
-  if (c->blend_on) return Fail(c, JXLHIP_ERR_UNSUPPORTED, "alpha on a blended frame (blending extra channels is not in the back-end)");
-  if (c->dc_only_on) return Fail(c, JXLHIP_ERR_UNSUPPORTED, "alpha on a frame with DC-only groups");
+  if (c->st.ups.factor > 1) return Fail(c, JXLHIP_ERR_UNSUPPORTED, "alpha on an upsampled frame");
+  if (c->st.patches.on) return Fail(c, JXLHIP_ERR_UNSUPPORTED, "alpha on a frame with patches (they would have to blend it)");
+  if (c->st.blend.on) return Fail(c, JXLHIP_ERR_UNSUPPORTED, "alpha on a blended frame (blending extra channels is not in the back-end)");
+  if (c->st.dc_only.on) return Fail(c, JXLHIP_ERR_UNSUPPORTED, "alpha on a frame with DC-only groups");
   if (c->multi) {  // every stripe takes its own rows of the plane
     for (MultiChild& k : c->multi->kids) {
       const int rc = jxlhip_set_alpha(k.ctx, host_plane, stride_floats);
@@ -442,537 +435,13 @@ int jxlhip_set_alpha(jxlhip_ctx* c, const float* host_plane, size_t stride_float
   return JXLHIP_OK;
 }
 
-// Photon noise of the current frame (FrameHeader::kNoise): NoiseParams::lut and the seed indices of
-// PassesDecoderState; frame_begin resets to "no noise".  A LUT without an entry above 1e-3 is recorded as no noise,
-// as AddNoiseStage skips it (noise.h:37-42).
-int jxlhip_set_noise(jxlhip_ctx* c, const float lut[8], uint32_t visible_frame_index, uint32_t nonvisible_frame_index) {
-  if (!c || !lut) return JXLHIP_ERR_INVALID_ARGUMENT;
-  if (c->multi) return Fail(c, JXLHIP_ERR_UNSUPPORTED, "noise on a multi-device context");
-  if (!c->have_frame) return Fail(c, JXLHIP_ERR_STATE, "set_noise before frame_begin");
-  if (c->f.group_y0 != 0 || c->f.group_rows != c->f.ysg) return Fail(c, JXLHIP_ERR_UNSUPPORTED, "noise with stripes");
-  if (c->p.undo_orientation > 1) return Fail(c, JXLHIP_ERR_UNSUPPORTED, "noise with undo_orientation %u", c->p.undo_orientation);
-  if (c->dc_only_on) return Fail(c, JXLHIP_ERR_UNSUPPORTED, "noise on a frame with DC-only groups");
-  bool any = false;
-  for (int i = 0; i < 8; i++) any = any || fabsf(lut[i]) > 1e-3f;
-  c->noise_on = false;
-  if (!any) return JXLHIP_OK;
-  HIPCHK(c, hipSetDevice(c->device));
-  if (!c->noise_jump) {
-    static const std::vector<uint32_t> table = [] {
-      std::vector<uint32_t> t((size_t)kNoiseSegs * kNoiseJumpWords);
-      NoiseJumpTable(t.data());
-      return t;
-    }();
-    const int rc = c->noise_jump.Reserve(c, table.size());
-    if (rc) return rc;
-    HIPCHK(c, hipMemcpyAsync(c->noise_jump, table.data(), table.size() * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
-  }
-  memcpy(c->noise_lut, lut, sizeof(c->noise_lut));
-  c->noise_visible = visible_frame_index;
-  c->noise_nonvisible = nonvisible_frame_index;
-  c->noise_on = true;
-  return JXLHIP_OK;
-}
-
-// std::llround of a float as the reference's x86-64 build evaluates it: out-of-range and NaN arguments give INT64_MIN
-static int64_t SplineRound(float v) { return fabsf(v) < 9.0e18f ? (int64_t)llroundf(v) : INT64_MIN; }
-
-// Splines of the current frame (FrameHeader::kSplines): the draw list of Splines::InitializeDrawCache for the frame's
-// size and base colour correlation, binned by 64 x 16 tile for k_splines; frame_begin resets to "no splines".
-int jxlhip_set_splines(jxlhip_ctx* c, const jxlhip_splines* s) {
-  if (!c) return JXLHIP_ERR_INVALID_ARGUMENT;
-  if (c->multi) return Fail(c, JXLHIP_ERR_UNSUPPORTED, "splines on a multi-device context");
-  if (!c->have_frame) return Fail(c, JXLHIP_ERR_STATE, "set_splines before frame_begin");
-  if (c->f.group_y0 != 0 || c->f.group_rows != c->f.ysg) return Fail(c, JXLHIP_ERR_UNSUPPORTED, "splines with stripes");
-  if (c->p.undo_orientation > 1)
-    return Fail(c, JXLHIP_ERR_UNSUPPORTED, "splines with undo_orientation %u", c->p.undo_orientation);
-  c->splines_on = false;
-  if (!s) return JXLHIP_OK;
-  if (c->dc_only_on) return Fail(c, JXLHIP_ERR_UNSUPPORTED, "splines on a frame with DC-only groups");
-  const uint32_t W = c->f.xsize, H = c->f.ysize;
-  // an upsampled frame: the draw cache is made for the upsampled size (dec_frame.cc:304-308), the stage draws the
-  // rows and columns of the coded frame
-  const uint32_t DW = (uint32_t)OutCols(c), DH = c->ups_factor > 1 ? c->ups_ysize : H;
-  HIPCHK(c, hipSetDevice(c->device));
-  if (c->spl_ev_pending) {  // the previous frame's upload still reads the host copies
-    HIPCHK(c, hipEventSynchronize(c->spl_ev));
-    c->spl_ev_pending = false;
-  }
-  size_t n = 0;
-  int rc = jxlhip_splines_segments(s, DW, DH, c->p.cfl_base_x, c->p.cfl_base_b, nullptr, 0, &n);
-  if (rc) return Fail(c, rc, "invalid splines");
-  std::vector<jxlhip_spline_segment> segs(n);
-  if (n && (rc = jxlhip_splines_segments(s, DW, DH, c->p.cfl_base_x, c->p.cfl_base_b, segs.data(), n, &n)))
-    return Fail(c, rc, "invalid splines");
-  // bin by tile: the column span of DrawSegment (splines.cc:116-125) clipped to the frame, the row span as computed
-  const uint32_t tx = (W + 63) / 64, ty = (H + 15) / 16, tiles = tx * ty;
-  std::vector<SplineSeg>& hs = c->spl_host_segs;
-  hs.clear();
-  std::vector<uint32_t> count(tiles + 1, 0);
-  for (const jxlhip_spline_segment& g : segs) {
-    const int64_t start = SplineRound(g.center_x - g.maximum_distance);
-    const int64_t end = SplineRound(g.center_x + g.maximum_distance);
-    if (end < 0 || start >= (int64_t)W || g.y1 <= g.y0 || g.y0 >= (int64_t)H) continue;
-    SplineSeg d;
-    d.cx = g.center_x;
-    d.cy = g.center_y;
-    d.inv_sigma = g.inv_sigma;
-    d.s4i = g.sigma_over_4_times_intensity;
-    for (int k = 0; k < 3; k++) d.color[k] = g.color[k];
-    d.y0 = g.y0;
-    d.y1 = (int32_t)std::min<int64_t>(g.y1, (int64_t)H);
-    d.x0 = (int32_t)std::max<int64_t>(start, 0);
-    d.x1 = (int32_t)std::min<int64_t>(end, (int64_t)W - 1);
-    d.pad = 0.0f;
-    hs.push_back(d);
-    for (uint32_t y = (uint32_t)d.y0 / 16; y <= (uint32_t)(d.y1 - 1) / 16; y++)
-      for (uint32_t x = (uint32_t)d.x0 / 64; x <= (uint32_t)d.x1 / 64; x++) count[y * tx + x + 1]++;
-  }
-  std::vector<uint32_t>& ht = c->spl_host_tiles;
-  ht.assign(tiles + 1, 0);
-  uint32_t active = 0;
-  for (uint32_t t = 0; t < tiles; t++) {
-    active += count[t + 1] != 0;
-    ht[t + 1] = ht[t] + count[t + 1];
-  }
-  const size_t entries = ht[tiles];
-  if (entries == 0) return JXLHIP_OK;  // nothing reaches the frame: the spline-free path
-  if (entries > 0xFFFFFFFFu - tiles) return Fail(c, JXLHIP_ERR_OUT_OF_MEMORY, "spline draw list too long");
-  ht.resize(tiles + 1 + entries + active);
-  uint32_t* fill = count.data();  // write cursor per tile
-  for (uint32_t t = 0; t < tiles; t++) fill[t] = ht[t];
-  for (uint32_t i = 0; i < (uint32_t)hs.size(); i++) {
-    const SplineSeg& d = hs[i];
-    for (uint32_t y = (uint32_t)d.y0 / 16; y <= (uint32_t)(d.y1 - 1) / 16; y++)
-      for (uint32_t x = (uint32_t)d.x0 / 64; x <= (uint32_t)d.x1 / 64; x++) ht[tiles + 1 + fill[y * tx + x]++] = i;
-  }
-  for (uint32_t t = 0, a = 0; t < tiles; t++)
-    if (ht[t + 1] != ht[t]) ht[tiles + 1 + entries + a++] = t;
-  if ((rc = c->spl_segs.Reserve(c, hs.size()))) return rc;
-  if ((rc = c->spl_tiles.Reserve(c, ht.size()))) return rc;
-  HIPCHK(c, hipMemcpyAsync(c->spl_segs, hs.data(), hs.size() * sizeof(SplineSeg), hipMemcpyHostToDevice, c->stream));
-  HIPCHK(c, hipMemcpyAsync(c->spl_tiles, ht.data(), ht.size() * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
-  HIPCHK(c, c->spl_ev.Create());
-  HIPCHK(c, hipEventRecord(c->spl_ev, c->stream));
-  c->spl_ev_pending = true;
-  c->spl_tiles_x = tx;
-  c->spl_num_tiles = tiles;
-  c->spl_num_active = active;
-  c->spl_entries = entries;
-  c->splines_on = true;
-  return JXLHIP_OK;
-}
-
-// A reference frame for patches: three XYB planes into slot `slot` of the context (dense, xsize floats per row).
-int jxlhip_set_reference_frame(jxlhip_ctx* c, uint32_t slot, uint32_t xsize, uint32_t ysize, const float* const planes[3],
-                               size_t stride_floats, int on_device) {
-  if (!c || slot > 3) return JXLHIP_ERR_INVALID_ARGUMENT;
-  if (c->multi) return Fail(c, JXLHIP_ERR_UNSUPPORTED, "reference frames on a multi-device context");
-  c->ref_serial++;  // (an uploaded dictionary points into the slots: DecodeFrameFeatures refuses it from here on)
-  c->seq_open = false;  // (a sequence of jxlhip_decode_codestream_next must not go on over slots emptied behind its back)
-  c->canvas_w[slot] = c->canvas_h[slot] = 0;  // (a slot holds one kind: an XYB frame drops the canvas)
-  c->canvas_nec[slot] = 0;                     // (... and its extra-channel planes)
-  if (xsize == 0 || ysize == 0) {  // cleared; the memory stays for the next frame of the slot
-    c->ref_w[slot] = c->ref_h[slot] = 0;
-    return JXLHIP_OK;
-  }
-  if (!planes || !planes[0] || !planes[1] || !planes[2]) return Fail(c, JXLHIP_ERR_INVALID_ARGUMENT, "null reference plane");
-  if (stride_floats < xsize) return Fail(c, JXLHIP_ERR_INVALID_ARGUMENT, "reference stride %zu < xsize", stride_floats);
-  HIPCHK(c, hipSetDevice(c->device));
-  c->ref_w[slot] = c->ref_h[slot] = 0;
-  const size_t plane = (size_t)xsize * ysize;
-  HIPCHK(c, hipStreamSynchronize(c->stream));  // an earlier frame's k_patches may still read the slot
-  const int rc = c->ref_planes[slot].Reserve(c, 3 * plane);
-  if (rc) return rc;
-  for (int k = 0; k < 3; k++)
-    HIPCHK(c, hipMemcpy2DAsync(c->ref_planes[slot] + k * plane, xsize * sizeof(float), planes[k], stride_floats * sizeof(float),
-                               xsize * sizeof(float), ysize, on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice,
-                               c->stream));
-  HIPCHK(c, hipStreamSynchronize(c->stream));  // (the caller's planes are free when this returns)
-  c->ref_w[slot] = xsize;
-  c->ref_h[slot] = ysize;
-  return JXLHIP_OK;
-}
-
-// Patches of the current frame (FrameHeader::kPatches): the dictionary as records of k_patches, binned by 64 x 16 tile
-// in dictionary order; frame_begin resets to "no patches".
-int jxlhip_set_patches(jxlhip_ctx* c, const jxlhip_patches* s) {
-  if (!c) return JXLHIP_ERR_INVALID_ARGUMENT;
-  if (c->multi) return Fail(c, JXLHIP_ERR_UNSUPPORTED, "patches on a multi-device context");
-  if (!c->have_frame) return Fail(c, JXLHIP_ERR_STATE, "set_patches before frame_begin");
-  if (c->f.group_y0 != 0 || c->f.group_rows != c->f.ysg) return Fail(c, JXLHIP_ERR_UNSUPPORTED, "patches with stripes");
-  if (c->p.undo_orientation > 1)
-    return Fail(c, JXLHIP_ERR_UNSUPPORTED, "patches with undo_orientation %u", c->p.undo_orientation);
-  c->patches_on = false;
-  if (!s) return JXLHIP_OK;
-  uint32_t n = 0, nec = 0, uses_ec = 0;
-  int rc = jxlhip_patches_list(s, &n, &nec, &uses_ec, nullptr, nullptr);
-  if (rc) return Fail(c, rc, "invalid patch dictionary");
-  if (n == 0) return JXLHIP_OK;  // nothing reaches the frame: the plain path
-  if (c->dc_only_on) return Fail(c, JXLHIP_ERR_UNSUPPORTED, "patches on a frame with DC-only groups");
-  if (uses_ec) return Fail(c, JXLHIP_ERR_UNSUPPORTED, "patches that blend extra channels");
-  if (c->fp.alpha) return Fail(c, JXLHIP_ERR_UNSUPPORTED, "patches on a frame with alpha (they would have to blend it)");
-  std::vector<jxlhip_patch> list(n);
-  if ((rc = jxlhip_patches_list(s, &n, nullptr, nullptr, list.data(), nullptr))) return Fail(c, rc, "invalid patch dictionary");
-  const uint32_t W = c->f.xsize, H = c->f.ysize;
-  const uint64_t WP = ((uint64_t)W + 7) & ~7ull, HP = ((uint64_t)H + 7) & ~7ull;  // FrameDimensions::xsize_padded
-  HIPCHK(c, hipSetDevice(c->device));
-  if (c->pat_ev_pending) {  // the previous frame's upload still reads the host copies
-    HIPCHK(c, hipEventSynchronize(c->pat_ev));
-    c->pat_ev_pending = false;
-  }
-  const uint32_t tx = (W + 63) / 64, ty = (H + 15) / 16, tiles = tx * ty;
-  std::vector<PatchRec>& hr = c->pat_host_recs;
-  hr.clear();
-  std::vector<uint32_t> count(tiles + 1, 0);
-  for (uint32_t i = 0; i < n; i++) {
-    const jxlhip_patch& p = list[i];
-    if (p.ref <= 3 && c->canvas_w[p.ref] != 0)
-      return Fail(c, JXLHIP_ERR_INVALID_ARGUMENT, "patch %u: slot %u holds a frame saved after the colour transform", i, p.ref);
-    if (p.ref > 3 || c->ref_w[p.ref] == 0)
-      return Fail(c, JXLHIP_ERR_INVALID_ARGUMENT, "patch %u: reference slot %u is empty", i, p.ref);
-    const uint32_t rw = c->ref_w[p.ref], rh = c->ref_h[p.ref];
-    if (p.xsize == 0 || p.ysize == 0 || (uint64_t)p.ref_x0 + p.xsize > rw || (uint64_t)p.ref_y0 + p.ysize > rh)
-      return Fail(c, JXLHIP_ERR_INVALID_ARGUMENT, "patch %u: %ux%u at (%u, %u) leaves the %ux%u frame of slot %u", i, p.xsize,
-                  p.ysize, p.ref_x0, p.ref_y0, rw, rh, p.ref);
-    if ((uint64_t)p.x + p.xsize > WP || (uint64_t)p.y + p.ysize > HP)
-      return Fail(c, JXLHIP_ERR_INVALID_ARGUMENT, "patch %u: %ux%u at (%u, %u) leaves the frame", i, p.xsize, p.ysize, p.x, p.y);
-    if (p.mode > 7) return Fail(c, JXLHIP_ERR_INVALID_ARGUMENT, "patch %u: blend mode %u", i, p.mode);
-    if (p.mode == JXLHIP_PATCH_NONE || p.x >= W || p.y >= H) continue;  // the frame keeps its samples
-    PatchRec r;
-    r.x0 = (int32_t)p.x;
-    r.y0 = (int32_t)p.y;
-    r.x1 = (int32_t)std::min<uint64_t>((uint64_t)p.x + p.xsize, W);
-    r.y1 = (int32_t)std::min<uint64_t>((uint64_t)p.y + p.ysize, H);
-    r.src = c->ref_planes[p.ref] + (size_t)p.ref_y0 * rw + p.ref_x0;
-    r.stride = rw;
-    r.plane = rw * rh;
-    // PerformBlending's colour modes without an alpha channel (blending.cc:150-184)
-    r.op = p.mode == JXLHIP_PATCH_MUL ? (p.clamp ? kPatchOpMulClamp : kPatchOpMul)
-           : (p.mode == JXLHIP_PATCH_ADD || p.mode >= JXLHIP_PATCH_ALPHA_WEIGHTED_ADD_ABOVE) ? kPatchOpAdd
-                                                                                             : kPatchOpReplace;
-    r.pad = 0;
-    hr.push_back(r);
-    for (uint32_t y = (uint32_t)r.y0 / 16; y <= (uint32_t)(r.y1 - 1) / 16; y++)
-      for (uint32_t x = (uint32_t)r.x0 / 64; x <= (uint32_t)(r.x1 - 1) / 64; x++) count[y * tx + x + 1]++;
-  }
-  std::vector<uint32_t>& ht = c->pat_host_tiles;
-  ht.assign(tiles + 1, 0);
-  uint32_t active = 0;
-  uint64_t total = 0;
-  for (uint32_t t = 0; t < tiles; t++) {
-    active += count[t + 1] != 0;
-    total += count[t + 1];
-    ht[t + 1] = (uint32_t)total;
-  }
-  if (total == 0) return JXLHIP_OK;
-  if (total > 0xFFFFFFFFull - tiles - active - 1) return Fail(c, JXLHIP_ERR_OUT_OF_MEMORY, "patch list too long");
-  const size_t entries = (size_t)total;
-  ht.resize(tiles + 1 + entries + active);
-  uint32_t* fill = count.data();  // write cursor per tile
-  for (uint32_t t = 0; t < tiles; t++) fill[t] = ht[t];
-  for (uint32_t i = 0; i < (uint32_t)hr.size(); i++) {
-    const PatchRec& r = hr[i];
-    for (uint32_t y = (uint32_t)r.y0 / 16; y <= (uint32_t)(r.y1 - 1) / 16; y++)
-      for (uint32_t x = (uint32_t)r.x0 / 64; x <= (uint32_t)(r.x1 - 1) / 64; x++) ht[tiles + 1 + fill[y * tx + x]++] = i;
-  }
-  for (uint32_t t = 0, a = 0; t < tiles; t++)
-    if (ht[t + 1] != ht[t]) ht[tiles + 1 + entries + a++] = t;
-  if ((rc = c->pat_recs.Reserve(c, hr.size()))) return rc;
-  if ((rc = c->pat_tiles.Reserve(c, ht.size()))) return rc;
-  HIPCHK(c, hipMemcpyAsync(c->pat_recs, hr.data(), hr.size() * sizeof(PatchRec), hipMemcpyHostToDevice, c->stream));
-  HIPCHK(c, hipMemcpyAsync(c->pat_tiles, ht.data(), ht.size() * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
-  HIPCHK(c, c->pat_ev.Create());
-  HIPCHK(c, hipEventRecord(c->pat_ev, c->stream));
-  c->pat_ev_pending = true;
-  c->pat_tiles_x = tx;
-  c->pat_num_tiles = tiles;
-  c->pat_num_active = active;
-  c->pat_entries = entries;
-  c->pat_ref_serial = c->ref_serial;
-  c->patches_on = true;
-  return JXLHIP_OK;
-}
-
-// Upsampling of the current frame (FrameHeader::upsampling): the factor, its kernels (UpsamplingStage's constructor on
-// the coded or the default weights) and the size the frame comes out at; frame_begin resets to "not upsampled".
-int jxlhip_set_upsampling(jxlhip_ctx* c, uint32_t factor, const float* weights, uint32_t out_xsize, uint32_t out_ysize) {
-  if (!c) return JXLHIP_ERR_INVALID_ARGUMENT;
-  if (c->multi) return Fail(c, JXLHIP_ERR_UNSUPPORTED, "upsampling on a multi-device context");
-  if (!c->have_frame) return Fail(c, JXLHIP_ERR_STATE, "set_upsampling before frame_begin");
-  if (factor != 1 && factor != 2 && factor != 4 && factor != 8)
-    return Fail(c, JXLHIP_ERR_INVALID_ARGUMENT, "upsampling factor %u", factor);
-  if (factor == 1) {
-    // (a draw list made for the upsampled size must not outlive it)
-    if (c->ups_factor > 1 && c->splines_on)
-      return Fail(c, JXLHIP_ERR_STATE, "set_upsampling after set_splines (the draw list depends on it)");
-    c->ups_factor = 1;
-    return JXLHIP_OK;
-  }
-  if (c->f.group_y0 != 0 || c->f.group_rows != c->f.ysg) return Fail(c, JXLHIP_ERR_UNSUPPORTED, "upsampling with stripes");
-  if (c->p.undo_orientation > 1)
-    return Fail(c, JXLHIP_ERR_UNSUPPORTED, "upsampling with undo_orientation %u", c->p.undo_orientation);
-  if (c->fp.alpha) return Fail(c, JXLHIP_ERR_UNSUPPORTED, "alpha on an upsampled frame");
-  if (c->splines_on) return Fail(c, JXLHIP_ERR_STATE, "set_upsampling after set_splines (the draw list depends on it)");
-  if (c->dc_only_on) return Fail(c, JXLHIP_ERR_UNSUPPORTED, "upsampling on a frame with DC-only groups");
-  if (out_xsize == 0 || out_ysize == 0 || (out_xsize + factor - 1) / factor != c->f.xsize ||
-      (out_ysize + factor - 1) / factor != c->f.ysize)
-    return Fail(c, JXLHIP_ERR_INVALID_ARGUMENT, "a %ux%u frame upsampled %ux does not give %ux%u", c->f.xsize, c->f.ysize,
-                factor, out_xsize, out_ysize);
-  HIPCHK(c, hipSetDevice(c->device));
-  const float* coded = weights ? weights : factor == 2 ? kUpsampling2Weights : factor == 4 ? kUpsampling4Weights : kUpsampling8Weights;
-  UpsampleKernels(factor, coded, c->ups_weights_host);
-  const int rc = c->ups_weights.Reserve(c, 64 * 25);
-  if (rc) return rc;
-  // (a pageable source: staged by the runtime when hipMemcpyAsync returns, the next frame may overwrite it)
-  HIPCHK(c, hipMemcpyAsync(c->ups_weights, c->ups_weights_host, sizeof(float) * factor * factor * 25, hipMemcpyHostToDevice,
-                           c->stream));
-  c->ups_factor = factor;
-  c->ups_xsize = out_xsize;
-  c->ups_ysize = out_ysize;
-  return JXLHIP_OK;
-}
-
-// DC-only groups of the current frame (FrameDecoder::Flush on a group without AC, dec_frame.cc:737-797): the mask and
-// the 8x kernels go up here; the decode calls zero the groups' coefficient slots and launch k_dc_upsample8 behind
-// phase 1 (LaunchDcOnly); frame_begin resets to "none".
-int jxlhip_set_dc_only_groups(jxlhip_ctx* c, const uint8_t* mask, const float* weights8) {
-  if (!c) return JXLHIP_ERR_INVALID_ARGUMENT;
-  if (c->multi) return Fail(c, JXLHIP_ERR_UNSUPPORTED, "DC-only groups on a multi-device context");
-  if (!c->have_frame) return Fail(c, JXLHIP_ERR_STATE, "set_dc_only_groups before frame_begin");
-  c->dc_only_on = false;
-  const size_t ng = (size_t)c->f.xsg * c->f.ysg;
-  bool any = false;
-  for (size_t g = 0; mask && g < ng; g++) any = any || mask[g] != 0;
-  if (!any) return JXLHIP_OK;  // the frame's own path, untouched
-  if (c->f.group_y0 != 0 || c->f.group_rows != c->f.ysg) return Fail(c, JXLHIP_ERR_UNSUPPORTED, "DC-only groups with stripes");
-  const char* other = c->noise_on ? "noise" : c->splines_on ? "splines" : c->patches_on ? "patches" : c->ups_factor > 1 ? "upsampling"
-                      : c->blend_on ? "blending" : c->fp.alpha ? "alpha" : nullptr;
-  if (other) return Fail(c, JXLHIP_ERR_UNSUPPORTED, "DC-only groups on a frame with %s", other);
-  HIPCHK(c, hipSetDevice(c->device));
-  int rc;
-  if ((rc = c->dc_only_mask.Reserve(c, ng)) || (rc = c->dc_only_weights.Reserve(c, 25 * 64))) return rc;
-  float kernels[64 * 25], tap_major[25 * 64];
-  UpsampleKernels(8, weights8 ? weights8 : kUpsampling8Weights, kernels);
-  DcUpsampleWeights(kernels, tap_major);
-  c->dc_only_host.assign(mask, mask + ng);
-  // (pageable sources: staged by the runtime when hipMemcpyAsync returns)
-  HIPCHK(c, hipMemcpyAsync(c->dc_only_mask, c->dc_only_host.data(), ng, hipMemcpyHostToDevice, c->stream));
-  HIPCHK(c, hipMemcpyAsync(c->dc_only_weights, tap_major, sizeof(tap_major), hipMemcpyHostToDevice, c->stream));
-  c->dc_only_on = true;
-  return JXLHIP_OK;
-}
-
-// Blending of the current frame (FrameHeader::blending_info, frame_origin, save_as_reference): recorded here, carried
-// out by DecodeFrameBlended; frame_begin resets to "not blended".
-int jxlhip_set_blending(jxlhip_ctx* c, const jxlhip_blend_params* b) {
-  if (!c) return JXLHIP_ERR_INVALID_ARGUMENT;
-  if (c->multi) return Fail(c, JXLHIP_ERR_UNSUPPORTED, "blending on a multi-device context");
-  if (!c->have_frame) return Fail(c, JXLHIP_ERR_STATE, "set_blending before frame_begin");
-  c->blend_on = false;
-  c->blend_ec_on = false;
-  if (!b) return JXLHIP_OK;
-  if (c->dc_only_on) return Fail(c, JXLHIP_ERR_UNSUPPORTED, "blending on a frame with DC-only groups");
-  if (c->f.group_y0 != 0 || c->f.group_rows != c->f.ysg) return Fail(c, JXLHIP_ERR_UNSUPPORTED, "blending with stripes");
-  if (c->p.undo_orientation > 1)
-    return Fail(c, JXLHIP_ERR_UNSUPPORTED, "blending with undo_orientation %u", c->p.undo_orientation);
-  if (c->p.output_kind == JXLHIP_OUT_XYB_PLANAR)
-    return Fail(c, JXLHIP_ERR_UNSUPPORTED, "blending with planar XYB output (canvases are frames saved after the colour transform)");
-  if (c->fp.alpha) return Fail(c, JXLHIP_ERR_UNSUPPORTED, "blending on a frame with alpha (blending extra channels is not in the back-end)");
-  if (c->tm_on) return Fail(c, JXLHIP_ERR_UNSUPPORTED, "blending on a tone-mapped frame (tone mapping behind a blend is not in the back-end)");
-  if (b->image_xsize == 0 || b->image_ysize == 0 || b->image_xsize > (1u << 19) || b->image_ysize > (1u << 19))
-    return Fail(c, JXLHIP_ERR_INVALID_ARGUMENT, "image size %ux%u out of range", b->image_xsize, b->image_ysize);
-  if (b->x0 < -(1 << 30) || b->x0 > (1 << 30) || b->y0 < -(1 << 30) || b->y0 > (1 << 30))
-    return Fail(c, JXLHIP_ERR_INVALID_ARGUMENT, "frame origin (%d, %d) out of range", b->x0, b->y0);
-  if (b->mode > JXLHIP_BLEND_MUL) return Fail(c, JXLHIP_ERR_INVALID_ARGUMENT, "blend mode %u", b->mode);
-  if (b->source > 3 || (b->save_slot > 3 && b->save_slot != JXLHIP_BLEND_NO_SAVE))
-    return Fail(c, JXLHIP_ERR_INVALID_ARGUMENT, "blend source slot %u / save slot %u", b->source, b->save_slot);
-  c->blend = *b;
-  c->blend_on = true;
-  return JXLHIP_OK;
-}
-
-int jxlhip_canvas_read(jxlhip_ctx* c, uint32_t slot, float* dev_out, size_t stride_floats, uint32_t* w, uint32_t* h) {
-  if (!c || slot > 3 || !w || !h) return JXLHIP_ERR_INVALID_ARGUMENT;
-  if (c->multi) return Fail(c, JXLHIP_ERR_UNSUPPORTED, "canvases on a multi-device context");
-  *w = c->canvas_w[slot];
-  *h = c->canvas_h[slot];
-  if (!dev_out || *w == 0) return JXLHIP_OK;
-  if (stride_floats < 3 * (size_t)*w) return Fail(c, JXLHIP_ERR_INVALID_ARGUMENT, "canvas stride %zu < 3 * %u", stride_floats, *w);
-  HIPCHK(c, hipSetDevice(c->device));
-  HIPCHK(c, hipMemcpy2DAsync(dev_out, stride_floats * sizeof(float), c->canvas[slot], CanvasStride(*w) * sizeof(float),
-                             3 * (size_t)*w * sizeof(float), *h, hipMemcpyDeviceToDevice, c->stream));
-  return JXLHIP_OK;
-}
-
-namespace {
-bool Capturing(hipStream_t st);  // (below, with the launches)
-}
-
-// What DecodeFrameBlended and jxlhip_set_blending_extra both need to know about a blended frame of an image with extra
-// channels: whether the colour's mode comes to "replace" (PerformBlending's copy(fg)), and whether nothing of any
-// source is read at all (a full-size frame at the origin whose colour and extra channels all replace).
-static bool EcHasAlpha(const jxlhip_blend_extra_params& e) {
-  for (uint32_t i = 0; i < e.num_extra_channels; i++)
-    if (e.channel[i].is_alpha) return true;
-  return false;
-}
-static bool EcSourcesDead(const jxlhip_ctx* c, const jxlhip_blend_extra_params& e) {
-  const jxlhip_blend_params& b = c->blend;
-  const bool full = b.x0 == 0 && b.y0 == 0 && OutCols(c) == b.image_xsize && OutRows(c) == b.image_ysize;
-  bool replaces = b.mode == JXLHIP_BLEND_REPLACE || (b.mode == JXLHIP_BLEND_BLEND && !EcHasAlpha(e));
-  for (uint32_t i = 0; i < e.num_extra_channels; i++) replaces = replaces && e.channel[i].mode == JXLHIP_BLEND_REPLACE;
-  return full && replaces;
-}
-// the source slots of the extra channels, as DecodeFrameBlended checks the colour's
-static int CheckEcSources(jxlhip_ctx* c, const jxlhip_blend_extra_params& e) {
-  if (EcSourcesDead(c, e)) return JXLHIP_OK;
-  const uint32_t W = c->blend.image_xsize, H = c->blend.image_ysize;
-  for (uint32_t i = 0; i < e.num_extra_channels; i++) {
-    const uint32_t s = e.channel[i].source;
-    if (c->ref_w[s] != 0)
-      return Fail(c, JXLHIP_ERR_INVALID_ARGUMENT, "blend source slot %u of extra channel %u holds an XYB reference frame", s, i);
-    if (c->canvas_w[s] != 0 && (c->canvas_w[s] < W || c->canvas_h[s] < H))
-      return Fail(c, JXLHIP_ERR_INVALID_ARGUMENT, "the %ux%u canvas of slot %u (extra channel %u) is smaller than the %ux%u image",
-                  c->canvas_w[s], c->canvas_h[s], s, i, W, H);
-  }
-  return JXLHIP_OK;
-}
-
-// The extra channels of the current blended frame (FrameHeader::extra_channel_blending_info, ExtraChannelInfo):
-// recorded and uploaded here, carried out by DecodeFrameBlended with k_ec_blend; frame_begin and set_blending reset.
-int jxlhip_set_blending_extra(jxlhip_ctx* c, const jxlhip_blend_extra_params* e) {
-  if (!c || !e) return JXLHIP_ERR_INVALID_ARGUMENT;
-  if (c->multi) return Fail(c, JXLHIP_ERR_UNSUPPORTED, "blending on a multi-device context");
-  if (!c->have_frame) return Fail(c, JXLHIP_ERR_STATE, "set_blending_extra before frame_begin");
-  c->blend_ec_on = false;
-  if (!c->blend_on) return Fail(c, JXLHIP_ERR_STATE, "set_blending_extra without set_blending on this frame");
-  if (c->fp.alpha) return Fail(c, JXLHIP_ERR_UNSUPPORTED, "set_blending_extra on a frame with set_alpha (the alpha channel is one of the planes here)");
-  if (c->ups_factor > 1) return Fail(c, JXLHIP_ERR_UNSUPPORTED, "extra channels of an upsampled frame");
-  if (c->patches_on) return Fail(c, JXLHIP_ERR_UNSUPPORTED, "extra channels of a frame with patches (they would have to blend them)");
-  const uint32_t n = e->num_extra_channels;
-  if (n == 0 || n > 4) return Fail(c, JXLHIP_ERR_INVALID_ARGUMENT, "%u extra channels (1..4)", n);
-  if (e->color_alpha_channel >= n) return Fail(c, JXLHIP_ERR_INVALID_ARGUMENT, "colour alpha channel %u of %u", e->color_alpha_channel, n);
-  const size_t fw = c->f.xsize, fh = c->f.ysize;
-  for (uint32_t i = 0; i < n; i++) {
-    const jxlhip_blend_extra_channel& ch = e->channel[i];
-    if (ch.mode > JXLHIP_BLEND_MUL) return Fail(c, JXLHIP_ERR_INVALID_ARGUMENT, "extra channel %u: blend mode %u", i, ch.mode);
-    if (ch.alpha_channel >= n) return Fail(c, JXLHIP_ERR_INVALID_ARGUMENT, "extra channel %u: alpha channel %u of %u", i, ch.alpha_channel, n);
-    if (ch.source > 3) return Fail(c, JXLHIP_ERR_INVALID_ARGUMENT, "extra channel %u: blend source slot %u", i, ch.source);
-    if (!e->planes[i]) return Fail(c, JXLHIP_ERR_INVALID_ARGUMENT, "extra channel %u: null plane", i);
-  }
-  if (e->stride_floats < fw) return Fail(c, JXLHIP_ERR_INVALID_ARGUMENT, "extra channel stride %zu < xsize", e->stride_floats);
-  int rc = CheckEcSources(c, *e);
-  if (rc) return rc;
-  HIPCHK(c, hipSetDevice(c->device));
-  // staged like the colour: (x0 mod 4) floats into rows padded to four pixels (kernels_blend_ec.hip)
-  const size_t lead = (size_t)(c->blend.x0 - (c->blend.x0 & ~3));
-  const size_t stride = EcStride((uint32_t)(lead + fw));
-  const size_t need = n * fh * stride;
-  if (need > c->blend_ec_stage.n) {
-    if (Capturing(c->stream)) return Fail(c, JXLHIP_ERR_UNSUPPORTED, "blending while the stream is being captured");
-    HIPCHK(c, hipStreamSynchronize(c->stream));  // an earlier launch may still read the planes
-    if ((rc = c->blend_ec_stage.Reserve(c, need))) return rc;
-    // (the padding is read, never used: zeroed once so that nothing reads memory nobody wrote)
-    HIPCHK(c, hipMemsetAsync(c->blend_ec_stage, 0, need * sizeof(float), c->stream));
-  }
-  for (uint32_t i = 0; i < n; i++)
-    HIPCHK(c, hipMemcpy2DAsync(c->blend_ec_stage + i * fh * stride + lead, stride * sizeof(float), e->planes[i],
-                               e->stride_floats * sizeof(float), fw * sizeof(float), fh, hipMemcpyHostToDevice, c->stream));
-  c->blend_ec_stage_stride = stride;
-  c->blend_ec = *e;
-  for (int i = 0; i < 4; i++) c->blend_ec.planes[i] = nullptr;
-  c->blend_ec_on = true;
-  return JXLHIP_OK;
-}
-
-int jxlhip_canvas_read_extra(jxlhip_ctx* c, uint32_t slot, uint32_t ec, float* dev_out, size_t stride_floats, uint32_t* w,
-                             uint32_t* h) {
-  if (!c || slot > 3 || ec > 3 || !w || !h) return JXLHIP_ERR_INVALID_ARGUMENT;
-  if (c->multi) return Fail(c, JXLHIP_ERR_UNSUPPORTED, "canvases on a multi-device context");
-  const bool have = c->canvas_w[slot] != 0 && ec < c->canvas_nec[slot];
-  *w = have ? c->canvas_w[slot] : 0;
-  *h = have ? c->canvas_h[slot] : 0;
-  if (!dev_out || !have) return JXLHIP_OK;
-  if (stride_floats < *w) return Fail(c, JXLHIP_ERR_INVALID_ARGUMENT, "plane stride %zu < %u", stride_floats, *w);
-  HIPCHK(c, hipSetDevice(c->device));
-  const size_t es = EcStride(*w);
-  HIPCHK(c, hipMemcpy2DAsync(dev_out, stride_floats * sizeof(float), c->canvas_ec[slot] + (size_t)ec * *h * es, es * sizeof(float),
-                             (size_t)*w * sizeof(float), *h, hipMemcpyDeviceToDevice, c->stream));
-  return JXLHIP_OK;
-}
-
-int jxlhip_frame_extra_read(jxlhip_ctx* c, uint32_t ec, float* dev_out, size_t stride_floats) {
-  if (!c || !dev_out || ec > 3) return JXLHIP_ERR_INVALID_ARGUMENT;
-  if (c->multi) return Fail(c, JXLHIP_ERR_UNSUPPORTED, "canvases on a multi-device context");
-  if (ec >= c->frame_ec_n) return Fail(c, JXLHIP_ERR_STATE, "the current frame has no blended plane of extra channel %u", ec);
-  const uint32_t w = c->frame_ec_w, h = c->frame_ec_h;
-  if (stride_floats < w) return Fail(c, JXLHIP_ERR_INVALID_ARGUMENT, "plane stride %zu < %u", stride_floats, w);
-  HIPCHK(c, hipSetDevice(c->device));
-  const size_t es = EcStride(w);
-  HIPCHK(c, hipMemcpy2DAsync(dev_out, stride_floats * sizeof(float), c->frame_ec_planes + (size_t)ec * h * es, es * sizeof(float),
-                             (size_t)w * sizeof(float), h, hipMemcpyDeviceToDevice, c->stream));
-  return JXLHIP_OK;
-}
-
-// ToneMappingStage's constructor for `t` (stage_tone_mapping.cc:33-64): 1 = the Rec.2408 tone mapper is built, 0 = no
-// stage (the frame's plain path), else the error (with its reason in c->err when c is given)
-static int ToneMappingKind(jxlhip_ctx* c, const jxlhip_tone_mapping* t) {
-  if (!(t->orig_intensity_target > 0.0f) || !(t->desired_intensity_target > 0.0f) || !std::isfinite(t->orig_intensity_target) ||
-      !std::isfinite(t->desired_intensity_target))
-    return Fail(c, JXLHIP_ERR_INVALID_ARGUMENT, "tone mapping: intensity targets %g -> %g", t->orig_intensity_target,
-                t->desired_intensity_target);
-  for (int i = 0; i < 3; i++)
-    if (!std::isfinite(t->luminances[i])) return Fail(c, JXLHIP_ERR_INVALID_ARGUMENT, "tone mapping: luminance %d is not finite", i);
-  if (t->orig_transfer > JXLHIP_TF_HLG) return Fail(c, JXLHIP_ERR_INVALID_ARGUMENT, "tone mapping: orig_transfer %u", t->orig_transfer);
-  if (t->desired_intensity_target == t->orig_intensity_target) return 0;
-  if (t->orig_transfer == JXLHIP_TF_PQ) return t->desired_intensity_target < t->orig_intensity_target ? 1 : 0;
-  if (t->orig_transfer == JXLHIP_TF_HLG)
-    return Fail(c, JXLHIP_ERR_UNSUPPORTED, "tone mapping of an HLG original (the HlgOOTF branch is not in the back-end)");
-  return 0;
-}
-
-// Tone mapping of the current frame (JxlDecoderSetDesiredIntensityTarget): recorded here, carried out by
-// DecodeFrameToneMapped; frame_begin resets to "not tone-mapped".
-int jxlhip_set_tone_mapping(jxlhip_ctx* c, const jxlhip_tone_mapping* t) {
-  if (!c) return JXLHIP_ERR_INVALID_ARGUMENT;
-  if (c->multi) return Fail(c, JXLHIP_ERR_UNSUPPORTED, "tone mapping on a multi-device context");
-  if (!c->have_frame) return Fail(c, JXLHIP_ERR_STATE, "set_tone_mapping before frame_begin");
-  c->tm_on = false;
-  if (!t) return JXLHIP_OK;
-  const int kind = ToneMappingKind(c, t);
-  if (kind <= 0) return kind;
-  if (c->f.group_y0 != 0 || c->f.group_rows != c->f.ysg) return Fail(c, JXLHIP_ERR_UNSUPPORTED, "tone mapping with stripes");
-  if (c->p.undo_orientation > 1)
-    return Fail(c, JXLHIP_ERR_UNSUPPORTED, "tone mapping with undo_orientation %u", c->p.undo_orientation);
-  if (c->p.output_kind == JXLHIP_OUT_XYB_PLANAR)
-    return Fail(c, JXLHIP_ERR_UNSUPPORTED, "tone mapping with planar XYB output (the stage works on linear RGB)");
-  if (c->blend_on)
-    return Fail(c, JXLHIP_ERR_UNSUPPORTED, "tone mapping on a blended frame (tone mapping behind a blend is not in the back-end)");
-  const bool dest_pq = c->p.output_kind == JXLHIP_OUT_PACKED && c->p.out_format.transfer == JXLHIP_TF_PQ;
-  ToneMapHostConstants(t->orig_intensity_target, t->desired_intensity_target, t->luminances, dest_pq, &c->tm_k);
-  c->tm_on = true;
-  return JXLHIP_OK;
-}
-
-int jxlhip_tone_mapping_constants(const jxlhip_tone_mapping* t, uint32_t dest_transfer, float* out, size_t n) {
-  if (!t || !out || n > kToneMapConstants || dest_transfer > JXLHIP_TF_HLG) return JXLHIP_ERR_INVALID_ARGUMENT;
-  const int kind = ToneMappingKind(nullptr, t);
-  if (kind != 1) return JXLHIP_ERR_INVALID_ARGUMENT;
-  ToneMapConstants k;
-  ToneMapHostConstants(t->orig_intensity_target, t->desired_intensity_target, t->luminances, dest_transfer == JXLHIP_TF_PQ, &k);
-  memcpy(out, &k, n * sizeof(float));
-  return JXLHIP_OK;
-}
-
-int jxlhip_noise_rng_state(uint32_t visible_frame_index, uint32_t nonvisible_frame_index, uint32_t x0, uint32_t y0,
-                           uint64_t fills, uint64_t state[16]) {
-  if (!state) return JXLHIP_ERR_INVALID_ARGUMENT;
-  NoiseStateAfter(visible_frame_index, nonvisible_frame_index, x0, y0, fills, state);
-  return JXLHIP_OK;
-}
-
 // ---- decode -------------------------------------------------------------------
+bool jxlhip::Capturing(hipStream_t st) {
+  hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
+  (void)hipStreamIsCapturing(st, &cap);
+  return cap == hipStreamCaptureStatusActive;
+}
+
 namespace {
 
 // Phase 1 over the context's whole stripe (DevFrame::band_g0 / band_g1 = its group rows, set by jxlhip_frame_begin), in
@@ -1012,12 +481,6 @@ namespace {
 // calls prepare every time until the next jxlhip_frame_begin.
 // fused: 0 = two-phase, 1 = the whole frame through the fused kernel, 2 = a STRIPE through it (the DCT8 cells of
 // the stripe's first / last block row are decoded into the planes as well: they are the halo rows its neighbours pull)
-bool Capturing(hipStream_t st) {
-  hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
-  (void)hipStreamIsCapturing(st, &cap);
-  return cap == hipStreamCaptureStatusActive;
-}
-
 // the frame as both steps of phase 1 see it
 DevFrame Phase1Frame(const jxlhip_ctx* c, int fused) {
   DevFrame f = c->f;
@@ -1112,7 +575,8 @@ int LaunchPhase1(jxlhip_ctx* c, int fused = 0, const FilterParams* emit = nullpt
 // epf_iters = 3: [Gaborish] + EPF0 into the second plane set -- from the fused producer's slab (k_fused_pc0) or from
 // the planes (k_epf0) -- then EPF1 + EPF2 + output from there.  *declined: the EPF0 march does not take the geometry,
 // nothing was launched.
-int LaunchEpf0Then12(jxlhip_ctx* c, const DevFrame& f, const FilterParams& fp, bool fused, bool* declined) {
+int LaunchEpf0Then12(jxlhip_ctx* c, const DevFrame& f, const OutTarget& t, bool fused, bool* declined) {
+  const FilterParams& fp = t.fp;
   float* dst[3];
   const size_t plane_floats = (size_t)f.plane_tile_rows * f.tile_stride * 64;
   for (int ch = 0; ch < 3; ch++) dst[ch] = c->planes2 + ch * plane_floats;
@@ -1123,13 +587,14 @@ int LaunchEpf0Then12(jxlhip_ctx* c, const DevFrame& f, const FilterParams& fp, b
   DevFrame f2 = f;
   for (int ch = 0; ch < 3; ch++) f2.xyb[ch] = dst[ch];
   f2.linear_stride = f.tile_stride * 32u;
-  if (!LaunchFiltersFast(f2, fp, 0, 2, (int)c->p.output_kind, c->stream))
+  if (!LaunchFiltersFast(f2, fp, 0, 2, (int)t.kind, c->stream))
     return Fail(c, JXLHIP_ERR_STATE, "EPF1 + EPF2 march refused a frame the EPF0 march accepted");
   return JXLHIP_OK;
 }
 
 // phase 2 for pixel rows [fy0, fy1) of the stripe
-int LaunchFiltersRows(jxlhip_ctx* c, const FilterParams& fp, uint32_t fy0, uint32_t fy1, bool fused = false) {
+int LaunchFiltersRows(jxlhip_ctx* c, const OutTarget& t, uint32_t fy0, uint32_t fy1, bool fused = false) {
+  const FilterParams& fp = t.fp;
   DevFrame f = c->f;
   f.fy0 = fy0;
   f.fy1 = fy1;
@@ -1138,7 +603,7 @@ int LaunchFiltersRows(jxlhip_ctx* c, const FilterParams& fp, uint32_t fy0, uint3
   ProfBegin(c);
   if (fused && c->p.lf.epf_iters == 3) {
     bool declined;
-    const int rc = LaunchEpf0Then12(c, f, fp, true, &declined);
+    const int rc = LaunchEpf0Then12(c, f, t, true, &declined);
     if (rc) return rc;
     if (declined) return Fail(c, JXLHIP_ERR_STATE, "fused EPF0 kernel refused a frame FusedEpf0Supported accepted");
     ProfMark(c, JXLHIP_KERNEL_FILTERS);
@@ -1146,7 +611,7 @@ int LaunchFiltersRows(jxlhip_ctx* c, const FilterParams& fp, uint32_t fy0, uint3
     return JXLHIP_OK;
   }
   if (fused) {
-    if (!LaunchFused(f, fp, (int)c->p.lf.gab, (int)c->p.lf.epf_iters, (int)c->p.output_kind, c->stream))
+    if (!LaunchFused(f, fp, (int)c->p.lf.gab, (int)c->p.lf.epf_iters, (int)t.kind, c->stream))
       return Fail(c, JXLHIP_ERR_STATE, "fused kernel refused a frame FusedSupported accepted");
     ProfMark(c, JXLHIP_KERNEL_FUSED);
       HIPCHK(c, hipGetLastError());
@@ -1155,14 +620,13 @@ int LaunchFiltersRows(jxlhip_ctx* c, const FilterParams& fp, uint32_t fy0, uint3
   bool fast = false;
   if (!c->generic_filters && fy1 > fy0 && c->p.lf.epf_iters == 3 && c->planes2) {
     bool declined;  // (then the generic kernel below)
-    const int rc = LaunchEpf0Then12(c, f, fp, false, &declined);
+    const int rc = LaunchEpf0Then12(c, f, t, false, &declined);
     if (rc) return rc;
     fast = !declined;
   } else if (!c->generic_filters && fy1 > fy0) {
-    fast = LaunchFiltersFast(f, fp, (int)c->p.lf.gab, (int)c->p.lf.epf_iters, (int)c->p.output_kind, c->stream);
+    fast = LaunchFiltersFast(f, fp, (int)c->p.lf.gab, (int)c->p.lf.epf_iters, (int)t.kind, c->stream);
   }
-  if (!fast && LaunchFilters(f, fp, (int)c->p.lf.gab, (int)c->p.lf.epf_iters,
-                             (int)c->p.output_kind, c->stream) != 0)
+  if (!fast && LaunchFilters(f, fp, (int)c->p.lf.gab, (int)c->p.lf.epf_iters, (int)t.kind, c->stream) != 0)
     return Fail(c, JXLHIP_ERR_INVALID_ARGUMENT, "unsupported filter configuration");
   ProfMark(c, JXLHIP_KERNEL_FILTERS);
   HIPCHK(c, hipGetLastError());
@@ -1175,20 +639,16 @@ int LaunchFiltersRows(jxlhip_ctx* c, const FilterParams& fp, uint32_t fy0, uint3
 // only a detour (configs[4]: 76.1 vs 79.6 Gpx/s).  Packed outputs: the two-phase filter kernel has the formats djxl
 // writes most (8-bit sRGB RGB / RGBA, 16-bit sRGB RGB) fixed at compile time, the fused kernel only the general
 // per-sample format path -- measured at 8K d1.0: 0.42 ms two-phase against 0.74 - 0.82 ms fused
-// (profiles/r03_packed_paths.txt).
-bool WantFused(const jxlhip_ctx* c) {
+// (profiles/r03_packed_paths.txt).  kind, fmt: what the path would write (OutTarget).
+bool WantFused(const jxlhip_ctx* c, uint32_t kind, const jxlhip_output_format& fmt) {
   const DevFrame& f = c->f;
-  if (c->dc_only_on) return false;  // (the fused kernel decodes DCT8 cells from the coefficient stream and never sees the planes)
+  if (c->st.dc_only.on) return false;  // (the fused kernel decodes DCT8 cells from the coefficient stream and never sees the planes)
   // alone a context fuses from 12 Mpx; with several frames in flight on the device (jxlhip_set_concurrency_hint) the
   // step is bound by HBM traffic and the fused path, which moves less, pays from 6 Mpx (profiles/r04_path_choice.txt)
   const uint64_t min_px = c->concurrency > 1 ? (6ull << 20) : (12ull << 20);
   const bool big = (uint64_t)f.xsize * f.ysize >= min_px || (c->p.lf.gab == 0 && c->p.lf.epf_iters == 0);
   const bool has_dct8 = f.used_acs == 0 || (f.used_acs & 1u);
-  bool packed_fixed = false;
-  if (c->p.output_kind == JXLHIP_OUT_PACKED) {
-    const jxlhip_output_format& o = c->p.out_format;
-    packed_fixed = FastFixedFormat(o);
-  }
+  const bool packed_fixed = kind == JXLHIP_OUT_PACKED && FastFixedFormat(fmt);
   if (c->p.lf.epf_iters == 3) {
     // three EPF iterations: EPF0 marches from the fused producer's slab (k_fused_pc0), the rest as before; whole frames
     // only, and only with several frames in flight on the device (jxlhip_set_concurrency_hint): the producer / consumer
@@ -1201,7 +661,7 @@ bool WantFused(const jxlhip_ctx* c) {
            f.group_y0 == 0 && f.group_rows == f.ysg && FusedEpf0Supported(f, (int)c->p.lf.gab);
   }
   return (c->fuse > 0 || (c->fuse < 0 && big && has_dct8 && !packed_fixed)) && !c->generic_filters &&
-         FusedSupported(f, (int)c->p.lf.gab, (int)c->p.lf.epf_iters, (int)c->p.output_kind);
+         FusedSupported(f, (int)c->p.lf.gab, (int)c->p.lf.epf_iters, (int)kind);
 }
 
 int BeginDecode(jxlhip_ctx* c) {
@@ -1233,53 +693,24 @@ int BeginDecode(jxlhip_ctx* c) {
   return JXLHIP_OK;
 }
 
-// jxlhip_set_dc_only_groups, in front of phase 1: the coefficient slots of the masked groups are zeroed (the context's
-// upload buffer only: nothing was submitted into them, and phase 1 must not read what an earlier frame left), runs of
-// neighbouring groups with one memset each
-int ZeroDcOnlySlots(jxlhip_ctx* c) {
-  if (!c->dc_only_on || c->f.coeffs[0] != c->up_coeffs[0] || !c->up_coeffs[0]) return JXLHIP_OK;
-  const size_t ng = (size_t)c->f.xsg * c->f.ysg, slot = 3 * (size_t)JXLHIP_GROUP_COEFFS * c->up_esz;
-  if (c->up_groups != ng) return Fail(c, JXLHIP_ERR_STATE, "the upload buffers were laid out for another frame");
-  for (size_t g = 0; g < ng;) {
-    if (!c->dc_only_host[g]) {
-      g++;
-      continue;
-    }
-    size_t e = g;
-    while (e < ng && c->dc_only_host[e]) e++;
-    HIPCHK(c, hipMemsetAsync((char*)c->up_coeffs[0] + g * slot, 0, (e - g) * slot, c->stream));
-    g = e;
-  }
-  return JXLHIP_OK;
-}
-// ... and behind it: k_dc_upsample8 writes the masked groups' tiles of the planes
-int LaunchDcOnly(jxlhip_ctx* c) {
-  if (!c->dc_only_on) return JXLHIP_OK;
-  if (!LaunchDcUpsample8(c->f, c->dc_only_mask, c->dc_only_weights, c->stream))
-    return Fail(c, JXLHIP_ERR_UNSUPPORTED, "DC-only groups: a stripe, or planes beyond 32-bit indices");
-  ProfMark(c, JXLHIP_KERNEL_DC_UPSAMPLE);
-  HIPCHK(c, hipGetLastError());
-  return JXLHIP_OK;
-}
 
-// cols x rows: what the call writes -- the stripe at coded size, or an upsampled frame (OutCols / OutRows)
-int CheckOutArgs(jxlhip_ctx* c, void* out, size_t out_stride, size_t out_plane_stride, size_t cols, size_t rows) {
-  if (!out) return Fail(c, JXLHIP_ERR_INVALID_ARGUMENT, "null output");
-  if (c->p.output_kind == JXLHIP_OUT_LINEAR_RGB_F32) {
+}  // namespace
+
+int jxlhip::CheckOutArgs(jxlhip_ctx* c, const OutTarget& t, size_t cols, size_t rows) {
+  const size_t out_stride = t.fp.out_stride;
+  if (!t.fp.out) return Fail(c, JXLHIP_ERR_INVALID_ARGUMENT, "null output");
+  if (t.kind == JXLHIP_OUT_LINEAR_RGB_F32) {
     if (out_stride < cols * 12 || (out_stride & 3))
       return Fail(c, JXLHIP_ERR_INVALID_ARGUMENT, "RGB row stride %zu too small", out_stride);
-  } else if (c->p.output_kind == JXLHIP_OUT_PACKED) {
-    const size_t ssz = OutSampleBytes(c->p.out_format);
-    if (out_stride < cols * OutPixelBytes(c) || (out_stride % ssz) ||
-        ((uintptr_t)out % ssz))
+  } else if (t.kind == JXLHIP_OUT_PACKED) {
+    const size_t ssz = OutSampleBytes(t.fmt);
+    if (out_stride < cols * OutPixelBytes(t.kind, t.fmt) || (out_stride % ssz) || ((uintptr_t)t.fp.out % ssz))
       return Fail(c, JXLHIP_ERR_INVALID_ARGUMENT, "packed row stride %zu / alignment invalid", out_stride);
-  } else if (out_stride < cols || out_plane_stride < out_stride * (rows - 1) + cols) {
+  } else if (out_stride < cols || t.fp.out_plane_stride < out_stride * (rows - 1) + cols) {
     return Fail(c, JXLHIP_ERR_INVALID_ARGUMENT, "XYB strides too small");
   }
   return JXLHIP_OK;
 }
-
-}  // namespace
 
 int jxlhip::PrepareAhead(jxlhip_ctx* c, bool render_stages) {
   if (!c->prepare_once || c->capture_seen || !c->have_frame || !c->have_inputs || Capturing(c->stream)) return JXLHIP_OK;
@@ -1287,11 +718,9 @@ int jxlhip::PrepareAhead(jxlhip_ctx* c, bool render_stages) {
   // split calls (2 or 0).  A decode that wants another one -- the split calls on a whole frame, a render stage that
   // changes the output kind -- prepares again: correct, and one launch.
   const bool stripe = c->f.group_y0 != 0 || c->f.group_rows != c->f.ysg;
-  const uint32_t kind = c->p.output_kind;
-  if (render_stages || c->noise_on || c->splines_on || c->patches_on || c->ups_factor > 1 || c->tm_on)
-    c->p.output_kind = JXLHIP_OUT_XYB_PLANAR;  // as DecodeFrameFeatures / DecodeFrameToneMapped
-  const int fused = WantFused(c) ? (stripe ? 2 : 1) : 0;
-  c->p.output_kind = kind;
+  // (DecodeFrameFeatures and DecodeFrameToneMapped pass a planar target down)
+  const bool planar = render_stages || c->st.RenderStagesOn() || c->st.tone_map.on;
+  const int fused = WantFused(c, planar ? JXLHIP_OUT_XYB_PLANAR : c->p.output_kind, c->p.out_format) ? (stripe ? 2 : 1) : 0;
   int block;
   const int rc = EnqueuePrepare(c, fused, false, &block);
   c->prepared_ahead = rc == JXLHIP_OK && c->prepared;
@@ -1323,7 +752,7 @@ int jxlhip_decode_blocks(jxlhip_ctx* c) {
   // first / last block row ALSO reach the planes -- the halo rows the neighbours pull with jxlhip_halo_export.
   // A whole frame through the split calls stays two-phase (the taps read the planes).
   const bool stripe = c->f.group_y0 != 0 || c->f.group_rows != c->f.ysg;
-  c->blocks_fused = stripe && WantFused(c);
+  c->blocks_fused = stripe && WantFused(c, c->p.output_kind, c->p.out_format);
   if ((rc = ZeroDcOnlySlots(c))) return rc;
   rc = LaunchPhase1(c, c->blocks_fused ? 2 : 0);
   if (rc) return rc;
@@ -1379,22 +808,16 @@ int jxlhip_decode_filters_rows(jxlhip_ctx* c, void* out, size_t out_stride, size
   JXLHIP_NO_MULTI(c);
   if (!c->blocks_done) return Fail(c, JXLHIP_ERR_STATE, "decode_filters before decode_blocks");
   if (c->p.undo_orientation > 1) return Fail(c, JXLHIP_ERR_UNSUPPORTED, "undo_orientation with the split calls");
-  if (c->noise_on) return Fail(c, JXLHIP_ERR_UNSUPPORTED, "noise with the split calls (jxlhip_decode_frame takes it)");
-  if (c->splines_on)
-    return Fail(c, JXLHIP_ERR_UNSUPPORTED, "splines with the split calls (jxlhip_decode_frame takes them)");
-  if (c->patches_on)
-    return Fail(c, JXLHIP_ERR_UNSUPPORTED, "patches with the split calls (jxlhip_decode_frame takes them)");
-  if (c->ups_factor > 1)
-    return Fail(c, JXLHIP_ERR_UNSUPPORTED, "upsampling with the split calls (jxlhip_decode_frame takes it)");
-  if (c->blend_on) return Fail(c, JXLHIP_ERR_UNSUPPORTED, "blending with the split calls (jxlhip_decode_frame takes it)");
-  if (c->tm_on) return Fail(c, JXLHIP_ERR_UNSUPPORTED, "tone mapping with the split calls (jxlhip_decode_frame takes it)");
-  int rc = CheckOutArgs(c, out, out_stride, out_plane_stride, c->f.xsize, c->f.y1 - c->f.y0);
+  if (c->st.noise.on) return Fail(c, JXLHIP_ERR_UNSUPPORTED, "noise with the split calls (jxlhip_decode_frame takes it)");
+  if (c->st.splines.on) return Fail(c, JXLHIP_ERR_UNSUPPORTED, "splines with the split calls (jxlhip_decode_frame takes them)");
+  if (c->st.patches.on) return Fail(c, JXLHIP_ERR_UNSUPPORTED, "patches with the split calls (jxlhip_decode_frame takes them)");
+  if (c->st.ups.factor > 1) return Fail(c, JXLHIP_ERR_UNSUPPORTED, "upsampling with the split calls (jxlhip_decode_frame takes it)");
+  if (c->st.blend.on) return Fail(c, JXLHIP_ERR_UNSUPPORTED, "blending with the split calls (jxlhip_decode_frame takes it)");
+  if (c->st.tone_map.on) return Fail(c, JXLHIP_ERR_UNSUPPORTED, "tone mapping with the split calls (jxlhip_decode_frame takes it)");
+  const OutTarget t = MakeTarget(c, out, out_stride, out_plane_stride);
+  int rc = CheckOutArgs(c, t, c->f.xsize, c->f.y1 - c->f.y0);
   if (rc) return rc;
   HIPCHK(c, hipSetDevice(c->device));
-  FilterParams fp = c->fp;
-  fp.out = out;
-  fp.out_stride = out_stride;
-  fp.out_plane_stride = out_plane_stride;
   const bool whole = y_begin == c->f.y0 && y_end == c->f.y1;
   if (!whole) {
     if (y_begin == y_end && y_begin >= c->f.y0 && y_end <= c->f.y1) return JXLHIP_OK;  // (an edge stripe has no boundary rows on its outer side)
@@ -1404,7 +827,7 @@ int jxlhip_decode_filters_rows(jxlhip_ctx* c, void* out, size_t out_stride, size
                   y_end, c->f.y0, c->f.y1);
     if (c->p.lf.epf_iters == 3) return Fail(c, JXLHIP_ERR_UNSUPPORTED, "row ranges with epf_iters = 3 (two marches over a second plane set)");
   }
-  return LaunchFiltersRows(c, fp, y_begin, y_end, c->blocks_fused);
+  return LaunchFiltersRows(c, t, y_begin, y_end, c->blocks_fused);
 }
 
 // ---- one stripe step in three calls (round 5) ----------------------------------------------------
@@ -1436,19 +859,13 @@ int jxlhip_stripe_finish(jxlhip_ctx* c, const float* recv_up, const float* recv_
 }
 
 // Both phases, each over the whole stripe.
-static int DecodeFrameCoded(jxlhip_ctx* c, void* out, size_t out_stride, size_t out_plane_stride);
-static int DecodeFrameFeatures(jxlhip_ctx* c, void* out, size_t out_stride, size_t out_plane_stride);
-static int DecodeFrameBlended(jxlhip_ctx* c, void* out, size_t out_stride);
-static int DecodeFrameToneMapped(jxlhip_ctx* c, void* out, size_t out_stride);
-
 int jxlhip_decode_frame(jxlhip_ctx* c, void* out, size_t out_stride, size_t out_plane_stride) {
   if (!c) return JXLHIP_ERR_INVALID_ARGUMENT;
   if (c->multi) return out ? MultiDecodeFrame(c, out, nullptr, out_stride, out_plane_stride) : JXLHIP_ERR_INVALID_ARGUMENT;
   if (!c->have_frame) return Fail(c, JXLHIP_ERR_STATE, "decode needs frame_begin + inputs");
-  if (c->tm_on) return DecodeFrameToneMapped(c, out, out_stride);
-  if (c->blend_on) return DecodeFrameBlended(c, out, out_stride);
-  if (c->noise_on || c->splines_on || c->patches_on || c->ups_factor > 1) return DecodeFrameFeatures(c, out, out_stride, out_plane_stride);
-  if (c->p.undo_orientation <= 1) return DecodeFrameCoded(c, out, out_stride, out_plane_stride);
+  if (c->st.tone_map.on) return DecodeFrameToneMapped(c, out, out_stride);
+  if (c->st.blend.on) return DecodeFrameBlended(c, out, out_stride);
+  if (c->p.undo_orientation <= 1 || c->st.RenderStagesOn()) return DecodeFrameOwnPath(c, MakeTarget(c, out, out_stride, out_plane_stride));
   // undo_orientation: coded orientation into a staging frame, k_orient into the caller's buffer
   const DevFrame& f = c->f;
   const size_t bpp = OutPixelBytes(c);
@@ -1461,412 +878,43 @@ int jxlhip_decode_frame(jxlhip_ctx* c, void* out, size_t out_stride, size_t out_
   const size_t row = ((size_t)f.xsize * bpp + 255) & ~(size_t)255;
   int rc;
   if ((rc = c->orient_dev.Reserve(c, (size_t)f.ysize * row))) return rc;
-  if ((rc = DecodeFrameCoded(c, c->orient_dev, row, 0))) return rc;
+  if ((rc = DecodeFrameCoded(c, MakeTarget(c, c->orient_dev, row, 0)))) return rc;
   if (!LaunchOrient(c->orient_dev, row, f.xsize, f.ysize, (uint32_t)bpp, c->p.undo_orientation, out, out_stride, c->stream))
     return Fail(c, JXLHIP_ERR_UNSUPPORTED, "undo_orientation %u with %zu-byte pixels", c->p.undo_orientation, bpp);
   HIPCHK(c, hipGetLastError());
   return JXLHIP_OK;
 }
 
-static int DecodeFrameCoded(jxlhip_ctx* c, void* out, size_t out_stride, size_t out_plane_stride) {
+int jxlhip::DecodeFrameCoded(jxlhip_ctx* c, const OutTarget& t) {
   const DevFrame& f = c->f;
   c->blocks_fused = false;
   int rc = BeginDecode(c);
   if (rc) return rc;
-  rc = CheckOutArgs(c, out, out_stride, out_plane_stride, f.xsize, f.y1 - f.y0);  // (always at coded size here)
+  rc = CheckOutArgs(c, t, f.xsize, f.y1 - f.y0);  // (always at coded size here)
   if (rc) return rc;
-  FilterParams fp = c->fp;
-  fp.out = out;
-  fp.out_stride = out_stride;
-  fp.out_plane_stride = out_plane_stride;
   // A frame of DCT32X32 varblocks only, no loop filter, linear float RGB out (BASELINE configs[4]): the matrix-core
   // class kernel applies the opsin inverse and writes the pixels itself (kernels_mfma.hip, EMIT) -- no XYB planes,
   // no second kernel.  used_acs is the caller's promise; k_prepare reports any other strategy it meets.
   if (c->mfma != 0 && f.used_acs == (1u << 5) && c->p.lf.gab == 0 && c->p.lf.epf_iters == 0 &&
-      c->p.output_kind == JXLHIP_OUT_LINEAR_RGB_F32 && !c->generic_filters && !c->dc_only_on) {
-    rc = LaunchPhase1(c, 0, &fp);
+      t.kind == JXLHIP_OUT_LINEAR_RGB_F32 && !c->generic_filters && !c->st.dc_only.on) {
+    rc = LaunchPhase1(c, 0, &t.fp);
     c->blocks_done = false;  // nothing in the planes
     return rc;
   }
-  // Whole frame on this context: the fused kernel decodes the DCT8 blocks inside the filter
-  // march (kernels_fused.hip).  The split calls (jxlhip_decode_blocks / _filters) stay two-phase: a
-  // stripe's halo rows must exist in the planes for its neighbours.
-  // auto: with a filter, frames of 12 Mpx and more (see jxlhip_ctx::fuse); without one the fused wave has no
-  // halo rows to pay for and wins at 4K as well (95.8 vs 83.4 Gpx/s); never when the caller's used_acs says the
-  // frame has no DCT8 block -- then the slab is only a detour (configs[4]: 76.1 vs 79.6 Gpx/s)
-  if (WantFused(c) && f.group_y0 == 0 && f.group_rows == f.ysg) {
+  // Whole frame on this context: the fused kernel decodes the DCT8 blocks inside the filter march (kernels_fused.hip;
+  // WantFused says when).  The split calls (jxlhip_decode_blocks / _filters) stay two-phase: a stripe's halo rows must
+  // exist in the planes for its neighbours.
+  if (WantFused(c, t.kind, t.fmt) && f.group_y0 == 0 && f.group_rows == f.ysg) {
     if ((rc = LaunchPhase1(c, 1))) return rc;
     c->blocks_done = false;  // the planes do not hold the whole frame
-    return LaunchFiltersRows(c, fp, f.y0, f.y1, true);
+    return LaunchFiltersRows(c, t, f.y0, f.y1, true);
   }
   // (a frame with DC-only groups always comes here: WantFused; k_dc_upsample8 between phase 1 and the filters)
   if ((rc = ZeroDcOnlySlots(c))) return rc;
   if ((rc = LaunchPhase1(c))) return rc;
   if ((rc = LaunchDcOnly(c))) return rc;
   c->blocks_done = true;
-  return LaunchFiltersRows(c, fp, f.y0, f.y1);
-}
-
-// A frame with splines, upsampling and / or photon noise (jxlhip_set_splines, jxlhip_set_upsampling, jxlhip_set_noise;
-// whole frames, coded orientation): the frame's own path -- fused or two-phase, whatever DecodeFrameCoded picks for it --
-// writes the filtered frame as planar XYB into context memory; the render stages the reference's pipeline has between
-// the loop filters and the XYB stage follow in its order (dec_cache.cc:194-218): splines at coded size, upsampling,
-// noise at output size, and the last launch writes the caller's output:
-//   splines only  k_splines draws every tile and emits;
-//   noise only    k_noise_rng + k_noise_emit (kernels_noise.hip);
-//   upsampling    k_upsample emits; with noise it writes planar XYB at output size and the noise launches emit;
-//   splines in front of either: k_splines draws the tiles with segments back into the planes.
-// Noise behind upsampling is the noise of a frame of the output size: PrepareNoiseInput seeds one generator per
-// group_dim tile in OUTPUT coordinates and fills it clipped to the image (dec_noise.cc:120-151).
-static int DecodeFrameFeatures(jxlhip_ctx* c, void* out, size_t out_stride, size_t out_plane_stride) {
-  const bool ups = c->ups_factor > 1;
-  int rc = CheckOutArgs(c, out, out_stride, out_plane_stride, OutCols(c), OutRows(c));
-  if (rc) return rc;
-  const DevFrame& f = c->f;
-  if (f.group_y0 != 0 || f.group_rows != f.ysg || c->p.undo_orientation > 1)
-    return Fail(c, JXLHIP_ERR_UNSUPPORTED, "noise / splines / upsampling need a whole frame in coded orientation");
-  if (c->patches_on && c->pat_ref_serial != c->ref_serial)  // (in front of every launch of the frame)
-    return Fail(c, JXLHIP_ERR_STATE, "set_reference_frame after set_patches (the uploaded dictionary points into the slots)");
-  HIPCHK(c, hipSetDevice(c->device));
-  // the filtered frame at coded size (cns x f.ysize per plane), and the frame the noise launches work on (W x H)
-  const uint32_t cns = (f.xsize + 63u) & ~63u;
-  const size_t cplane = (size_t)cns * f.ysize;
-  const uint32_t W = (uint32_t)OutCols(c), H = (uint32_t)OutRows(c);
-  const uint32_t ns = (W + 63u) & ~63u;
-  const size_t nplane = (size_t)ns * H;
-  if (ups && (rc = c->ups_planes.Reserve(c, 3 * cplane))) return rc;
-  if ((!ups || c->noise_on) && (rc = c->noise_buf.Reserve(c, (c->noise_on ? 6 : 3) * nplane))) return rc;
-  float* coded = ups ? c->ups_planes : c->noise_buf;
-  const uint32_t kind = c->p.output_kind;
-  c->p.output_kind = JXLHIP_OUT_XYB_PLANAR;
-  rc = DecodeFrameCoded(c, coded, cns, cplane);
-  c->p.output_kind = kind;
-  if (rc) return rc;
-  FilterParams fp = c->fp;
-  fp.out = out;
-  fp.out_stride = out_stride;
-  fp.out_plane_stride = out_plane_stride;
-  ProfBegin(c);
-  if (c->patches_on) {
-    PatchArgs A{};
-    A.xsize = f.xsize;
-    A.ysize = f.ysize;
-    A.tiles_x = c->pat_tiles_x;
-    A.num_active = c->pat_num_active;
-    A.xyb = coded;
-    A.xyb_out = coded;
-    A.ns = cns;
-    A.nplane = cplane;
-    A.recs = c->pat_recs;
-    A.tile_start = c->pat_tiles;
-    A.tile_idx = c->pat_tiles + c->pat_num_tiles + 1;
-    A.active = c->pat_tiles + c->pat_num_tiles + 1 + c->pat_entries;
-    if (!LaunchPatches(A, fp, (int)kind, /*in_place=*/c->splines_on || c->noise_on || ups, c->stream))
-      return Fail(c, JXLHIP_ERR_INVALID_ARGUMENT, "patches output kind %u", kind);
-    ProfMark(c, JXLHIP_KERNEL_PATCHES);
-  }
-  if (c->splines_on) {
-    SplineArgs S{};
-    S.xsize = f.xsize;
-    S.ysize = f.ysize;
-    S.tiles_x = c->spl_tiles_x;
-    S.num_active = c->spl_num_active;
-    S.xyb = coded;
-    S.xyb_out = coded;
-    S.ns = cns;
-    S.nplane = cplane;
-    S.segs = c->spl_segs;
-    S.tile_start = c->spl_tiles;
-    S.tile_idx = c->spl_tiles + c->spl_num_tiles + 1;
-    S.active = c->spl_tiles + c->spl_num_tiles + 1 + c->spl_entries;
-    if (!LaunchSplines(S, fp, (int)kind, /*in_place=*/c->noise_on || ups, c->stream))
-      return Fail(c, JXLHIP_ERR_INVALID_ARGUMENT, "splines output kind %u", kind);
-    ProfMark(c, JXLHIP_KERNEL_SPLINES);
-  }
-  if (ups) {
-    UpsampleArgs U{};
-    U.cw = f.xsize;
-    U.ch = f.ysize;
-    U.xsize = W;
-    U.ysize = H;
-    U.n = c->ups_factor;
-    U.xyb = coded;
-    U.ns = cns;
-    U.nplane = cplane;
-    U.weights = c->ups_weights;
-    if (!LaunchUpsample(U, fp, (int)kind, c->noise_on ? (float*)c->noise_buf : nullptr, ns, nplane, c->stream))
-      return Fail(c, JXLHIP_ERR_INVALID_ARGUMENT, "upsampling output kind %u", kind);
-    ProfMark(c, JXLHIP_KERNEL_UPSAMPLE);
-  }
-  if (c->noise_on) {
-    NoiseArgs N{};
-    N.xsize = W;
-    N.ysize = H;
-    N.xsg = (W + 255u) / 256u;
-    N.ysg = (H + 255u) / 256u;
-    N.visible = c->noise_visible;
-    N.nonvisible = c->noise_nonvisible;
-    memcpy(N.lut, c->noise_lut, sizeof(N.lut));
-    N.ytox = c->p.cfl_base_x;  // ColorCorrelation::YtoXRatio(0) / YtoBRatio(0) (chroma_from_luma.h:51-57)
-    N.ytob = c->p.cfl_base_b;
-    N.xyb = c->noise_buf;
-    N.rnd = c->noise_buf + 3 * nplane;
-    N.ns = ns;
-    N.nplane = nplane;
-    N.jump = c->noise_jump;
-    if (!LaunchNoise(N, fp, (int)kind, c->stream)) return Fail(c, JXLHIP_ERR_INVALID_ARGUMENT, "noise output kind %u", kind);
-    ProfMark(c, JXLHIP_KERNEL_NOISE);
-  }
-  HIPCHK(c, hipGetLastError());
-  return JXLHIP_OK;
-}
-
-// A blended frame (jxlhip_set_blending): the frame's whole path -- DecodeFrameCoded or DecodeFrameFeatures, whatever it
-// would take without blending -- writes packed float RGB in the caller's transfer function into blend_stage, and
-// k_blend (kernels_blend.hip) blends that over the source canvas into the save slot and / or the caller's buffer,
-// which is image-sized.  The canvas never leaves the device.  With jxlhip_set_blending_extra the launch is k_ec_blend
-// (kernels_blend_ec.hip), which blends and saves the image's extra channels beside the colour.
-static int DecodeFrameBlended(jxlhip_ctx* c, void* out, size_t out_stride) {
-  const jxlhip_blend_params& b = c->blend;
-  const DevFrame& f = c->f;
-  // (set_blending has checked these; set_alpha, set_upsampling .. may have been called since)
-  if (f.group_y0 != 0 || f.group_rows != f.ysg || c->p.undo_orientation > 1 || c->p.output_kind == JXLHIP_OUT_XYB_PLANAR)
-    return Fail(c, JXLHIP_ERR_UNSUPPORTED, "blending needs a whole frame in coded orientation and an interleaved output");
-  if (c->fp.alpha) return Fail(c, JXLHIP_ERR_UNSUPPORTED, "blending on a frame with alpha");
-  const bool ec = c->blend_ec_on;
-  const jxlhip_blend_extra_params& e = c->blend_ec;
-  const uint32_t nec = ec ? e.num_extra_channels : 0;
-  if (ec && (c->ups_factor > 1 || c->patches_on))
-    return Fail(c, JXLHIP_ERR_UNSUPPORTED, "extra channels of an upsampled frame or of a frame with patches");
-  const uint32_t W = b.image_xsize, H = b.image_ysize;
-  const bool save = b.save_slot != JXLHIP_BLEND_NO_SAVE;
-  if (!out && !save) return Fail(c, JXLHIP_ERR_INVALID_ARGUMENT, "null output and no save slot");
-  int rc;
-  if (out && (rc = CheckOutArgs(c, out, out_stride, 0, W, H))) return rc;
-  if (Capturing(c->stream))  // (canvas and staging memory may have to grow: a synchronise and an allocation)
-    return Fail(c, JXLHIP_ERR_UNSUPPORTED, "blending while the stream is being captured");
-  const int64_t fw = (int64_t)OutCols(c), fh = (int64_t)OutRows(c);
-  const uint32_t op = b.mode == JXLHIP_BLEND_MUL ? (b.clamp ? kPatchOpMulClamp : kPatchOpMul)
-                      : (b.mode == JXLHIP_BLEND_ADD || b.mode == JXLHIP_BLEND_ALPHA_WEIGHTED_ADD) ? kPatchOpAdd
-                                                                                                 : kPatchOpReplace;
-  const bool full = b.x0 == 0 && b.y0 == 0 && fw == W && fh == H;
-  // a full frame that replaces never reads its source: whatever the slot holds is no concern of this frame.  (With
-  // extra channels "replaces" means the colour AND every channel: a full frame whose colour replaces while a channel
-  // blends has the colour's slot checked too although the colour does not read it, as BlendingStage's constructor does.)
-  const bool bg_dead = ec ? EcSourcesDead(c, e) : full && op == kPatchOpReplace;
-  if (!bg_dead && c->ref_w[b.source] != 0)
-    return Fail(c, JXLHIP_ERR_INVALID_ARGUMENT, "blend source slot %u holds an XYB reference frame", b.source);
-  const bool have_src = !bg_dead && c->canvas_w[b.source] != 0;
-  if (have_src && (c->canvas_w[b.source] < W || c->canvas_h[b.source] < H))
-    return Fail(c, JXLHIP_ERR_INVALID_ARGUMENT, "the %ux%u canvas of slot %u is smaller than the %ux%u image",
-                c->canvas_w[b.source], c->canvas_h[b.source], b.source, W, H);
-  const bool in_place = save && have_src && b.save_slot == b.source;
-  if (in_place && (c->canvas_w[b.source] != W || c->canvas_h[b.source] != H))
-    return Fail(c, JXLHIP_ERR_INVALID_ARGUMENT, "save_slot == source with a %ux%u canvas and a %ux%u image",
-                c->canvas_w[b.source], c->canvas_h[b.source], W, H);
-  // the extra channels: each from the plane of its own source slot (zeroes when the slot has none); a slot that is
-  // saved into while one of its planes is read must already have the layout it is given
-  bool ec_src[4] = {false, false, false, false};
-  bool ec_in_place = true;
-  if (ec) {
-    if ((rc = CheckEcSources(c, e))) return rc;
-    for (uint32_t i = 0; i < nec; i++) {
-      const uint32_t s = e.channel[i].source;
-      ec_src[i] = !bg_dead && c->canvas_w[s] != 0 && i < c->canvas_nec[s];
-      ec_in_place = ec_in_place && ec_src[i] && save && s == b.save_slot;
-      if (save && ec_src[i] && s == b.save_slot && (c->canvas_w[s] != W || c->canvas_h[s] != H || c->canvas_nec[s] != nec))
-        return Fail(c, JXLHIP_ERR_INVALID_ARGUMENT,
-                    "save_slot == source of extra channel %u with a %ux%u canvas of %u extra channels and a %ux%u image of %u", i,
-                    c->canvas_w[s], c->canvas_h[s], c->canvas_nec[s], W, H, nec);
-    }
-  }
-  const bool in_place_all = in_place && ec_in_place;  // (without extra channels: in_place)
-  // a full frame that replaces and is not saved: today's path and launches, nothing else
-  if (!ec && full && op == kPatchOpReplace && !save) {
-    return c->noise_on || c->splines_on || c->patches_on || c->ups_factor > 1 ? DecodeFrameFeatures(c, out, out_stride, 0)
-                                                                             : DecodeFrameCoded(c, out, out_stride, 0);
-  }
-  HIPCHK(c, hipSetDevice(c->device));
-  BlendArgs A{};
-  A.W = W;
-  A.H = H;
-  A.rx0 = (int32_t)std::max<int64_t>(b.x0, 0);
-  A.ry0 = (int32_t)std::max<int64_t>(b.y0, 0);
-  A.rx1 = (int32_t)std::min<int64_t>((int64_t)b.x0 + fw, W);
-  A.ry1 = (int32_t)std::min<int64_t>((int64_t)b.y0 + fh, H);
-  const bool empty = A.rx1 <= A.rx0 || A.ry1 <= A.ry0;
-  if (empty) A.rx0 = A.rx1 = A.ry0 = A.ry1 = 0;
-  A.op = op;
-  // the frame itself, staged: (x0 mod 4) pixels into rows padded to four pixels (see kernels_blend.hip).  A frame that
-  // lies wholly outside the image is still decoded: its stream errors must surface as they do without blending.
-  const int32_t xa = b.x0 & ~3;  // (rounds down, also below zero)
-  const size_t lead = (size_t)(b.x0 - xa);
-  const size_t stage_stride = CanvasStride((uint32_t)(lead + (size_t)fw));
-  if ((rc = c->blend_stage.Reserve(c, (size_t)fh * stage_stride))) return rc;
-  {
-    const jxlhip_frame_params keep_p = c->p;
-    const FilterParams keep_fp = c->fp;
-    if (c->p.output_kind == JXLHIP_OUT_PACKED) {  // float RGB in the caller's transfer function: no dither, no alpha
-      jxlhip_output_format& o = c->p.out_format;
-      o.sample_type = JXLHIP_SAMPLE_F32;
-      o.num_channels = 3;
-      o.swap_endianness = 0;
-      c->fp.fmt = o;
-      c->fp.sample_mul = 1.0f;
-    }
-    float* stage_out = c->blend_stage + 3 * lead;
-    rc = c->noise_on || c->splines_on || c->patches_on || c->ups_factor > 1
-             ? DecodeFrameFeatures(c, stage_out, stage_stride * sizeof(float), 0)
-             : DecodeFrameCoded(c, stage_out, stage_stride * sizeof(float), 0);
-    c->p = keep_p;
-    c->fp = keep_fp;
-    if (rc) return rc;
-  }
-  A.fg = c->blend_stage;
-  A.fg_xa = xa;
-  A.fg_y0 = b.y0;
-  A.fg_stride = stage_stride;
-  if (have_src) {
-    A.src = c->canvas[b.source];
-    A.src_stride = CanvasStride(c->canvas_w[b.source]);
-  }
-  if (save) {
-    const uint32_t s = b.save_slot;
-    if (!in_place) {
-      const size_t need = (size_t)H * CanvasStride(W);
-      if (need > c->canvas[s].n) HIPCHK(c, hipStreamSynchronize(c->stream));  // an earlier launch may still read the slot
-      if ((rc = c->canvas[s].Reserve(c, need))) return rc;
-    }
-    A.dst = c->canvas[s];
-    A.dst_stride = CanvasStride(W);
-  }
-  A.dst_all = in_place_all ? 0u : 1u;
-  // the caller's buffer or another slot is written everywhere; a frame blended into its own source slot -- the source of
-  // its colour and of every extra channel -- only under its rectangle
-  if (out || !in_place_all) {
-    A.gx0 = 0;
-    A.gx1 = (W + 3) / 4;
-    A.y0 = 0;
-    A.y1 = H;
-  } else {
-    A.gx0 = (uint32_t)A.rx0 / 4;
-    A.gx1 = ((uint32_t)A.rx1 + 3) / 4;
-    A.y0 = (uint32_t)A.ry0;
-    A.y1 = (uint32_t)A.ry1;
-  }
-  FilterParams fp = c->fp;
-  fp.fmt.transfer = JXLHIP_TF_LINEAR;  // the samples are encoded already: neither the HLG OOTF nor the curve runs twice
-  fp.out = out;
-  fp.out_stride = out_stride;
-  fp.out_plane_stride = 0;
-  BlendEcArgs E{};
-  if (ec) {
-    const size_t es = EcStride(W), plane = (size_t)H * es;
-    // where the blended planes go: the save slot's, or the frame's own
-    DevBuf<float>& planes = save ? c->canvas_ec[b.save_slot] : c->frame_ec;
-    if ((size_t)nec * plane > planes.n) HIPCHK(c, hipStreamSynchronize(c->stream));  // an earlier launch may still read them
-    if ((rc = planes.Reserve(c, (size_t)nec * plane))) return rc;
-    E.num_ec = nec;
-    E.has_alpha = EcHasAlpha(e) ? 1u : 0u;
-    E.color_mode = b.mode;
-    E.color_clamp = b.clamp;
-    E.color_alpha = e.color_alpha_channel;
-    E.out_alpha = -1;
-    E.fg_stride = c->blend_ec_stage_stride;
-    E.dst_stride = es;
-    for (uint32_t i = 0; i < nec; i++) {
-      const jxlhip_blend_extra_channel& ch = e.channel[i];
-      E.mode[i] = ch.mode;
-      E.clamp[i] = ch.clamp;
-      E.alpha[i] = ch.alpha_channel;
-      E.premul[i] = ch.alpha_associated ? 1u : 0u;
-      if (ch.is_alpha && E.out_alpha < 0) E.out_alpha = (int32_t)i;
-      E.fg[i] = c->blend_ec_stage + (size_t)i * (size_t)fh * E.fg_stride;
-      if (ec_src[i]) {
-        const uint32_t s = ch.source;
-        E.src_stride[i] = EcStride(c->canvas_w[s]);
-        E.src[i] = c->canvas_ec[s] + (size_t)i * c->canvas_h[s] * E.src_stride[i];
-      }
-      E.dst[i] = planes + (size_t)i * plane;
-    }
-    if (E.out_alpha >= 0) {  // the fourth sample of a packed output: read back from the blended plane
-      fp.alpha = E.dst[E.out_alpha];
-      fp.alpha_stride = (uint32_t)es;
-    }
-    c->frame_ec_planes = planes;
-    c->frame_ec_n = nec;
-    c->frame_ec_w = W;
-    c->frame_ec_h = H;
-  }
-  // (a layer wholly outside the image that is blended into its own source slot visits nothing: no launch, no span)
-  if (A.gx1 > A.gx0 && A.y1 > A.y0) {
-    ProfBegin(c);
-    if (ec) {
-      E.B = A;
-      if (!LaunchBlendEc(E, fp, out ? (int)c->p.output_kind : 0, c->stream))
-        return Fail(c, JXLHIP_ERR_INVALID_ARGUMENT, "blend launch arguments");
-      ProfMark(c, JXLHIP_KERNEL_BLEND_EC);
-    } else {
-      if (!LaunchBlend(A, fp, out ? (int)c->p.output_kind : 0, c->stream))
-        return Fail(c, JXLHIP_ERR_INVALID_ARGUMENT, "blend launch arguments");
-      ProfMark(c, JXLHIP_KERNEL_BLEND);
-    }
-    HIPCHK(c, hipGetLastError());
-  }
-  if (save) {
-    const uint32_t s = b.save_slot;
-    c->canvas_w[s] = W;
-    c->canvas_h[s] = H;
-    c->canvas_nec[s] = nec;
-    if (c->ref_w[s] != 0) {  // (a slot holds one kind: the canvas drops the XYB frame, and a dictionary that points into it)
-      c->ref_w[s] = c->ref_h[s] = 0;
-      c->ref_serial++;
-    }
-  }
-  return JXLHIP_OK;
-}
-
-// A tone-mapped frame (jxlhip_set_tone_mapping): the frame's whole path -- DecodeFrameCoded or DecodeFrameFeatures,
-// whatever it would take without tone mapping -- writes planar XYB at output size into tm_planes, and k_tone_map
-// (kernels_tonemap.hip) writes the caller's output from that.
-static int DecodeFrameToneMapped(jxlhip_ctx* c, void* out, size_t out_stride) {
-  const DevFrame& f = c->f;
-  // (set_tone_mapping has checked these; set_blending refuses a tone-mapped frame)
-  if (f.group_y0 != 0 || f.group_rows != f.ysg || c->p.undo_orientation > 1 || c->p.output_kind == JXLHIP_OUT_XYB_PLANAR || c->blend_on)
-    return Fail(c, JXLHIP_ERR_UNSUPPORTED, "tone mapping needs a whole unblended frame in coded orientation and an interleaved output");
-  const uint32_t W = (uint32_t)OutCols(c), H = (uint32_t)OutRows(c);
-  int rc = CheckOutArgs(c, out, out_stride, 0, W, H);
-  if (rc) return rc;
-  HIPCHK(c, hipSetDevice(c->device));
-  const uint32_t ns = (W + 63u) & ~63u;
-  const size_t nplane = (size_t)ns * H;
-  if (3 * nplane > 0xFFFFFFFFull)
-    return Fail(c, JXLHIP_ERR_UNSUPPORTED, "tone mapping of a frame whose three planes exceed 2^32 samples (k_tone_map indexes with 32 bits)");
-  if (3 * nplane > c->tm_planes.n && Capturing(c->stream))  // (a synchronise and an allocation)
-    return Fail(c, JXLHIP_ERR_UNSUPPORTED, "tone mapping while the stream is being captured and its planes have to grow");
-  if ((rc = c->tm_planes.Reserve(c, 3 * nplane))) return rc;
-  const uint32_t kind = c->p.output_kind;
-  c->p.output_kind = JXLHIP_OUT_XYB_PLANAR;
-  rc = c->noise_on || c->splines_on || c->patches_on || c->ups_factor > 1 ? DecodeFrameFeatures(c, c->tm_planes, ns, nplane)
-                                                                         : DecodeFrameCoded(c, c->tm_planes, ns, nplane);
-  c->p.output_kind = kind;
-  if (rc) return rc;
-  ToneMapArgs A{};
-  A.xsize = W;
-  A.ysize = H;
-  A.xyb = c->tm_planes;
-  A.ns = ns;
-  A.nplane = (uint32_t)nplane;
-  A.k = c->tm_k;
-  FilterParams fp = c->fp;
-  fp.out = out;
-  fp.out_stride = out_stride;
-  fp.out_plane_stride = 0;
-  ProfBegin(c);
-  if (!LaunchToneMap(A, fp, (int)kind, c->stream)) return Fail(c, JXLHIP_ERR_INVALID_ARGUMENT, "tone map launch arguments");
-  ProfMark(c, JXLHIP_KERNEL_TONE_MAP);
-  HIPCHK(c, hipGetLastError());
-  return JXLHIP_OK;
+  return LaunchFiltersRows(c, t, f.y0, f.y1);
 }
 
 // The boundary handing over a HOST buffer (what JxlDecoderSetImageOutBuffer gives libjxl): both phases
@@ -1905,8 +953,9 @@ int jxlhip_decode_frame_pinned(jxlhip_ctx* c, const void** host_frame, size_t* s
   const jxlhip_frame_params& p = c->p;
   if (p.output_kind == JXLHIP_OUT_XYB_PLANAR) return Fail(c, JXLHIP_ERR_UNSUPPORTED, "pinned frames are interleaved outputs");
   const bool transposed = p.undo_orientation >= 5;
-  const size_t rows = transposed ? p.xsize : (c->blend_on ? c->blend.image_ysize : c->ups_factor > 1 ? c->ups_ysize : p.ysize);
-  const size_t cols = transposed ? p.ysize : (c->blend_on ? c->blend.image_xsize : c->ups_factor > 1 ? c->ups_xsize : p.xsize);
+  // (a multi-device parent's c->f is its first child's stripe: the whole frame there, and no stage is ever on)
+  const size_t rows = transposed ? p.xsize : c->multi ? p.ysize : BufRows(c);
+  const size_t cols = transposed ? p.ysize : BufCols(c);
   const size_t row_bytes = cols * OutPixelBytes(c);
   const size_t pitch = (row_bytes + 63) & ~(size_t)63;
   if (rows * pitch > c->pinned_frame.bytes) {

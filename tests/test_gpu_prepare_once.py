@@ -396,3 +396,37 @@ def test_whole_file_prepares_once_per_file(dq, oracle, monkeypatch):
         assert float(np.abs(out.cpu().numpy() - rs.rgb).max()) / scale <= tc.TIGHT
         assert d.prepare_launches() == (n, 0)  # launched behind the side info, taken up by the frame's one decode
     d.close()
+
+
+# (launched, reused) of jxlhip_debug_prepare_launches after one hand-over and two decodes of a staged frame.  Taken from
+# the commit before the render stages moved into render_stages.hip, on the same machine: the explicit output target
+# must route every staged decode, and PrepareAhead's guess for it, exactly as the temporary rewrite of c->p did.
+STAGED_PAIRS = {"plain": (1, 1), "noise": (1, 1), "tone-mapped": (1, 1), "blended": (1, 1), "blended-srgb8-rgba": (1, 1)}
+
+
+@pytest.mark.parametrize("stage", sorted(STAGED_PAIRS))
+def test_staged_frames_prepare_as_before(dq, stage, monkeypatch):
+    """A one-group frame without Gaborish or EPF (the automatic rule fuses it at any size), handed over once through
+    jxlhip_upload_side_info (which prepares ahead, in the mode PrepareAhead assumes for the stage) and decoded twice."""
+    from output_sweep import fmt
+    monkeypatch.delenv("JXLHIP_FUSE", raising=False)
+    monkeypatch.delenv("JXLHIP_PREPARE_ONCE", raising=False)
+    rgba8 = stage == "blended-srgb8-rgba"
+    params, t = synth.synth_frame(200, 56, mix=synth.MIX_D1, gab=False, epf_iters=0, seed=46, output_kind=2 if rgba8 else 1,
+                                  out_format=fmt(abi.TF_SRGB, abi.SAMPLE_U8, 4) if rgba8 else None)
+    d = VarDctDecoder(0)
+    d.begin_frame(params)
+    if stage == "noise":
+        d.set_noise([0.02, 0.03, 0.05, 0.05, 0.04, 0.03, 0.02, 0.02])
+    elif stage == "tone-mapped":
+        d.set_tone_mapping(1000.0, 100.0)
+    elif stage.startswith("blended"):  # over an empty slot, off the origin, into a larger image: k_blend runs
+        d.set_blending((208, 60), (3, 2), abi.BLEND_ADD)
+    upload(d, params, t, dq)
+    outs = [d.decode_frame().clone() for _ in range(2)]
+    d.sync()
+    pair = d.prepare_launches()
+    print("prepare launches", stage, pair)
+    assert torch.equal(outs[0], outs[1])
+    assert pair == STAGED_PAIRS[stage]
+    d.close()
