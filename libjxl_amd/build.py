@@ -18,7 +18,7 @@ FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=o
 LIB_SOURCES = ["kernels_fused.hip", "kernels_filters_fast_general.hip", "kernels_filters_fast_general_epf2.hip",
                "kernels_filters_fast_fp.hip", "kernels_filters_fast_be16.hip", "kernels_filters_fast_int.hip",
                "kernels_blocks.hip", "kernels_filters_fast.hip", "kernels_fused_epf0.hip", "entropy.cc", "context.hip",
-               "render_stages.hip", "handover.hip", "codestream.hip", "multi.hip",
+               "render_stages.hip", "handover.hip", "codestream.hip", "frame_decode.hip", "multi.hip",
                "kernels_filters.hip", "kernels_mfma.hip", "kernels_epf0.hip", "kernels_tables.hip", "kernels_noise.hip",
                "kernels_splines.hip", "kernels_upsample.hip", "kernels_patches.hip", "kernels_blend.hip", "kernels_blend_ec.hip",
                "kernels_tonemap.hip", "kernels_dc_upsample.hip"]

@@ -143,7 +143,7 @@ def test_decode_codestream_matches_the_reference_decoder(L, ref, kw, workers):
 ])
 def test_one_runner_call_equals_three_barriers(L, ref, kw, monkeypatch):
     """With a runner the DC groups, AC global and the AC groups are ONE pool of work units in one runner call, the AC
-    groups under a DC group starting when its block info is in (codestream.hip: PipelineJob); JXLHIP_NO_PIPELINE=1 runs
+    groups under a DC group starting when its block info is in (frame_decode.hip: PipelineJob); JXLHIP_NO_PIPELINE=1 runs
     the three phases of FrameDecoder one after the other (dec_frame.cc:596-703).  Same pixels, bit for bit, same
     coefficient type, for several worker counts -- and equal to the reference decoder's."""
     import torch
@@ -241,6 +241,57 @@ def test_redo_with_int32_coefficients(L, ref, barriers, workers, group, monkeypa
     for _, px in got:
         assert float(np.abs(px - rs.rgb).max()) / scale <= TIGHT
     assert np.array_equal(got[0][1], got[2][1])
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("barriers", [False, True])
+def test_redo_with_int32_coefficients_of_a_frame_with_alpha(L, ref, barriers, monkeypatch):
+    """The int32 redo of a frame whose AC-group sections carry an extra channel behind the coefficients: the bit
+    positions where the Modular part of each section begins are written by the 16-bit attempt and again by the int32
+    one.  8-bit RGBA of the 520x300 alpha stream of tests/test_extra_channels.py (six AC groups, one DC group), with
+    and without JXLHIP_TEST_RANGE_GROUP: the alpha bytes are equal (the host's integer path), the colour samples agree
+    to the bar of test_redo_with_int32_coefficients."""
+    import torch
+    from libjxl_amd import VarDctDecoder
+    rs = ref.RealStream(seed=31, xsize=520, ysize=300, alpha_bits=8, distance=1.0, speed_tier=3)
+    cs = rs.codestream.tobytes()
+    W, H = rs.xsize, rs.ysize
+    R = C.CDLL(abi.runner_library_path())
+    R.JxlThreadParallelRunnerCreate.restype = C.c_void_p
+    R.JxlThreadParallelRunnerCreate.argtypes = [C.c_void_p, C.c_size_t]
+    R.JxlThreadParallelRunnerDestroy.argtypes = [C.c_void_p]
+    runner = C.cast(R.JxlThreadParallelRunner, C.c_void_p)
+    pool = R.JxlThreadParallelRunnerCreate(None, 4)
+    dec = VarDctDecoder(0)
+    fmt8 = abi.OutputFormat(1, 1, 4, 8, 0, 0.0, (C.c_float * 3)(0.2126, 0.7152, 0.0722))
+    if barriers:
+        monkeypatch.setenv("JXLHIP_NO_PIPELINE", "1")
+    try:
+        got = []
+        for hook in (None, "4"):
+            if hook:
+                monkeypatch.setenv("JXLHIP_TEST_RANGE_GROUP", hook)
+            else:
+                monkeypatch.delenv("JXLHIP_TEST_RANGE_GROUP", raising=False)
+            abi.load_library().jxlhip_debug_reload_env()
+            info = abi.CodestreamInfo()
+            out = torch.zeros((H, W, 4), dtype=torch.uint8, device="cuda")
+            rc = L.jxlhip_decode_codestream(dec.ctx, runner, pool, cs, len(cs), 2, C.byref(fmt8), out.data_ptr(), W * 4, 0, C.byref(info))
+            assert rc == 0, (hook, rc, L.jxlhip_last_error(dec.ctx))
+            got.append((info.coeff_type, out.cpu().numpy()))
+    finally:
+        dec.close()
+        R.JxlThreadParallelRunnerDestroy(pool)
+        monkeypatch.delenv("JXLHIP_TEST_RANGE_GROUP", raising=False)
+        monkeypatch.delenv("JXLHIP_NO_PIPELINE", raising=False)
+        abi.load_library().jxlhip_debug_reload_env()
+    assert [g[0] for g in got] == [0, 1]  # JXLHIP_COEFF_I16, then _I32
+    plain, redone = got[0][1], got[1][1]
+    assert np.array_equal(plain[..., 3], np.rint(rs.alpha * 255.0).astype(np.uint8))
+    assert np.array_equal(redone[..., 3], plain[..., 3])
+    diff = float(np.abs(redone[..., :3].astype(np.float32) - plain[..., :3].astype(np.float32)).max()) / 255.0
+    print("colour, int32 redo against the 16-bit decode: max |diff| = %g of full scale" % diff)
+    assert diff <= TIGHT
 
 
 @pytest.mark.gpu
