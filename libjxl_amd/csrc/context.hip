@@ -11,6 +11,7 @@
 
 #include "context.h"
 #include "dither_pattern.inc"
+#include "phase1_plan.h"
 
 extern "C" __attribute__((visibility("default"))) void jxlhip_debug_reload_env(void) {
   std::lock_guard<std::mutex> lock(jxlhip_env::g.mu);
@@ -486,17 +487,10 @@ DevFrame Phase1Frame(const jxlhip_ctx* c, int fused) {
   DevFrame f = c->f;
   f.fused = (uint32_t)fused;
   f.cell_info = c->cell_info;
-  constexpr uint32_t kOthers32 = (1u << 8) | (1u << 9) | (1u << 10) | (1u << 11);  // 32x8 .. 16x32
-  const bool lone32 = (f.used_acs & (1u << 5)) && !(f.used_acs & kOthers32);
-  f.mfma32 = (c->mfma > 0 || (c->mfma < 0 && lone32)) ? c->tables + kTabMfma32 : nullptr;
-  // DCT16X16: the same rule against the 16-point row-per-lane family (16x8, 8x16), only when no 32-point class
-  // pulls the merged launch in anyway, and on frames of 16 Mpx and more (measured, all-DCT16X16 frames: 8K blocks
-  // 132 -> 118 us, 16x16 + 32x32 176 -> 161 us; 4K 33.6 -> 37.6 us: the butterflies stay; on the mixed c3 frame a
-  // launch of its own costs 97 -> 117 us, like DCT32X32)
-  constexpr uint32_t kOthers16 = (1u << 6) | (1u << 7);
-  const bool lone16 = (f.used_acs & (1u << 4)) && !(f.used_acs & (kOthers16 | kOthers32)) &&
-                      (!(f.used_acs & (1u << 5)) || f.mfma32) && (uint64_t)f.xsize * f.ysize >= (16u << 20);
-  f.mfma16 = (c->mfma > 0 || (c->mfma < 0 && lone16)) ? c->tables + kTabMfma16 : nullptr;
+  // DCT32X32 / DCT16X16 on the matrix cores: the rule is PickMfma's (phase1_plan.h)
+  const Phase1Mfma m = PickMfma(f.used_acs, (uint64_t)f.xsize * f.ysize, c->mfma);
+  f.mfma32 = m.mfma32 ? c->tables + kTabMfma32 : nullptr;
+  f.mfma16 = m.mfma16 ? c->tables + kTabMfma16 : nullptr;
   return f;
 }
 

@@ -15,10 +15,9 @@
 
 #include <type_traits>
 
-#include <initializer_list>
-
 #include "blocks_common.h"
 #include "env_switches.h"
+#include "phase1_plan.h"
 
 namespace jxlhip {
 
@@ -358,8 +357,8 @@ static constexpr TabOffsets kSingleTabOffset = MakeTabOffsets();
 
 template <typename CT>
 struct Dct8Geom {
-  static constexpr int kSteps = sizeof(CT) == 2 ? 4 : 2;  // steps of 8 blocks per wave
-  static constexpr uint32_t kPerWg = 4 * kSteps * 8;      // blocks per 256-thread workgroup
+  static constexpr int kSteps = Dct8Steps(sizeof(CT) == 2);      // steps of 8 blocks per wave
+  static constexpr uint32_t kPerWg = Dct8PerWg(sizeof(CT) == 2);  // blocks per 256-thread workgroup
 };
 
 // workgroup `wg` of the DCT8 list (n entries)
@@ -1479,12 +1478,8 @@ __global__ __launch_bounds__(256) void k_large(DevFrame f, const WorkItem* __res
 // 128 blocks of area of ONE class, located from the class list lengths k_prepare left on the
 // device (a prefix over the family's counters in SGPRs).  The host never learns the list
 // lengths; it bounds the unit count by cells/64 + N and caps the grid at a few resident
-// generations, the workgroups loop (UnitDispatch).
-struct FamilyEntry {
-  int cls;
-  int unit_varblocks;
-};
-
+// generations, the workgroups loop (UnitDispatch).  The family tables (FamilyEntry, kFamilyA / A1 / R / R16 / R32), the
+// grids and the roles of the merged launch: phase1_plan.h.
 struct UnitPick {
   int index;       // entry of the family, -1 = past the end
   int cls;         // its work class
@@ -1517,19 +1512,6 @@ static_assert(TransposeLdsBytes<32>() <= kLdsFamilyA && TransposeLdsBytes<16>() 
 static_assert(sizeof(BlockHdr) <= 48, "header slots are 48 bytes");
 static_assert(MediumGeom<64, 32>::kLdsBytes <= kLdsFamilyA && MediumGeom<32, 64>::kLdsBytes <= kLdsFamilyA, "");
 
-// A: 64x64, 64x32, 32x64 (long units first)
-static constexpr FamilyEntry kFamilyA[3] = {{kClsMedium0 + 8, 1}, {kClsMedium0 + 9, 2}, {kClsMedium0 + 10, 2}};
-// B: 16x8 .. 32x32, long units first so that the drain ends on short ones
-// row-per-lane kernels, 4 waves x (64 / S) varblocks per unit.  R16: longer side 16 (4 waves per
-// SIMD), R32: longer side 32 (twice the registers per lane)
-static constexpr FamilyEntry kFamilyR16[3] = {{kClsMedium0 + 2, 16}, {kClsMedium0 + 0, 32}, {kClsMedium0 + 1, 32}};
-static constexpr FamilyEntry kFamilyR32[5] = {{kClsMedium0 + 7, 8},  {kClsMedium0 + 5, 16}, {kClsMedium0 + 6, 16},
-                                              {kClsMedium0 + 3, 32}, {kClsMedium0 + 4, 32}};
-static_assert(kMediumStrategy[8] == 18 && kMediumStrategy[9] == 19 && kMediumStrategy[10] == 20 &&
-              kMediumStrategy[7] == 5 && kMediumStrategy[5] == 10 && kMediumStrategy[6] == 11 &&
-              kMediumStrategy[2] == 4 && kMediumStrategy[3] == 8 && kMediumStrategy[4] == 9 &&
-              kMediumStrategy[0] == 6 && kMediumStrategy[1] == 7, "class table mismatch");
-
 // Workgroup w decodes units w, w + gridDim.x, ... of the family.  The host only knows the
 // bound cells/64 + N on the unit count; a grid of that size costs ~10 us per launch in
 // workgroups that find nothing to do when the family covers a small part of the frame, so
@@ -1553,9 +1535,7 @@ __device__ __forceinline__ void UnitDispatch(const FamilyEntry (&fam)[N], const 
   }
 }
 
-// one varblock per task for every class of the family
-static constexpr FamilyEntry kFamilyA1[3] = {{kClsMedium0 + 8, 1}, {kClsMedium0 + 9, 1}, {kClsMedium0 + 10, 1}};
-
+// int16: one varblock per task for every class of the family (kFamilyA1)
 __device__ __forceinline__ void FamilyALoop16(const DevFrame& f, const WorkLists& wl, unsigned char* smem, uint32_t wg_index,
                                               uint32_t num_wgs) {
   uint32_t cnt[3];
@@ -1605,11 +1585,12 @@ __device__ __forceinline__ void FamilyALoop16(const DevFrame& f, const WorkLists
 // (168 VGPRs, what its LDS use allows anyway); the 64-point transforms would like ~180 and
 // spill a few values to scratch instead.  In row-per-lane form (64 values per lane, > 256
 // registers, one wave per SIMD) these classes were 30 % slower.
+// workgroup wg_index of the num_wgs that share the 64-point family
 template <typename CT>
-__global__ __launch_bounds__(192, sizeof(CT) == 2 ? 3 : 2) void k_transform_a(DevFrame f, WorkLists wl) {
-  __shared__ __attribute__((aligned(16))) unsigned char smem[kLdsFamilyA];
+__device__ __forceinline__ void FamilyAWorkgroup(const DevFrame& f, const WorkLists& wl, unsigned char* smem,
+                                                 uint32_t wg_index, uint32_t num_wgs) {
   if constexpr (sizeof(CT) == 2) {
-    FamilyALoop16(f, wl, smem, blockIdx.x, gridDim.x);
+    FamilyALoop16(f, wl, smem, wg_index, num_wgs);
   } else {
     UnitDispatch(kFamilyA, wl,
                  [&](int index, const WorkItem* __restrict__ list, uint32_t first, uint32_t n) {
@@ -1619,44 +1600,52 @@ __global__ __launch_bounds__(192, sizeof(CT) == 2 ? 3 : 2) void k_transform_a(De
                      default: MediumUnit<32, 64, 20, CT>(f, list, first, n, smem); break;
                    }
                  },
-                 blockIdx.x, gridDim.x);
+                 wg_index, num_wgs);
+  }
+}
+
+template <typename CT>
+__global__ __launch_bounds__(192, sizeof(CT) == 2 ? 3 : 2) void k_transform_a(DevFrame f, WorkLists wl) {
+  __shared__ __attribute__((aligned(16))) unsigned char smem[kLdsFamilyA];
+  FamilyAWorkgroup<CT>(f, wl, smem, blockIdx.x, gridDim.x);
+}
+
+// one unit of class `index` of kFamilyR.  LDS_T: the transposes go through smem (the merged launch, which has family
+// A's allocation anyway); the stand-alone kernels declare no LDS (k_transform_r16: 93 VGPRs, five waves per SIMD)
+template <typename CT, bool LDS_T>
+__device__ __forceinline__ void RowLaneCase(int index, const DevFrame& f, const WorkItem* __restrict__ list,
+                                            uint32_t first, uint32_t n, unsigned char* smem) {
+  switch (index) {
+    case 0: RowLaneUnit<32, 32, 5, CT, LDS_T>(f, list, first, n, smem); break;
+    case 1: RowLaneUnit<32, 16, 10, CT, LDS_T>(f, list, first, n, smem); break;
+    case 2: RowLaneUnit<16, 32, 11, CT, LDS_T>(f, list, first, n, smem); break;
+    case 3: RowLaneUnit<32, 8, 8, CT, LDS_T>(f, list, first, n, smem); break;
+    case 4: RowLaneUnit<8, 32, 9, CT, LDS_T>(f, list, first, n, smem); break;
+    case 5: RowLaneUnit<16, 16, 4, CT, LDS_T>(f, list, first, n, smem); break;
+    case 6: RowLaneUnit<16, 8, 6, CT, LDS_T>(f, list, first, n, smem); break;
+    default: RowLaneUnit<8, 16, 7, CT, LDS_T>(f, list, first, n, smem); break;
   }
 }
 
 template <typename CT>
 __global__ __launch_bounds__(256) void k_transform_r16(DevFrame f, WorkLists wl) {
-  UnitDispatch(kFamilyR16, wl,
+  UnitDispatch(kFamilyR16.e, wl,
                [&](int index, const WorkItem* __restrict__ list, uint32_t first, uint32_t n) {
-                 switch (index) {
-                   case 0: RowLaneUnit<16, 16, 4, CT>(f, list, first, n); break;
-                   case 1: RowLaneUnit<16, 8, 6, CT>(f, list, first, n); break;
-                   default: RowLaneUnit<8, 16, 7, CT>(f, list, first, n); break;
-                 }
+                 RowLaneCase<CT, false>(index + kNumR32, f, list, first, n, nullptr);
                },
                blockIdx.x, gridDim.x, f.mfma16 != nullptr ? 1u : 0u);
 }
 
 template <typename CT>
 __global__ __launch_bounds__(256) void k_transform_r32(DevFrame f, WorkLists wl) {
-  UnitDispatch(kFamilyR32, wl,
+  UnitDispatch(kFamilyR32.e, wl,
                [&](int index, const WorkItem* __restrict__ list, uint32_t first, uint32_t n) {
-                 switch (index) {
-                   case 0: RowLaneUnit<32, 32, 5, CT>(f, list, first, n); break;
-                   case 1: RowLaneUnit<32, 16, 10, CT>(f, list, first, n); break;
-                   case 2: RowLaneUnit<16, 32, 11, CT>(f, list, first, n); break;
-                   case 3: RowLaneUnit<32, 8, 8, CT>(f, list, first, n); break;
-                   default: RowLaneUnit<8, 32, 9, CT>(f, list, first, n); break;
-                 }
+                 RowLaneCase<CT, false>(index, f, list, first, n, nullptr);
                },
                blockIdx.x, gridDim.x, f.mfma32 != nullptr ? 1u : 0u);
 }
 
-// Both row-per-lane families in one launch, the (few, long, register-heavy) L = 32 units first:
-// on a mixed frame their single-generation latency (~27 us as a launch of its own) disappears
-// behind the L = 16 bulk, at the price of the L = 16 units running at the L = 32 occupancy.
-static constexpr FamilyEntry kFamilyR[8] = {{kClsMedium0 + 7, 8},  {kClsMedium0 + 5, 16}, {kClsMedium0 + 6, 16},
-                                            {kClsMedium0 + 3, 32}, {kClsMedium0 + 4, 32}, {kClsMedium0 + 2, 16},
-                                            {kClsMedium0 + 0, 32}, {kClsMedium0 + 1, 32}};
+// Both row-per-lane families in one launch (kFamilyR), the L = 32 units first
 // ... and, on its first `big_wgs` workgroups, the LDS-staged 64-point classes of family A: their
 // workgroups are three waves (the fourth ends at once; a finished wave no longer counts at the
 // workgroup barrier) looping over the big units, while the others loop over the row-per-lane units.
@@ -1674,138 +1663,49 @@ __global__ __launch_bounds__(256, sizeof(CT) == 2 ? 3 : 2) void k_transform_r(De
     SpecialWorkgroup<CT>(f, wl, blockIdx.x);
     return;
   }
-  // Two-phase: the DCT8 workgroups (short, LDS-free, the bulk of a d1.0 frame) alternate with the persistent
-  // workgroups of the other classes in the dispatch order, so that the two kinds run side by side from the first
-  // wave on -- as two launches the second waits for the first's tail, which on frames of a few Mpx is most of it
-  // (1080p: blocks 39 -> ? us; the two-stream form pays ~40 us of fork / join events instead).
-  // The launch is sized for a frame of nothing but DCT8 (dct8_wgs); k_prepare's count says how many of those
-  // workgroups have work (need8).  On genuine content -- a few per cent DCT8 -- thousands of empty workgroups between
-  // the persistent ones cost more than the DCT8 blocks themselves: then only the ones with work alternate and the
-  // surplus sits at the end of the grid, leaving at once (two-phase, real-content shares: 8K 257 -> 200 us, 4K 61 ->
-  // 51 us).  With a quarter or more of the bound in use (the d1 mix: 45 %) the old placement stays: there the empty
-  // workgroups between the later persistent ones HELP (4K 39 vs 45 us; profiles/r03_dct8_workgroup_roles.txt).
-  const uint32_t np = big_wgs + r_wgs;
+  // Two-phase: the DCT8 workgroups alternate with the persistent workgroups of the other classes (RoleOf,
+  // phase1_plan.h); k_prepare's count says how many of the launch's DCT8 workgroups have work.  (The kinds are tested in
+  // the order the decode finds them: as a switch the int16 instance needs 166 VGPRs instead of 165.)
   const uint32_t i = blockIdx.x - special_wgs;
   const uint32_t need8 = (wl.count[kClsDct8 * kCounterPad] + Dct8Geom<CT>::kPerWg - 1) / Dct8Geom<CT>::kPerWg;
-  const uint32_t d8 = need8 * 4 < dct8_wgs ? need8 : dct8_wgs;
-  const uint32_t pairs = np < d8 ? np : d8;
-  bool is_dct8;
-  uint32_t idx;
-  if (i < 2 * pairs) {
-    is_dct8 = (i & 1u) != 0;
-    idx = i >> 1;
-  } else {
-    is_dct8 = d8 > np;
-    idx = i - pairs;
-    if (idx >= (is_dct8 ? d8 : np)) return;
-  }
-  if (is_dct8) {
-    Dct8Rows<CT>(f, wl.list[kClsDct8], wl.count[kClsDct8 * kCounterPad], idx);
+  const Phase1Role role = RoleOf(i, big_wgs, r_wgs, dct8_wgs, need8);
+  if (role.kind == kRoleIdle) return;
+  if (role.kind == kRoleDct8) {
+    Dct8Rows<CT>(f, wl.list[kClsDct8], wl.count[kClsDct8 * kCounterPad], role.idx);
     return;
   }
-  if (idx < big_wgs) {
+  if (role.kind == kRoleBig) {
     if (threadIdx.x >= 192) return;
-    if constexpr (sizeof(CT) == 2) {
-      FamilyALoop16(f, wl, smem, idx, big_wgs);
-    } else {
-      UnitDispatch(kFamilyA, wl,
-                   [&](int index, const WorkItem* __restrict__ list, uint32_t first, uint32_t n) {
-                     switch (index) {
-                       case 0: MediumUnit<64, 64, 18, CT>(f, list, first, n, smem); break;
-                       case 1: MediumUnit<64, 32, 19, CT>(f, list, first, n, smem); break;
-                       default: MediumUnit<32, 64, 20, CT>(f, list, first, n, smem); break;
-                     }
-                   },
-                   idx, big_wgs);
-    }
+    FamilyAWorkgroup<CT>(f, wl, smem, role.idx, big_wgs);
     return;
   }
   UnitDispatch(kFamilyR, wl,
                [&](int index, const WorkItem* __restrict__ list, uint32_t first, uint32_t n) {
-                 switch (index) {
-                   case 0: RowLaneUnit<32, 32, 5, CT, true>(f, list, first, n, smem); break;
-                   case 1: RowLaneUnit<32, 16, 10, CT, true>(f, list, first, n, smem); break;
-                   case 2: RowLaneUnit<16, 32, 11, CT, true>(f, list, first, n, smem); break;
-                   case 3: RowLaneUnit<32, 8, 8, CT, true>(f, list, first, n, smem); break;
-                   case 4: RowLaneUnit<8, 32, 9, CT, true>(f, list, first, n, smem); break;
-                   case 5: RowLaneUnit<16, 16, 4, CT, true>(f, list, first, n, smem); break;
-                   case 6: RowLaneUnit<16, 8, 6, CT, true>(f, list, first, n, smem); break;
-                   default: RowLaneUnit<8, 16, 7, CT, true>(f, list, first, n, smem); break;
-                 }
+                 RowLaneCase<CT, true>(index, f, list, first, n, smem);
                },
-               idx - big_wgs, r_wgs, (f.mfma32 != nullptr ? 1u : 0u) | (f.mfma16 != nullptr ? 1u << 5 : 0u));
+               role.idx, r_wgs, (f.mfma32 != nullptr ? 1u : 0u) | (f.mfma16 != nullptr ? 1u << kNumR32 : 0u));
 }
 
 // --------------------------------------------------------------- launchers
 template <typename CT>
 static void LaunchBlocksT(const DevFrame& f, const WorkLists& wl, uint32_t cells, const float* wc,
                           const float* resample, hipStream_t st, const FilterParams* emit) {
-  const uint32_t units = cells / 64;
-  const uint32_t grid_l = cells / 128 < 512u ? (cells / 128 ? cells / 128 : 1) : 512u;
-  constexpr uint32_t kDct8PerWg = Dct8Geom<CT>::kPerWg;
-  // caps: residency of the kernel (workgroups per CU by LDS / registers) x 256 CUs x 2 generations
-  uint32_t grid_a = units + 3 < 1536u ? units + 3 : 1536u;
-  uint32_t grid_r16 = units + 3 < 4096u ? units + 3 : 4096u;
-  uint32_t grid_r32 = units / 2 + 5 < 3072u ? units / 2 + 5 : 3072u;  // units of 128 blocks
-  // experiments and tests/test_gpu_phase1_loops.py: fewer workgroups for the 64-point family (JXLHIP_BIG_WGS) or the
-  // row-per-lane families (JXLHIP_R_WGS), so that each one walks many units (anything outside [1, 4096]: the built-in caps)
-  const int big_env = jxlhip_env::Get().big_wgs.load(std::memory_order_relaxed);
-  const int r_env = jxlhip_env::Get().r_wgs.load(std::memory_order_relaxed);
-  const bool big_set = big_env >= 1 && big_env <= 4096;
-  if (big_set && (uint32_t)big_env < grid_a) grid_a = (uint32_t)big_env;
-  if (r_env >= 1 && r_env <= 4096) {
-    if ((uint32_t)r_env < grid_r16) grid_r16 = (uint32_t)r_env;
-    if ((uint32_t)r_env < grid_r32) grid_r32 = (uint32_t)r_env;
-  }
-  // used_acs (when the caller knows it) says which families have work at all
-  auto any = [&](std::initializer_list<int> strategies) {
-    if (f.used_acs == 0) return true;
-    for (int s : strategies)
-      if (f.used_acs & (1u << s)) return true;
-    return false;
-  };
-  const bool need_r16 = any({6, 7}) || (!f.mfma16 && any({4}));
-  const bool need_r32 = any({8, 9, 10, 11}) || (!f.mfma32 && any({5}));
-  const bool merged_r = need_r16 && need_r32;
-  const bool have_big = any({18, 19, 20});
-  bool specials_in_r = false, dct8_in_r = false;
-  uint32_t grid_specials = 0, grid_dct8 = 0;
-  if (have_big && !merged_r)
-    hipLaunchKernelGGL((k_transform_a<CT>), dim3(grid_a), dim3(192), 0, st, f, wl);
-  {
-    // worst cases: all cells special (3 tasks per 64 blocks, 4 tasks per workgroup) or all DCT8
-    const bool specials = any({1, 2, 3, 12, 13, 14, 15, 16, 17});
-    const uint32_t bound_s = specials ? (cells / 64 + kNumSpecial) * 3 / 4 + 1 : 0;
-    // fused == 2 (a stripe): only the DCT8 cells of the two block rows its neighbours pull are on the list
-    const uint32_t cells_8 = f.fused == 0 ? cells : (f.fused == 2 ? 2u * f.xsb : 0u);
-    const uint32_t bound_8 = (any({0}) && cells_8) ? (cells_8 + kDct8PerWg - 1) / kDct8PerWg : 0;
-    const uint32_t grid_8 = (bound_s > bound_8 ? bound_s : bound_8) + (specials ? kNumSpecial : 0);
-    // merged_r: the single-block classes ride in k_transform_r's launch (specials at its head, DCT8 workgroups
-    // alternating with the other classes' persistent ones)
-    specials_in_r = merged_r && specials;
-    dct8_in_r = merged_r && bound_8 != 0;
-    grid_specials = bound_s + kNumSpecial;
-    grid_dct8 = bound_8;
-    if (grid_8 && !merged_r) hipLaunchKernelGGL((k_transform_8<CT>), dim3(grid_8), dim3(256), 0, st, f, wl);
-  }
-  if (merged_r) {  // -10 us per 8K d1.0 frame against two launches, -15 us more with family A inside
-    const uint32_t big_cap = big_set ? (uint32_t)big_env : 512u;
-    const uint32_t big_wgs = have_big ? (grid_a < big_cap ? grid_a : big_cap) : 0u;
-    const uint32_t special_wgs = specials_in_r ? grid_specials : 0u;
-    const uint32_t dct8_wgs = dct8_in_r ? grid_dct8 : 0u;
-    // (round 6, again: the 16-point classes in a launch of their own -- 93 VGPRs, no LDS, five waves per SIMD, where inside
-    // this launch they run at three: all-DCT16X16 frames 159 against 115 us -- cost 9 us more per frame on both the d1 mix
-    // and genuine-content shares, profiles/r06_transform_overread.txt; the single launch stays)
-    hipLaunchKernelGGL((k_transform_r<CT>), dim3(special_wgs + big_wgs + grid_r16 + dct8_wgs), dim3(256), 0, st, f, wl,
-                       big_wgs, special_wgs, grid_r16, dct8_wgs);
-  } else {
-    if (need_r16) hipLaunchKernelGGL((k_transform_r16<CT>), dim3(grid_r16), dim3(256), 0, st, f, wl);
-    if (need_r32) hipLaunchKernelGGL((k_transform_r32<CT>), dim3(grid_r32), dim3(256), 0, st, f, wl);
-  }
-  if (f.mfma32 && any({5})) LaunchMfma32(f, wl, cells, st, emit);
-  if (f.mfma16 && any({4})) LaunchMfma16(f, wl, cells, st);
-  if (cells >= 256 && any({21, 22, 23, 24, 25, 26}))
-    hipLaunchKernelGGL(k_large<CT>, dim3(grid_l), dim3(256), 0, st, f, wl.list[kClsLarge],
+  // the launches, in this order on `st`, with the grids of PlanPhase1 (phase1_plan.h)
+  Phase1Inputs in{cells, f.used_acs, f.coeff_type, f.fused, f.xsb, f.mfma32 != nullptr, f.mfma16 != nullptr,
+                  jxlhip_env::Get().big_wgs.load(std::memory_order_relaxed),
+                  jxlhip_env::Get().r_wgs.load(std::memory_order_relaxed)};
+  const Phase1Plan p = PlanPhase1(in);
+  if (p.transform_a) hipLaunchKernelGGL((k_transform_a<CT>), dim3(p.transform_a), dim3(192), 0, st, f, wl);
+  if (p.transform_8) hipLaunchKernelGGL((k_transform_8<CT>), dim3(p.transform_8), dim3(256), 0, st, f, wl);
+  if (p.transform_r)
+    hipLaunchKernelGGL((k_transform_r<CT>), dim3(p.transform_r), dim3(256), 0, st, f, wl, p.big_wgs, p.special_wgs,
+                       p.r_wgs, p.dct8_wgs);
+  if (p.transform_r16) hipLaunchKernelGGL((k_transform_r16<CT>), dim3(p.transform_r16), dim3(256), 0, st, f, wl);
+  if (p.transform_r32) hipLaunchKernelGGL((k_transform_r32<CT>), dim3(p.transform_r32), dim3(256), 0, st, f, wl);
+  if (p.mfma32) LaunchMfma32(f, wl, p.mfma32, st, emit);
+  if (p.mfma16) LaunchMfma16(f, wl, p.mfma16, st);
+  if (p.large)
+    hipLaunchKernelGGL(k_large<CT>, dim3(p.large), dim3(256), 0, st, f, wl.list[kClsLarge],
                        wl.count + kClsLarge * kCounterPad, wc, resample);
 }
 

@@ -410,10 +410,8 @@ void MfmaDct16Constants(float* host /* 256 floats */) {
   }
 }
 
-void LaunchMfma16(const DevFrame& f, const WorkLists& wl, uint32_t cells, hipStream_t st) {
+void LaunchMfma16(const DevFrame& f, const WorkLists& wl, uint32_t grid, hipStream_t st) {
   const int cls = kClsMedium0 + 2;  // DCT16X16 (kMediumStrategy[2] == 4)
-  uint32_t grid = cells / 4 / 4 + 1;  // varblocks / 4 waves
-  if (grid > 4096u) grid = 4096u;
   if (f.coeff_type == JXLHIP_COEFF_I16)
     hipLaunchKernelGGL((k_transform_mfma16<int16_t>), dim3(grid), dim3(256), 0, st, f, wl.list[cls],
                        wl.count + cls * kCounterPad, f.mfma16);
@@ -440,11 +438,9 @@ void MfmaDct32Constants(float* host /* 2048 floats */) {
     }
 }
 
-void LaunchMfma32(const DevFrame& f, const WorkLists& wl, uint32_t cells, hipStream_t st, const FilterParams* emit) {
+void LaunchMfma32(const DevFrame& f, const WorkLists& wl, uint32_t grid, hipStream_t st, const FilterParams* emit) {
   const float* bc = f.mfma32;
   const int cls = kClsMedium0 + 7;  // DCT32X32 (kMediumStrategy[7] == 5)
-  uint32_t grid = cells / 16 / 4 + 1;  // varblocks / 4 waves
-  if (grid > 2048u) grid = 2048u;
   const FilterParams none{};
 #define JXLHIP_MFMA(CT, E)                                                                                  \
   hipLaunchKernelGGL((k_transform_mfma32<CT, E>), dim3(grid), dim3(256), 0, st, f, wl.list[cls],            \

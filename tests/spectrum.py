@@ -32,6 +32,7 @@ import torch
 
 import frames
 from libjxl_amd import synth
+from phase1_plan import launch_of  # noqa: F401  (the restated launch rule of phase 1: need_r16 / need_r32 / merged)
 
 LARGE_PER_BLOCK = 64           # at most this many range-setting impulses per varblock and channel
 SMALL_VALUES = (1, -1, 2, -3, 7, -300)
@@ -89,17 +90,6 @@ def strategy_blocks(t, s):
     base = (g * GROUP + off)[st == s]
     idx = base[:, None] + np.arange(slots(s), dtype=np.int64)[None, :]
     return np.stack([t["coeffs"][c].numpy()[idx].astype(np.int64) for c in range(3)])
-
-
-# ---- the launch LaunchBlocksT takes (kernels_blocks.hip), restated ----------------------------------------------------
-def launch_of(used_acs, mfma):
-    """need_r16 / need_r32 / merged from the frame's used_acs and JXLHIP_MFMA (1: DCT16X16 and DCT32X32 leave the
-    row-per-lane families for the matrix-core kernels)."""
-    def any_of(*ss):
-        return any(used_acs >> s & 1 for s in ss)
-    need_r16 = any_of(6, 7) or (not mfma and any_of(4))
-    need_r32 = any_of(8, 9, 10, 11) or (not mfma and any_of(5))
-    return dict(need_r16=need_r16, need_r32=need_r32, merged=need_r16 and need_r32)
 
 
 def used_set(params):

@@ -1,7 +1,7 @@
 """The persistent phase-1 loops past their first turn.
 
 Every phase-1 kernel (kernels_blocks.hip, kernels_mfma.hip) is a persistent launch: the host caps the grid
-(LaunchBlocksT, LaunchMfma32 / 16) and a workgroup -- a wave, on the matrix cores -- walks units u, u + workers, ...,
+(PlanPhase1, phase1_plan.h) and a workgroup -- a wave, on the matrix cores -- walks units u, u + workers, ...,
 reusing its LDS and carrying state from one varblock to the next (FamilyALoop16: the APrefetch registers, the hc / hn
 header swap, the request for varblock k + 1 in front of varblock k's stores; k_transform_mfma32 / 16: the Staged
 prefetch; UnitDispatch: the barrier in front of the LDS reuse; k_large: the llf / dcs tiles).  At the sizes of the
@@ -10,7 +10,9 @@ other parity tests no workgroup takes a second turn.  Here every case
   1. first PROVES that it loops: launch_plan() restates the launch rule (units per kernel from the strategy map and
      the coefficient type, workgroups from the caps and the knobs) and the case asserts its minimum turn count before
      it decodes, so that a retuned cap or a changed synth cannot quietly make it a one-turn test
-     (tests/test_phase1_launch_plan.py pins CAPS to the source text and checks that the assertions bite);
+     (tests/phase1_plan.py holds the restatement; tests/test_phase1_launch_plan.py pins its caps, its family tables
+     and its plans to the compiled libjxl_amd/csrc/phase1_plan.h through tests/fuzz/check_phase1_plan.cc, on the
+     CPU, and checks that the assertions bite);
   2. compares with the oracle at the bar of test_gpu_parity.py (TIGHT);
   3. compares, bit for bit, with the same frame decoded in a geometry where no workgroup takes a second turn
      (JXLHIP_BIG_WGS / JXLHIP_R_WGS unset at the small sizes; k_large: the frame decoded in stripes): how varblocks
@@ -50,98 +52,8 @@ TIGHT = 2e-5     # test_gpu_parity.py: what the kernels are held to (relative to
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 I32 = dict(coeff_type=1, amp=200000.0, decay=3.0)   # coefficients that need 32 bits, as in test_gpu_parity.py
 
-# ---- the launch rule, restated ------------------------------------------------------------------------------------
-# Grid caps of LaunchBlocksT (kernels_blocks.hip) and LaunchMfma32 / LaunchMfma16 (kernels_mfma.hip), in workgroups.
-# tests/test_phase1_launch_plan.py reads them out of the source text: a retuned cap fails there and names this table.
-CAPS = dict(grid_a=1536, big_cap=512, grid_r16=4096, grid_r32=3072, grid_l=512, mfma32=2048, mfma16=4096)
-# (strategy, varblocks per unit) in PickUnit's order: kFamilyA / kFamilyA1, kFamilyR, kFamilyR16, kFamilyR32
-FAMILY_A = {0: [(18, 1), (19, 1), (20, 1)], 1: [(18, 1), (19, 2), (20, 2)]}  # by coefficient type
-FAMILY_R = [(5, 8), (10, 16), (11, 16), (8, 32), (9, 32), (4, 16), (6, 32), (7, 32)]
-FAMILY_R16 = [(4, 16), (6, 32), (7, 32)]
-FAMILY_R32 = [(5, 8), (10, 16), (11, 16), (8, 32), (9, 32)]
-
-
-class Launch:
-    """One persistent launch (or role of the merged launch): `units` dealt round-robin to `workers`."""
-
-    def __init__(self, units, workers, per_class):
-        self.units, self.workers, self.per_class = int(units), int(workers), dict(per_class)
-
-    @property
-    def min_turns(self):  # turns every worker takes
-        return self.units // self.workers
-
-    @property
-    def max_turns(self):
-        return -(-self.units // self.workers)
-
-    def workers_with(self, turns):  # how many workers take at least `turns` turns
-        return max(0, min(self.workers, self.units - (turns - 1) * self.workers))
-
-    def __repr__(self):
-        return "Launch(%d units / %d workers, %s)" % (self.units, self.workers, self.per_class)
-
-
-def strategy_counts(acs):
-    acs = np.asarray(acs)
-    return np.bincount(acs[(acs & 1) == 1] >> 1, minlength=27)
-
-
-def _knob(v):
-    return int(v) if v is not None and 1 <= int(v) <= 4096 else None  # anything else: the built-in value
-
-
-def launch_plan(acs, xsize, ysize, coeff_type=0, big_wgs=None, r_wgs=None, mfma=None, group_rows=None, caps=CAPS):
-    """{kernel: Launch} of one jxlhip_decode_blocks call, by the rule of LaunchBlocksT / LaunchBlocksBand: "a"
-    (k_transform_a, or the 64-point role of k_transform_r), "r" (the row-per-lane role of k_transform_r) or "r16" /
-    "r32" (the stand-alone kernels), "large", "mfma32" / "mfma16" (workers = waves).  `acs`: the strategy map of the
-    rows decoded (the whole frame, or the stripe of `group_rows` group rows); big_wgs / r_wgs / mfma: the values of
-    JXLHIP_BIG_WGS / JXLHIP_R_WGS / JXLHIP_MFMA (None = unset)."""
-    n = strategy_counts(acs)
-    used = lambda *ss: any(n[s] for s in ss)  # noqa: E731
-    xsg, ysg = (xsize + 255) // 256, (ysize + 255) // 256
-    cells = xsg * (group_rows or ysg) * 1024
-    units = cells // 64
-    mfma = None if mfma is None else int(mfma) != 0
-    lone32 = used(5) and not used(8, 9, 10, 11)
-    mfma32 = lone32 if mfma is None else mfma
-    lone16 = used(4) and not used(6, 7, 8, 9, 10, 11) and (not used(5) or mfma32) and xsize * ysize >= (16 << 20)
-    mfma16 = lone16 if mfma is None else mfma
-    big, rw = _knob(big_wgs), _knob(r_wgs)
-    grid_a = min(units + 3, caps["grid_a"], big or (1 << 30))
-    grid_r16 = min(units + 3, caps["grid_r16"], rw or (1 << 30))
-    grid_r32 = min(units // 2 + 5, caps["grid_r32"], rw or (1 << 30))
-    grid_l = min(max(cells // 128, 1), caps["grid_l"])
-    need_r16 = used(6, 7) or (not mfma16 and used(4))
-    need_r32 = used(8, 9, 10, 11) or (not mfma32 and used(5))
-    merged = need_r16 and need_r32
-
-    def family(entries, skip=()):
-        return {s: -(-int(n[s]) // vb) for s, vb in entries if s not in skip and n[s]}
-
-    skip = ((5,) if mfma32 else ()) + ((4,) if mfma16 else ())
-    plan = {}
-    if used(18, 19, 20):
-        per = family(FAMILY_A[coeff_type])
-        plan["a"] = Launch(sum(per.values()), min(grid_a, big or caps["big_cap"]) if merged else grid_a, per)
-    if merged:
-        per = family(FAMILY_R, skip)
-        plan["r"] = Launch(sum(per.values()), grid_r16, per)
-    elif need_r16:
-        per = family(FAMILY_R16, skip)
-        plan["r16"] = Launch(sum(per.values()), grid_r16, per)
-    elif need_r32:
-        per = family(FAMILY_R32, skip)
-        plan["r32"] = Launch(sum(per.values()), grid_r32, per)
-    if mfma32 and used(5):
-        plan["mfma32"] = Launch(n[5], 4 * min(cells // 16 // 4 + 1, caps["mfma32"]), {5: int(n[5])})
-    if mfma16 and used(4):
-        plan["mfma16"] = Launch(n[4], 4 * min(cells // 4 // 4 + 1, caps["mfma16"]), {4: int(n[4])})
-    if cells >= 256 and used(21, 22, 23, 24, 25, 26):
-        per = {s: int(n[s]) for s in range(21, 27) if n[s]}
-        plan["large"] = Launch(sum(per.values()), grid_l, per)
-    plan["merged"] = merged
-    return plan
+# ---- the launch rule, restated: tests/phase1_plan.py (held to libjxl_amd/csrc/phase1_plan.h by test_phase1_launch_plan.py)
+from phase1_plan import CAPS, FAMILY_A, FAMILY_R, FAMILY_R16, FAMILY_R32, Launch, launch_plan, strategy_counts  # noqa: E402,F401
 
 
 def require_turns(launch, every=None, third=None, what=""):

@@ -1,71 +1,120 @@
-"""CPU checks of the launch rule restated in tests/test_gpu_phase1_loops.py (launch_plan, CAPS): the caps are the ones
-in the source text of LaunchBlocksT and LaunchMfma32 / LaunchMfma16, and the cases' "really loops" assertions fail when a
-cap exceeds the unit count -- so a retuned cap cannot quietly turn the loop tests into one-turn tests."""
+"""CPU checks of the launch rule of phase 1.  libjxl_amd/csrc/phase1_plan.h is the rule; tests/fuzz/check_phase1_plan.cc
+includes it into a stand-alone program built with -fsanitize=address,undefined, which checks that RoleOf deals every
+role of the merged launch exactly once and that every plan's grid is the sum of its parts, and prints the caps, the
+family tables and the plan of any frame.  The restatement the GPU tests use (tests/phase1_plan.py: CAPS, FAMILY_*,
+launch_plan) is held to that output; and the cases' "really loops" assertions fail when a cap exceeds the unit count --
+so a retuned cap cannot quietly turn the loop tests into one-turn tests."""
+import itertools
 import os
-import re
+import subprocess
 
 import numpy as np
 import pytest
 
 from libjxl_amd import synth
+import phase1_plan as plan
 import test_gpu_phase1_loops as loops
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "libjxl_amd", "csrc")
 
 
-def function_text(path, name):
-    """The definition of `name` (a function at namespace scope, closing brace in column 0)."""
-    text = open(os.path.join(CSRC, path)).read()
-    m = re.search(r"^(?:static )?void %s\([^;{]*\{.*?^\}" % name, text, re.S | re.M)
-    assert m, "%s not found in %s" % (name, path)
-    return m.group(0)
+@pytest.fixture(scope="module")
+def checker(tmp_path_factory):
+    """run(text) -> (stdout, stderr) of the compiled checker, which has passed its own sweeps."""
+    out = str(tmp_path_factory.mktemp("phase1_plan") / "check_phase1_plan")
+    cmd = ["g++", "-O1", "-g", "-std=c++17", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined",
+           "-fno-omit-frame-pointer", os.path.join(ROOT, "tests", "fuzz", "check_phase1_plan.cc"), "-o", out]
+    r = subprocess.run(cmd, capture_output=True, text=True)
+    assert r.returncode == 0, r.stderr[-3000:]
+    env = dict(os.environ, ASAN_OPTIONS="detect_leaks=1:abort_on_error=0", UBSAN_OPTIONS="print_stacktrace=1")
+
+    def run(text=""):
+        r = subprocess.run([out], input=text, capture_output=True, text=True, env=env, timeout=300)
+        assert r.returncode == 0, (r.stdout[-500:], r.stderr[-4000:])
+        return r.stdout, r.stderr
+    return run
 
 
-def one(pattern, text, what):
-    found = re.findall(pattern, text)
-    assert len(found) == 1, "%s: %r matches %d times -- update the pattern here and CAPS in test_gpu_phase1_loops.py" % (
-        what, pattern, len(found))
-    return int(found[0])
+@pytest.fixture(scope="module")
+def tables(checker):
+    out, err = checker()
+    return dict(line.split("=") for line in out.split()), dict(kv.split("=") for kv in err.split())
 
 
-def test_caps_of_the_loop_tests_are_the_ones_in_the_launchers():
-    """CAPS of tests/test_gpu_phase1_loops.py == the grid caps in the source.  If this fails after a cap was retuned:
-    update CAPS there, and re-derive the turn counts in that module's docstring and DESIGN.md section 6."""
-    blocks = function_text("kernels_blocks.hip", "LaunchBlocksT")
-    m32 = function_text("kernels_mfma.hip", "LaunchMfma32")
-    m16 = function_text("kernels_mfma.hip", "LaunchMfma16")
-    source = dict(
-        grid_a=one(r"grid_a = units \+ 3 < (\d+)u \? units \+ 3 : \1u;", blocks, "grid_a"),
-        grid_r16=one(r"grid_r16 = units \+ 3 < (\d+)u \? units \+ 3 : \1u;", blocks, "grid_r16"),
-        grid_r32=one(r"grid_r32 = units / 2 \+ 5 < (\d+)u \? units / 2 \+ 5 : \1u;", blocks, "grid_r32"),
-        grid_l=one(r"grid_l = cells / 128 < (\d+)u \? \(cells / 128 \? cells / 128 : 1\) : \1u;", blocks, "grid_l"),
-        big_cap=one(r"big_cap = big_set \? \(uint32_t\)big_env : (\d+)u;", blocks, "big_cap"),
-        mfma32=one(r"grid = cells / 16 / 4 \+ 1;[^\n]*\n\s*if \(grid > (\d+)u\) grid = \1u;", m32, "LaunchMfma32"),
-        mfma16=one(r"grid = cells / 4 / 4 \+ 1;[^\n]*\n\s*if \(grid > (\d+)u\) grid = \1u;", m16, "LaunchMfma16"))
-    assert source == loops.CAPS, "retuned cap: update CAPS in tests/test_gpu_phase1_loops.py (source %r)" % (source,)
+def test_roles_and_grids_under_asan_ubsan(tables):
+    """The checker's own sweeps ran (they end the program on the first failure): every role index of the merged launch
+    dealt exactly once over 5 x 5 x 7 x 6 geometries, the merged grid the sum of its parts over 34020 plans."""
+    _, swept = tables
+    assert int(swept["roles"]) >= 5 * 5 * 7 * 6 * 2 and int(swept["plans"]) >= 34020
+
+
+def test_caps_of_the_loop_tests_are_the_ones_in_the_launchers(tables):
+    """CAPS of tests/phase1_plan.py == the grid caps of phase1_plan.h.  If this fails after a cap was retuned: update
+    CAPS there, and re-derive the turn counts in test_gpu_phase1_loops.py's docstring and DESIGN.md section 6."""
+    printed, _ = tables
+    source = {k: int(printed[k]) for k in plan.CAPS}
+    assert source == loops.CAPS, "retuned cap: update CAPS in tests/phase1_plan.py (source %r)" % (source,)
     # the knobs: [1, 4096], anything else the built-in value; units = cells / 64
-    assert one(r"big_set = big_env >= 1 && big_env <= (\d+);", blocks, "JXLHIP_BIG_WGS range") == 4096
-    assert one(r"if \(r_env >= 1 && r_env <= (\d+)\)", blocks, "JXLHIP_R_WGS range") == 4096
-    assert one(r"const uint32_t units = cells / (\d+);", blocks, "units") == 64
+    assert int(printed["knob_max"]) == 4096 and int(printed["unit_cells"]) == 64
+    assert int(printed["mfma16_min_pixels"]) == 16 << 20
 
 
-def test_unit_tables_are_the_family_tables_of_the_kernels():
-    text = open(os.path.join(CSRC, "kernels_blocks.hip")).read()
-    medium = re.search(r"kMediumStrategy\[\w*\]\s*=\s*\{([^}]*)\}", open(os.path.join(CSRC, "dev_common.h")).read())
-    assert medium, "kMediumStrategy not found"
-    strategy = [int(v) for v in medium.group(1).split(",")]
+def test_unit_tables_are_the_family_tables_of_the_kernels(tables):
+    printed, _ = tables
 
     def table(name):
-        m = re.search(r"FamilyEntry %s\[\d+\] = \{(.*?)\};" % name, text, re.S)
-        assert m, name
-        return [(strategy[int(i)], int(vb)) for i, vb in re.findall(r"\{kClsMedium0 \+ (\d+), (\d+)\}", m.group(1))]
+        return [tuple(int(v) for v in e.split(":")) for e in printed[name].split(",")]
 
     assert table("kFamilyA1") == loops.FAMILY_A[0]
     assert table("kFamilyA") == loops.FAMILY_A[1]
     assert table("kFamilyR") == loops.FAMILY_R
     assert table("kFamilyR16") == loops.FAMILY_R16
     assert table("kFamilyR32") == loops.FAMILY_R32
+
+
+def _counts(mix, xsize, ysize):
+    """Strategy counts of a frame that holds every strategy of `mix` (launch_plan and PlanPhase1 read only which are
+    there; the numbers follow the area shares)."""
+    covered = np.array(synth.COVERED_X, np.int64) * np.array(synth.COVERED_Y, np.int64)
+    blocks = ((xsize + 7) // 8) * ((ysize + 7) // 8)
+    n = np.zeros(27, np.int64)
+    for s, share in mix.items():
+        n[s] = max(1, int(blocks * share / sum(mix.values())) // int(covered[s]))
+    return n
+
+
+def test_launch_plan_agrees_with_the_compiled_plan(checker):
+    """launch_plan() == PlanPhase1 over PickMfma on `merged`, on which launches happen and on every worker count."""
+    hand = {18: 5, 19: 3, 6: 40, 8: 20}   # test_launch_plan_on_a_map_counted_by_hand
+    mixes = [{s: 1} for s in range(27)] + [loops.MIX_A, loops.MIX_B, loops.MIX_C, loops.MIX_C16, loops.MIX_C32,
+                                          loops.real4k_mix(), hand]
+    knobs = (None, 1, 2, 4096, 5000)
+    cases, lines = [], []
+    for mix, (xs, ys) in itertools.product(mixes, ((264, 264), (520, 300), (1000, 776), (4096, 4096))):
+        n = _counts(mix, xs, ys)
+        used = sum(1 << s for s in range(27) if n[s])
+        cells = ((xs + 255) // 256) * ((ys + 255) // 256) * 1024
+        for ct, mfma, big, r in itertools.product((0, 1), (None, 0, 1), knobs, knobs):
+            cases.append((n, xs, ys, ct, big, r, mfma))
+            lines.append("%d %d %d 0 %d %d %d %d %d" % (
+                cells, used, ct, (xs + 7) // 8, xs * ys, -1 if mfma is None else mfma,
+                plan.KNOB_UNSET if big is None else big, plan.KNOB_UNSET if r is None else r))
+    out, _ = checker("\n".join(lines) + "\n")
+    answers = out.splitlines()
+    assert len(answers) == len(cases) == 34 * 4 * 2 * 3 * 25
+    for (n, xs, ys, ct, big, r, mfma), line in zip(cases, answers):
+        c = {k: int(v) for k, v in (kv.split("=") for kv in line.split())}
+        p = plan.launch_plan(n, xs, ys, ct, big_wgs=big, r_wgs=r, mfma=mfma)
+        used = lambda *ss: any(n[s] for s in ss)  # noqa: E731
+        assert (bool(c["pick32"]), bool(c["pick16"])) == plan.pick_mfma(used, xs * ys, None if mfma is None else bool(mfma))
+        want = {"merged": p["merged"]}
+        want.update({k: v.workers for k, v in p.items() if k != "merged"})
+        got = {"merged": c["r"] != 0}
+        got.update({k: v for k, v in (("a", c["big_wgs"] if c["r"] else c["a"]), ("r", c["r_wgs"]), ("r16", c["r16"]),
+                                      ("r32", c["r32"]), ("large", c["large"]), ("mfma32", 4 * c["mfma32"]),
+                                      ("mfma16", 4 * c["mfma16"])) if v})
+        assert got == want, (line, (xs, ys, ct, big, r, mfma), p)
+        assert c["r"] == c["special_wgs"] + c["big_wgs"] + c["r_wgs"] + c["dct8_wgs"]
 
 
 def test_launch_plan_on_a_map_counted_by_hand():
