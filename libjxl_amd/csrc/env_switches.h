@@ -20,7 +20,7 @@ struct Switches {
   // Sampled when a context is created (jxlhip_create_ex reloads), never on a launch.
   static constexpr int kUnset = -2147483647 - 1;
   std::atomic<int> fused_pc_rh{0};          // JXLHIP_FUSED_PC_RH: rows per window chunk (0 = fill the device)
-  std::atomic<int> filter_rh{0};            // JXLHIP_FILTER_RH: rows per wave of the two-phase filter march (0 = fill the device)
+  std::atomic<int> filter_rh{0};            // JXLHIP_FILTER_RH: rows per wave of the two-phase filter marches, k_filters_fast and k_epf0 (0 = fill the device)
   std::atomic<int> big_wgs{kUnset};         // JXLHIP_BIG_WGS: workgroups of the 64-point family (k_transform_r, k_transform_a)
   std::atomic<int> r_wgs{kUnset};           // JXLHIP_R_WGS: workgroups of the row-per-lane families (k_transform_r, _r16, _r32)
   std::atomic<bool> multi_force_gather{false};  // JXLHIP_MULTI_FORCE_GATHER: one-device boxes exercise the gather copies

@@ -198,7 +198,8 @@ __global__ __launch_bounds__(256, EPF == 2 ? 2 : 3) void k_filters_fast(DevFrame
 
 // Rows per wave: ChunkRows (kernels.h) over every height from 16 to 512 with two workgroups resident per compute unit;
 // a wave costs RH + 2 * HX row steps plus ~6 of prologue.  JXLHIP_FILTER_RH (sampled when a context is created,
-// env_switches.h) overrides.
+// env_switches.h) overrides, here and in LaunchEpf0 (kernels_epf0.hip): at three EPF iterations both marches are cut
+// at the forced height.
 template <int GAB, int EPF, int OUTK, int FMT = -1>
 void LaunchFastT(const DevFrame& f, const FilterParams& p, hipStream_t st) {
   using G = FastGeom<GAB, EPF>;

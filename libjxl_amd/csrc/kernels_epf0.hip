@@ -24,6 +24,7 @@
 // ~230 VALU issues per row step and wave (pair of columns per lane, packed fp32).
 #include <stdlib.h>
 
+#include "env_switches.h"
 #include "epf0_march.h"
 
 namespace jxlhip {
@@ -135,7 +136,9 @@ bool LaunchEpf0(const DevFrame& f, const FilterParams& p, int gab, float* const 
   constexpr int USE = Geom0<1>::USE;
   const unsigned strips = (f.xsize + USE - 1) / USE;
   const unsigned wgx = (strips + 3) / 4;
-  const int RH = ChunkRows(wgx, oy1 - oy0, DeviceCus() * 2u, 16, 512, 1, 2 * (3 + gab) + 6);  // two workgroups per CU
+  // two workgroups per CU; JXLHIP_FILTER_RH overrides, as in LaunchFastT (filters_fast.h)
+  const int forced = jxlhip_env::Get().filter_rh.load(std::memory_order_relaxed);
+  const int RH = forced > 0 ? forced : ChunkRows(wgx, oy1 - oy0, DeviceCus() * 2u, 16, 512, 1, 2 * (3 + gab) + 6);
   const dim3 grid(wgx, (oy1 - oy0 + RH - 1) / RH);
   if (gab) hipLaunchKernelGGL((k_epf0<1>), grid, dim3(256), 0, st, f, p, RH, oy0, oy1, dst[0], dst[1], dst[2]);
   else hipLaunchKernelGGL((k_epf0<0>), grid, dim3(256), 0, st, f, p, RH, oy0, oy1, dst[0], dst[1], dst[2]);
