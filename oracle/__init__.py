@@ -532,15 +532,36 @@ def ref_quant_dc_contexts(quant_dc):
 Frame.encode_ac_ref = _encode_ac_ref
 
 
-def feature_stream(feature, xsize=600, ysize=400, seed=5, distance=1.0):
+def feature_stream(feature, xsize=600, ysize=400, seed=5, distance=1.0, resampling=None, custom_weights_seed=None,
+                   noise_lut=None, gain=None):
     """A small codestream written by the REFERENCE ENCODER (oracle/ref_real_stream.cc: FeatureStream) that uses one
     feature the product's seam declines or handles specially: "noise" | "splines" | "patches" | "modular" | "animation" |
-    "progressive" | "plain" (the control).  Describes an 8-bit sRGB original.  Test infrastructure."""
+    "progressive" | "plain" (the control).  Describes an 8-bit sRGB original.  Test infrastructure.
+
+    Four knobs, each absent by default (the bytes are then the ones this function always wrote):
+      resampling           1, 2, 4 or 8: the encoder downsamples by that factor and writes FrameHeader::upsampling
+      custom_weights_seed  custom_weights_mask = 7: the three default tables jittered by +-0.02, rounded to F16
+      noise_lut            8 floats: the frame's noise LUT (CompressParams::manual_noise), coded in 10 bits each
+      gain                 the original is multiplied by this before it is encoded"""
     L = ref_lib()
-    L.jxr_feature_stream.restype = C.c_size_t
-    L.jxr_feature_stream.argtypes = [C.c_uint32, C.c_uint32, C.c_uint32, C.c_float, C.c_char_p, C.c_void_p, C.c_size_t]
+    assert resampling in (None, 1, 2, 4, 8), resampling
     buf = C.create_string_buffer(max(1 << 20, 4 * xsize * ysize))
-    n = L.jxr_feature_stream(xsize, ysize, seed, distance, feature.encode(), buf, len(buf))
+    if resampling is None and custom_weights_seed is None and noise_lut is None and gain is None:
+        # the entry point these streams always came through (a prebuilt library from before the knobs has it too)
+        L.jxr_feature_stream.restype = C.c_size_t
+        L.jxr_feature_stream.argtypes = [C.c_uint32, C.c_uint32, C.c_uint32, C.c_float, C.c_char_p, C.c_void_p, C.c_size_t]
+        n = L.jxr_feature_stream(xsize, ysize, seed, distance, feature.encode(), buf, len(buf))
+    else:
+        L.jxr_feature_stream_knobs.restype = C.c_size_t
+        L.jxr_feature_stream_knobs.argtypes = [C.c_uint32, C.c_uint32, C.c_uint32, C.c_float, C.c_char_p, C.c_int,
+                                               C.c_int, C.c_void_p, C.c_float, C.c_void_p, C.c_size_t]
+        lut = None
+        if noise_lut is not None:
+            assert len(noise_lut) == 8
+            lut = (C.c_float * 8)(*noise_lut)
+        n = L.jxr_feature_stream_knobs(xsize, ysize, seed, distance, feature.encode(), resampling or 0,
+                                       -1 if custom_weights_seed is None else int(custom_weights_seed), lut,
+                                       1.0 if gain is None else gain, buf, len(buf))
     if not n:
         raise ValueError("reference encoder failed for feature %r" % feature)
     return buf.raw[:n]

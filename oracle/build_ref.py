@@ -10,6 +10,7 @@ enc_adaptive_quantization.cc:840-919) on in-memory coefficients.
 Used only by tests/ and bench.py's cpu_baseline as a checker.  /root/reference
 exists only in the build container: on the GPU box the prebuilt .so travels.
 """
+import hashlib
 import os
 import re
 import subprocess
@@ -59,11 +60,21 @@ def _compile(job):
     vec = os.sep + "obj_v8" + os.sep in obj and any(src.endswith(u) for u in V8_UNITS)
     if vec:
         deps.append(os.path.join(SHIM_V, "hwy", "highway.h"))
-    if os.path.exists(obj) and all(os.path.getmtime(obj) > os.path.getmtime(d) for d in deps):
+    # the drivers are this repository's own and change with it: their objects are also tied to the source's CONTENT
+    # (an object directory kept from another checkout can be newer than a file that git has just written)
+    stamp, digest = obj + ".sha256", None
+    if src.startswith(HERE):
+        with open(src, "rb") as f:
+            digest = hashlib.sha256(f.read()).hexdigest()
+    same = digest is None or (os.path.exists(stamp) and open(stamp).read() == digest)
+    if same and os.path.exists(obj) and all(os.path.getmtime(obj) > os.path.getmtime(d) for d in deps):
         return obj, ""
     extra = ["-I" + HERE] if src.startswith(HERE) else []
     flags = ["-I" + SHIM_V] + FLAGS if vec else FLAGS  # (the vector highway.h in front of the single-lane one)
     r = subprocess.run([CXX] + flags + extra + ["-c", src, "-o", obj], capture_output=True, text=True)
+    if r.returncode == 0 and digest is not None:
+        with open(stamp, "w") as f:
+            f.write(digest)
     return (obj if r.returncode == 0 else None), r.stderr
 
 

@@ -593,8 +593,24 @@ void FillPage(Image3F* img, uint32_t seed) {  // a flat page with rows of repeat
   }
 }
 
+// What a test may ask of the encoder beyond the feature; the defaults leave the stream's bytes as they were.
+struct StreamKnobs {
+  int resampling = 0;            // 1, 2, 4, 8: CompressParams::resampling and ec_resampling (0 = the encoder's choice)
+  int custom_weights_seed = -1;  // >= 0: custom_weights_mask = 7, the three default tables jittered by +-0.02
+  const float* noise_lut = nullptr;  // 8 entries: CompressParams::manual_noise
+  float gain = 1.0f;             // the original is multiplied by this before encoding
+};
+
+// the nearest value F16Coder can write (11 significant bits; multiples of 2^-24 below the normal range)
+float RoundToF16(float v) {
+  int ex;
+  const float m = std::frexp(v, &ex);
+  const int shift = std::max(ex - 11, -24);
+  return std::ldexp(std::nearbyint(std::ldexp(m, ex - shift)), shift);
+}
+
 Status FeatureStream(uint32_t xs, uint32_t ys, uint32_t seed, float distance, const char* feature,
-                     std::vector<uint8_t>* out) {
+                     const StreamKnobs& knobs, std::vector<uint8_t>* out) {
   const std::string f = feature;
   JxlMemoryManager mm;
   JXL_RETURN_IF_ERROR(MemoryManagerInit(&mm, nullptr));
@@ -614,9 +630,25 @@ Status FeatureStream(uint32_t xs, uint32_t ys, uint32_t seed, float distance, co
   }
   // the lossy encoder is handed linear pixels under a "linear sRGB" copy of the metadata (no CMS in this build, as in
   // Run above); the lossless one takes the 8-bit samples as they are, in the original's own encoding
+  if (knobs.custom_weights_seed >= 0) {  // written as F16 (CustomTransformData::VisitFields): round first
+    CustomTransformData& td = metadata.transform_data;
+    td.custom_weights_mask = 7;
+    uint32_t s = static_cast<uint32_t>(knobs.custom_weights_seed) * 747796405u + 2891336453u;
+    auto jitter = [&](float* w, size_t n) {
+      for (size_t i = 0; i < n; i++) {
+        s = s * 1664525u + 1013904223u;
+        w[i] = RoundToF16(w[i] + 0.04f * ((s >> 8) / 16777216.0f - 0.5f));
+      }
+    };
+    jitter(td.upsampling2_weights, 15);
+    jitter(td.upsampling4_weights, 55);
+    jitter(td.upsampling8_weights, 210);
+  }
   CodecMetadata metadata_enc = metadata;
   if (!modular) metadata_enc.m.color_encoding = ColorEncoding::LinearSRGB(false);
   CompressParams cparams;
+  if (knobs.resampling > 0) cparams.resampling = cparams.ec_resampling = knobs.resampling;
+  if (knobs.noise_lut) cparams.manual_noise.assign(knobs.noise_lut, knobs.noise_lut + NoiseParams::kNumNoisePoints);
   cparams.butteraugli_distance = distance;
   cparams.speed_tier = SpeedTier::kSquirrel;
   cparams.patches = Override::kOff;
@@ -665,6 +697,13 @@ Status FeatureStream(uint32_t xs, uint32_t ys, uint32_t seed, float distance, co
     JXL_ASSIGN_OR_RETURN(Image3F img, Image3F::Create(&mm, xs, ys));
     if (f == "patches") FillPage(&img, seed);
     else FillImage(&img, seed + 31u * fi);
+    if (knobs.gain != 1.0f) {
+      for (int c = 0; c < 3; c++)
+        for (size_t y = 0; y < ys; y++) {
+          float* r = img.PlaneRow(c, y);
+          for (size_t x = 0; x < xs; x++) r[x] *= knobs.gain;
+        }
+    }
     if (modular) {  // 8-bit samples of an sRGB original: quantise, so that "lossless" has integers to keep
       for (int c = 0; c < 3; c++)
         for (size_t y = 0; y < ys; y++) {
@@ -685,13 +724,24 @@ Status FeatureStream(uint32_t xs, uint32_t ys, uint32_t seed, float distance, co
 }  // namespace
 
 // -> bytes written (0 = failed, or `cap` too small: call again with the returned size... the streams are < 1 MB)
-JXR_EXPORT size_t jxr_feature_stream(uint32_t xs, uint32_t ys, uint32_t seed, float distance, const char* feature,
-                                     uint8_t* out, size_t cap) {
+// resampling 0, custom_weights_seed < 0, noise_lut null and gain 1 are "not asked for" (StreamKnobs above)
+JXR_EXPORT size_t jxr_feature_stream_knobs(uint32_t xs, uint32_t ys, uint32_t seed, float distance, const char* feature,
+                                           int resampling, int custom_weights_seed, const float* noise_lut, float gain,
+                                           uint8_t* out, size_t cap) {
+  StreamKnobs knobs;
+  knobs.resampling = resampling;
+  knobs.custom_weights_seed = custom_weights_seed;
+  knobs.noise_lut = noise_lut;
+  knobs.gain = gain;
   std::vector<uint8_t> bytes;
-  if (!FeatureStream(xs, ys, seed, distance, feature, &bytes)) return 0;
+  if (!FeatureStream(xs, ys, seed, distance, feature, knobs, &bytes)) return 0;
   if (bytes.size() > cap) return 0;
   memcpy(out, bytes.data(), bytes.size());
   return bytes.size();
+}
+JXR_EXPORT size_t jxr_feature_stream(uint32_t xs, uint32_t ys, uint32_t seed, float distance, const char* feature,
+                                     uint8_t* out, size_t cap) {
+  return jxr_feature_stream_knobs(xs, ys, seed, distance, feature, 0, -1, nullptr, 1.0f, out, cap);
 }
 
 JXR_EXPORT void* jxr_real_case_create(uint32_t xs, uint32_t ys, uint32_t seed, float distance, int speed_tier,

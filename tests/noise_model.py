@@ -97,7 +97,8 @@ def convolve(plane):
     return _fma(others, F32(0.16), at(0, 0) * F32(-3.84))
 
 
-def strength(lut, x):
+def strength(lut, x, clamp=True):
+    """NoiseStrength; clamp=False leaves out its final clamp to [0, 1] (for tests that count where it decides)."""
     lut = np.asarray(lut, np.float32)
     scaled = np.maximum(F32(0), x * F32(6))
     fl = np.floor(scaled)
@@ -108,7 +109,7 @@ def strength(lut, x):
     i = fl.astype(np.int64)
     lo, hi = lut[i], lut[i + 1]
     v = _fma(hi - lo, fr, lo)
-    return np.clip(v, 0, 1).astype(np.float32)
+    return np.clip(v, 0, 1).astype(np.float32) if clamp else v
 
 
 def add_noise(xyb, lut, ytox, ytob, visible=1, nonvisible=0):

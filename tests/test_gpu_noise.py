@@ -4,7 +4,13 @@
     jxlhip_decode_codestream against the reference's public JxlDecoder (oracle/_ref/libjxl_dec_ref.so);
   - the kernels alone on synthetic frames: (noise on) == numpy restatement of RNG + ConvolveNoise + AddNoise applied
     to the (noise off) XYB planes (tests/noise_model.py), over every stage list and both routings (two-phase, fused);
-  - packed output with alpha, the silent LUT, a context reused after a noise frame, and the refused configurations."""
+  - packed output with alpha, the silent LUT, a context reused after a noise frame, and the refused configurations;
+  - genuine streams with a CHOSEN LUT (not monotone, one entry zero), plain and behind 4x upsampling, and of an original
+    bright enough to fill the LUT's upper intervals and the branch at 7 and beyond (tests/stream_chain.py; their CPU
+    twins, with the populations and the fault injection, are tests/test_render_stage_streams.py);
+  - the kernel against the model on planted frames (tests/planted_frames.py) whose (y - x) / 2 and (y + x) / 2 sit below
+    zero, on both sides of every knot, inside every interval and above 7 / 6, under a LUT with entries outside [0, 1]:
+    every branch of NoiseStrength, both ends of its clamp included, with the counts asserted on the device's planes."""
 import ctypes as C
 
 import numpy as np
@@ -13,6 +19,8 @@ import pytest
 from libjxl_amd import abi, synth
 
 import noise_model
+import planted_frames as pf
+import stream_chain as sc
 
 TIGHT = 2e-5
 LUT = [0.05, 0.12, 0.3, 0.45, 0.6, 0.75, 0.9, 1.0]
@@ -83,6 +91,46 @@ def test_noise_stream_matches_jxldecoder(L, ref, jxl_ref, size, distance, worker
             R.JxlThreadParallelRunnerDestroy(pool)
 
 
+@pytest.fixture(scope="module")
+def chosen(jxl_ref):
+    """name -> (the committed stream, JxlDecoder's picture) of stream_chain.NOISE_STREAMS: decoded once, never
+    modified.  (tests/test_render_stage_streams.py holds the committed files to what the reference encoder writes.)"""
+    ts, RL = jxl_ref
+    done = {}
+
+    def get(name):
+        if name not in done:
+            cs = sc.golden_stream(name)
+            want = ts.jxl_decode(RL, cs)
+            want.setflags(write=False)
+            done[name] = (cs, want)
+        return done[name]
+    return get
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("workers", [0, 6])
+@pytest.mark.parametrize("name", list(sc.NOISE_STREAMS))
+def test_chosen_lut_stream_matches_jxldecoder(L, chosen, name, workers):
+    """The LUT of stream_chain.NOISE_LUT: in gamut (intervals 0..2) at 2e-5, plain and at output size
+    behind 4x upsampling; the original times 30 (intervals 3..6 and the branch at 7 and beyond), plain and behind 2x, at
+    stream_chain.BRIGHT_BAR -- a bar from the CPU tier, not from this kernel.  Measured on an MI355X: noise 1.84e-5,
+    noise_n4 1.69e-5, bright 5.5e-5, bright_n2 7.2e-5 (0 and 6 workers alike).  The device's planes are within 1.5 ulp of
+    the model's; dark, saturated samples, which strong noise makes, carry such an ulp to 1e-5 of the range through the
+    colour conversion (DESIGN.md section 6 says how the LUT's amplitude was chosen with that in view)."""
+    from test_gpu_upsampling import _decode_stream
+    kw = sc.NOISE_STREAMS[name]
+    cs, want = chosen(name)
+    xs, ys = kw["xsize"], kw["ysize"]
+    assert want.shape == (ys, xs, 3)
+    got = _decode_stream(L, cs, xs, ys, workers, abi.SAMPLE_F32, 3, ups=kw.get("resampling", 1))
+    bar = sc.BRIGHT_BAR if name.startswith("bright") else TIGHT
+    scale = max(1.0, float(np.abs(want).max()))
+    err = float(np.abs(got - want).max()) / scale
+    print("NOISE-GPU %s workers %d: max|diff| / scale = %.3e (scale %.3f, bar %.1e)" % (name, workers, err, scale, bar))
+    assert err <= bar
+
+
 def _decode(dec, params, t, dq, noise=None, alpha=None):
     dec.begin_frame(params)
     dec.set_inputs(t, dq)
@@ -117,6 +165,44 @@ def test_noise_kernel_matches_the_numpy_restatement(xs, ys, gab, epf, vis):
     want = noise_model.add_noise(off, LUT, 0.0625, params["cfl_base_b"], visible=vis)
     assert np.abs(on - off).max() > 1e-3  # the noise is there
     err = float(np.abs(on - want).max())
+    assert err <= 1e-5, err
+
+
+# (xsize, ysize, visible, nonvisible frame index): one group; the group seams; both indices in the seed
+PLANTED_CASES = [(128, 64, 1, 0), (300, 520, 2, 0), (61, 70, 3, 2), (61, 70, 1, 5)]
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("xs,ys,vis,nonvis", PLANTED_CASES)
+def test_every_branch_of_noise_strength_on_planted_frames(xs, ys, vis, nonvis):
+    """Reaches, and would fail without: max(0, .) (arguments below zero), each of the six selects and both LUT entries
+    of every interval (values on both sides of every knot and inside every interval), scaled >= 7 (values on both sides
+    of 7 / 6 and far above), and both ends of the clamp to [0, 1] (LUT entries -0.2, -0.1, 1.2, 1.3)."""
+    from libjxl_amd import VarDctDecoder
+    params, t = pf.noise_frame(xs, ys, device="cuda")
+    params["cfl_base_x"] = 0.0625
+    lut = pf.NOISE_CLAMP_LUT
+    dec = VarDctDecoder(0)
+    try:
+        dq = dec.default_dequant_tables()
+        off = _decode(dec, params, t, dq)
+        on = _decode(dec, params, t, dq, noise=(lut, vis, nonvis))
+    finally:
+        dec.close()
+    # the population, on the device's own noise-free planes: a block is 64 pixels
+    for what, counts in pf.noise_population(off).items():
+        assert min(counts) >= 64, (what, counts)
+    # ... and from the model: each end of the clamp decides
+    for v in ((off[1] - off[0]) * np.float32(0.5), (off[1] + off[0]) * np.float32(0.5)):
+        raw = noise_model.strength(lut, v, clamp=False)
+        assert int((raw < 0).sum()) >= 64 and int((raw > 1).sum()) >= 64
+        assert np.abs(noise_model.strength(lut, v) - raw).max() > 0.1
+    want = noise_model.add_noise(off, lut, 0.0625, params["cfl_base_b"], visible=vis, nonvisible=nonvis)
+    assert np.abs(on - off).max() > 1e-3  # the noise is there
+    if nonvis:  # ... and the second index is in the seed
+        assert np.abs(want - noise_model.add_noise(off, lut, 0.0625, params["cfl_base_b"], visible=vis)).max() > 1e-3
+    err = float(np.abs(on - want).max())
+    print("NOISE-PLANTED %dx%d frame indices (%d, %d): max|diff| = %.3e" % (xs, ys, vis, nonvis, err))
     assert err <= 1e-5, err
 
 

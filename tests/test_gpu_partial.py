@@ -5,7 +5,8 @@
   (d) one byte short of the end                (e) not at all
 and the progressive one also behind pass 0 of every group and inside a section of pass 1; as float RGB within 2e-5 of
 the reference (normalised as in tests/test_gpu_patches.py, no pixel left out) and as 8-bit sRGB within one level,
-with 0 and 6 workers.  (e) equals jxlhip_decode_codestream bit for bit.  Then display orientation, and the refusals."""
+with 0 and 6 workers.  (e) equals jxlhip_decode_codestream bit for bit.  Then a file with custom upsampling weights (its
+own 8x table draws the DC-only groups), display orientation, and the refusals."""
 import ctypes as C
 
 import numpy as np
@@ -14,6 +15,7 @@ import pytest
 from libjxl_amd import abi
 
 import partial_ref as pr
+import stream_chain as sc
 
 TIGHT = 2e-5
 NEED_MORE_INPUT = -9
@@ -154,6 +156,39 @@ def test_partial_file_as_8_bit(L, dec, flushed, key, cut):
     err = float(np.abs(got.astype(np.float32) - want8).max())
     print("PARTIAL8 %s %dx%d cut %s: max level difference %g" % (key[0], key[1], key[2], cut, err))
     assert err <= 1.0
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("workers", [0, 6])
+def test_partial_file_with_custom_upsampling_weights(L, dec, ref, jxl_ref, workers):
+    """A 600x400 file that is NOT upsampled but carries custom upsampling weights (custom_weights_mask = 7), cut
+    behind AC global and in the middle of its AC groups: the DC-only groups are drawn with the file's own 8x table
+    (kernels_dc_upsample.hip), as JxlDecoderFlushImage draws them.  With the default table the picture is far off:
+    the same cut of the same image coded without custom weights differs by 10 bars and more."""
+    ts, RL = jxl_ref
+    kw = dict(xsize=600, ysize=400, seed=5, distance=1.0)
+    cs = sc.golden_stream("partial_custom")  # (= ref.feature_stream("plain", custom_weights_seed=3, **kw))
+    info = abi.CodestreamInfo()
+    assert L.jxlhip_codestream_basic_info(cs, len(cs), C.byref(info)) == 0 and info.upsampling == 1
+    plain = ref.feature_stream("plain", **kw)
+    assert len(cs) > len(plain)  # the three tables are in the image header
+    s, s_plain = pr.Sections(L, cs), pr.Sections(L, plain)
+    cuts, cuts_plain = _cuts(s, len(cs)), _cuts(s_plain, len(plain))
+    for cut in ("b", "c"):
+        n = cuts[cut]
+        ok, want = pr.flush(ts, RL, cs[:n])
+        assert ok and want.shape == (400, 600, 3) and not (want == pr.SENTINEL).any()
+        rc, got, pi = _decode(L, dec, cs, n, (400, 600), workers=workers)
+        assert rc == 0, L.jxlhip_last_error(dec.ctx)
+        assert pi.groups_dc_only > 0 and (pi.groups_dc_only < pi.num_groups) == (cut == "c")
+        scale = max(1.0, float(np.abs(want).max()))
+        err = float(np.abs(got - want).max()) / scale
+        print("PARTIAL custom weights cut %s workers %d (%d of %d groups DC only): max|diff| / scale = %.3e" % (
+            cut, workers, pi.groups_dc_only, pi.num_groups, err))
+        assert err <= TIGHT
+        if cut == "b":  # every group DC only, in both files
+            ok, other = pr.flush(ts, RL, plain[:cuts_plain[cut]])
+            assert ok and float(np.abs(want - other).max()) / scale >= 10 * TIGHT
 
 
 @pytest.mark.gpu

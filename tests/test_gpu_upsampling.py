@@ -6,8 +6,13 @@
     progressive;
   - the kernel alone on synthetic frames: (upsampling on) == tests/upsampling_model.py on the (upsampling off) XYB
     planes, for N = 2, 4, 8, default and custom weights, full and cropped output sizes, every output kind and both
-    routings, and with splines in front and noise behind it (tests/spline_model.py, tests/noise_model.py).  N = 4 and
-    8 have no genuine stream here: their evidence is the model, whose N = 2 path the genuine streams validate;
+    routings, and with splines in front and noise behind it (tests/spline_model.py, tests/noise_model.py);
+  - genuine streams beyond the encoder's own choice (oracle.feature_stream's resampling and custom_weights_seed,
+    tests/stream_chain.py; committed under tests/golden/render_stage_streams): N = 4 and 8 with the default tables, N = 2, 4 and 8 with custom ones, cropped and not, of
+    several sections and of one, against JxlDecoder; tests/test_render_stage_streams.py holds the model to the same
+    streams on the CPU and shows what a misread weight expansion or a missing clamp costs there;
+  - the kernel against the model on planted step edges (tests/planted_frames.py), where for every one of the N x N
+    output phases both ends of the clamp are asserted to decide;
   - a context reused after an upsampled frame, factor 1, and the refused configurations."""
 import ctypes as C
 
@@ -17,7 +22,9 @@ import pytest
 from libjxl_amd import abi, synth
 
 import noise_model
+import planted_frames as pf
 import spline_model as sm
+import stream_chain as sc
 import upsampling_model as um
 from test_splines_front_end import built_sets
 
@@ -56,7 +63,7 @@ def jxl_ref():
     return test_seam, test_seam.load(ref_so)
 
 
-def _decode_stream(L, cs, xs, ys, workers, sample, channels):
+def _decode_stream(L, cs, xs, ys, workers, sample, channels, ups=2):
     import torch
     from libjxl_amd import VarDctDecoder
     R = C.CDLL(abi.runner_library_path())
@@ -70,7 +77,7 @@ def _decode_stream(L, cs, xs, ys, workers, sample, channels):
         info = abi.CodestreamInfo()
         assert L.jxlhip_codestream_basic_info(cs, len(cs), C.byref(info)) == 0
         assert info.transfer_function == 13  # sRGB
-        assert (info.xsize, info.ysize, info.upsampling) == (xs, ys, 2)
+        assert (info.xsize, info.ysize, info.upsampling) == (xs, ys, ups)
         if sample == abi.SAMPLE_F32:
             fmt = abi.OutputFormat(abi.TF_SRGB, abi.SAMPLE_F32, channels, 32, 0, 0.0, info.luminances)
             out = torch.full((ys, xs, channels), -7.0, dtype=torch.float32, device="cuda")
@@ -83,7 +90,7 @@ def _decode_stream(L, cs, xs, ys, workers, sample, channels):
         rc = L.jxlhip_decode_codestream(dec.ctx, runner, pool, cs, len(cs), 2, C.byref(fmt), out.data_ptr(), stride,
                                         0, C.byref(got))
         assert rc == 0, L.jxlhip_last_error(dec.ctx)
-        assert (got.xsize, got.ysize, got.upsampling) == (xs, ys, 2)
+        assert (got.xsize, got.ysize, got.upsampling) == (xs, ys, ups)
         return out.cpu().numpy()
     finally:
         dec.close()
@@ -122,6 +129,53 @@ def test_upsampled_stream_as_8_bit(L, ref, jxl_ref, feature, size, distance, cha
     assert err <= 1.0
     if channels == 4:
         assert np.all(got[..., 3] == 255)  # no alpha channel: opaque
+
+
+@pytest.fixture(scope="module")
+def knob_streams(jxl_ref):
+    """name -> (the committed stream, JxlDecoder's picture) of stream_chain.UPSAMPLING_STREAMS: decoded once, never
+    modified.  (tests/test_render_stage_streams.py holds the committed files to what the reference encoder writes.)"""
+    ts, RL = jxl_ref
+    done = {}
+
+    def get(name):
+        if name not in done:
+            cs = sc.golden_stream(name)
+            want = ts.jxl_decode(RL, cs)
+            want.setflags(write=False)
+            done[name] = (cs, want)
+        return done[name]
+    return get
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("workers", [0, 6])
+@pytest.mark.parametrize("name", list(sc.UPSAMPLING_STREAMS))
+def test_4x_8x_and_custom_weight_streams_match_jxldecoder(L, knob_streams, name, workers):
+    """Reaches, and would fail without: the (ky, kx) indexing, the triangular index and the mirrored quarters of
+    UpsampleKernels at h = 2 and 4 (N = 4, 8), and the custom tables of all three factors from the image header to the
+    kernel (test_render_stage_streams.py: with the default tables instead these pictures are off by 10 bars and more)."""
+    kw = sc.UPSAMPLING_STREAMS[name]
+    cs, want = knob_streams(name)
+    xs, ys = kw["xsize"], kw["ysize"]
+    assert want.shape == (ys, xs, 3)
+    got = _decode_stream(L, cs, xs, ys, workers, abi.SAMPLE_F32, 3, ups=kw["resampling"])
+    scale = max(1.0, float(np.abs(want).max()))
+    err = float(np.abs(got - want).max()) / scale
+    print("UPS-GPU %s workers %d: max|diff| / scale = %.3e" % (name, workers, err))
+    assert err <= TIGHT
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("name", ["n2_custom", "n4_custom_crop", "n8_custom"])
+def test_custom_weight_streams_as_8_bit(L, knob_streams, name):
+    kw = sc.UPSAMPLING_STREAMS[name]
+    cs, ref_px = knob_streams(name)
+    want = np.round(np.clip(ref_px, 0.0, 1.0) * 255.0)
+    got = _decode_stream(L, cs, kw["xsize"], kw["ysize"], 0, abi.SAMPLE_U8, 3, ups=kw["resampling"])
+    err = float(np.abs(got.astype(np.float32) - want).max())
+    print("UPS-GPU8 %s: max level difference %g" % (name, err))
+    assert err <= 1.0
 
 
 # ---- the kernel against the model -----------------------------------------------------------------------------------
@@ -204,6 +258,39 @@ def test_upsample_kernel_matches_the_numpy_restatement(cw, ch, n, custom, crop):
     # packed: against the float output, as tests/test_gpu_splines.py does
     assert np.abs(out8[..., :3].astype(np.float32) - _srgb8(lin)).max() <= 1.6
     assert np.all(out8[..., 3] == 255)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("custom", [False, True])
+@pytest.mark.parametrize("n", [2, 4, 8])
+@pytest.mark.parametrize("cw,ch", [(61, 70), (7, 5)])
+def test_both_ends_of_the_clamp_on_planted_step_edges(cw, ch, n, custom):
+    """Step edges between two levels (rows, columns and a checkerboard of blocks; inside the one block of 7x5): the
+    kernels' negative lobes overshoot on both sides.  Asserted from the model before the comparison: in every one of
+    the N x N output phases the lower and the upper end of k_upsample's clamp each change a value (by more than ten
+    bars, not by a rounding), and without the clamp the model is 50 bars and more away."""
+    from libjxl_amd import VarDctDecoder
+    weights = _custom_weights(n, cw + n) if custom else None
+    params, t = pf.step_frame(cw, ch, device="cuda")
+    dec = VarDctDecoder(0)
+    try:
+        dq = dec.default_dequant_tables()
+        off = _decode(dec, params, t, dq)
+        on = _decode(dec, params, t, dq, ups=(n, (n * cw, n * ch), weights))
+    finally:
+        dec.close()
+    assert off.shape == (3, ch, cw) and on.shape == (3, n * ch, n * cw)
+    want = um.upsample(off, n, weights)
+    free = um.upsample(off, n, weights, clamp=False)
+    for oy in range(n):
+        for ox in range(n):
+            a, b = want[:, oy::n, ox::n], free[:, oy::n, ox::n]
+            assert (b < a - 1e-4).any() and (b > a + 1e-4).any(), (oy, ox)
+    assert np.abs(free - want).max() >= 50 * 1e-5
+    err = float(np.abs(on - want).max())
+    print("UPS-PLANTED coded %dx%d N=%d custom=%d: max|diff| = %.3e (the clamp moves %.3e)" % (
+        cw, ch, n, custom, err, float(np.abs(free - want).max())))
+    assert err <= 1e-5, err
 
 
 @pytest.mark.gpu

@@ -57,14 +57,16 @@ def _fma(a, b, c):
     return (np.asarray(a, np.float64) * np.asarray(b, np.float64) + np.asarray(c, np.float64)).astype(F32)
 
 
-def upsample(planes, n, weights=None, out_size=None):
+def upsample(planes, n, weights=None, out_size=None, kernel_table=None, clamp=True):
     """planes: [C, ch, cw] float32 at coded size -> [C, H, W] at out_size = (W, H) (default n * cw, n * ch), where
-    ceil(W / n) == cw and ceil(H / n) == ch: upsampled, then cropped."""
+    ceil(W / n) == cw and ceil(H / n) == ch: upsampled, then cropped.  kernel_table ([n * n, 25], in place of
+    kernels(n, weights)) and clamp=False are for tests that damage the model on purpose."""
     planes = np.asarray(planes, F32)
     nc, ch, cw = planes.shape
     W, H = out_size if out_size is not None else (n * cw, n * ch)
     assert -(-W // n) == cw and -(-H // n) == ch, (W, H, n, cw, ch)
-    k = kernels(n, default_weights(n) if weights is None else weights)
+    k = kernels(n, default_weights(n) if weights is None else weights) if kernel_table is None else kernel_table
+    assert k.shape == (n * n, 25) and k.dtype == F32
     ys = np.array([_mirror(i, ch) for i in range(-2, ch + 2)])
     xs = np.array([_mirror(i, cw) for i in range(-2, cw + 2)])
     p = planes[:, ys][:, :, xs]
@@ -81,5 +83,5 @@ def upsample(planes, n, weights=None, out_size=None):
                     acc[a] = _fma(taps[i + a], kk[i + a], acc[a])
             acc[0] = _fma(taps[24], kk[24], acc[0])
             r = (acc[1] + acc[2]) + acc[0]
-            out[:, oy::n, ox::n] = np.minimum(np.maximum(r, lo), hi)
+            out[:, oy::n, ox::n] = np.minimum(np.maximum(r, lo), hi) if clamp else r
     return out[:, :H, :W]
