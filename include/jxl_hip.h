@@ -604,6 +604,43 @@ JXLHIP_EXPORT int jxlhip_decode_frame_pinned(jxlhip_ctx* ctx, const void** host_
 
 JXLHIP_EXPORT int jxlhip_sync(jxlhip_ctx* ctx);
 
+/* ---- regular Modular frames (lossless files): integer planes to pixels ----
+ * jxlhip_decode_modular_frame: the device stage behind jxlhip_modular_image_decode (jxl_hip_frame.h), which leaves a
+ * lossless frame as three integer planes in coded channel order plus the reversible colour transforms (RCT) that are
+ * still to be undone.  The call copies the planes (HOST memory; pinned memory makes the copies true DMAs) and the
+ * programs into context-owned device memory on the context's stream and launches ONE kernel, k_modular_emit, which
+ * does per pixel what the reference does in InvRCT (modular/transform/rct.cc:29-148) and ModularImageToDecodedRect
+ * (dec_modular.cc:75-104,584-586,656-688): widen to int32; undo the pixel's group program, then the global one, each
+ * last-listed first, in int32 arithmetic that wraps; v * (float)(1.0 / (2^bits_per_sample - 1)), one IEEE multiply; the
+ * sample conversion of the output format.  The samples are the ORIGINAL's, encoded as the original was: no transfer
+ * function is applied and out_format->transfer is not read (the whole-file calls check it against the original's,
+ * jxl_hip_codestream.h).  A program is the first-listed RCT type | the second-listed type << 8; type 0 .. 41 = 7 *
+ * permutation + custom, 0 is the identity.
+ * output_kind: JXLHIP_OUT_LINEAR_RGB_F32 (3 floats per pixel, the samples as they are) or JXLHIP_OUT_PACKED with
+ * out_format (every sample type, 3 or 4 channels with the opaque alpha, the 8-bit dither, endianness);
+ * JXLHIP_OUT_XYB_PLANAR is JXLHIP_ERR_UNSUPPORTED: such a frame has no XYB form.  out / out_stride: device memory, bytes
+ * per row, as jxlhip_decode_frame.  undo_orientation: as jxlhip_frame_params (0 or 1 = coded orientation; 2..8 write
+ * display orientation, for 5..8 ysize pixels wide and xsize rows high).  Asynchronous like the decode calls: the planes,
+ * group_rct and `out` must stay valid until jxlhip_sync.  Needs no jxlhip_frame_begin and leaves the context's frame
+ * alone.  JXLHIP_ERR_INVALID_ARGUMENT: a zero size, bits_per_sample outside 1..16, a group_dim that is not 128, 256, 512
+ * or 1024, a program with a type above 41, a stride below xsize, a bad output format, stride or alignment.
+ * JXLHIP_ERR_UNSUPPORTED on a multi-device context. */
+enum { JXLHIP_MODULAR_I16 = 0, JXLHIP_MODULAR_I32 = 1 };
+#define JXLHIP_MODULAR_MAX_RCTS 2
+typedef struct jxlhip_modular_frame {
+  uint32_t xsize, ysize;
+  const void* planes[3];      /* host: ysize rows of stride_samples samples, channel order as coded */
+  size_t stride_samples;      /* >= xsize */
+  uint32_t sample_type;       /* JXLHIP_MODULAR_I16 / JXLHIP_MODULAR_I32 */
+  uint32_t bits_per_sample;   /* of the image: 1..16 */
+  uint32_t group_dim;         /* 128 << FrameHeader::group_size_shift */
+  const uint16_t* group_rct;  /* host: ceil(xsize / group_dim) * ceil(ysize / group_dim) programs, raster order; NULL = all 0 */
+  uint16_t global_rct;
+} jxlhip_modular_frame;
+JXLHIP_EXPORT int jxlhip_decode_modular_frame(jxlhip_ctx* ctx, const jxlhip_modular_frame* frame, uint32_t output_kind,
+                                              const jxlhip_output_format* out_format, void* out, size_t out_stride,
+                                              uint32_t undo_orientation);
+
 /* Debug/test taps on context-owned intermediates (device pointers).
  * export_xyb: row-major copy of the phase-1 result, rows [first row of the
  * stripe, + its block-padded height) x xsize_blocks*8 columns, row stride

@@ -25,12 +25,27 @@
  * one regular last frame whose flags may include kPatches (jxlhip_patches_decode, blended on the device,
  * jxlhip_set_patches), of images without extra channels.  The four reference slots of the context are cleared at the
  * start of every call; the info struct describes the visible frame.
+ * Also taken: lossless files -- an image that is NOT XYB encoded in one regular Modular frame, what `cjxl -d 0` writes
+ * (info->modular = 1): 8..16-bit integer RGB samples with an enumerated colour encoding, any group_size_shift, RCTs (all
+ * 42 types, global and per group), palettes without deltas, LZ77.  Such a frame has a stage path of its own
+ * (frame_decode.hip: DecodeModularFrameAt): headers; DC global = the DC dequant bit and the global Modular image; the
+ * ModularDC stream of every DC group and the ModularAC stream of every group on the runner (jxlhip_modular_image_decode's
+ * stages, jxl_hip_frame.h); the integer planes and RCT programs uploaded and turned into pixels by ONE kernel
+ * (jxlhip_decode_modular_frame, jxl_hip.h); jxlhip_sync.  The pixels are the original's samples: out_format->transfer
+ * must be the original's (info->transfer_function; JXLHIP_OUT_LINEAR_RGB_F32 wants a linear original), anything else is
+ * JXLHIP_ERR_UNSUPPORTED with the reason in jxlhip_last_error -- JxlDecoder without a CMS cannot convert either --, and so
+ * are JXLHIP_OUT_XYB_PLANAR and a display (jxlhip_codestream_set_display) with any field set.  jxlhip_codestream_phase_ms
+ * reports HEADERS, AC_GROUPS (the host's entropy decode of every group) and KERNELS (upload, kernel, sync); the others 0.
  * A file that has not arrived completely is rendered by jxlhip_decode_codestream_partial below (groups without AC from
  * their DC, upsampled 8x on the device: jxlhip_set_dc_only_groups); the other calls refuse truncated input.
  * Animations, layers, cropped and blended frames go through jxlhip_codestream_sequence_info /
  * jxlhip_decode_codestream_next below (blended on the device, jxlhip_set_blending); the single-frame calls refuse them.
  * Everything this front-end does not decode is refused with JXLHIP_ERR_UNSUPPORTED so that the caller can hand the
- * file to libjxl's CPU decoder: Modular-mode frames, animation / layers / any other sequence of frames (single-frame
+ * file to libjxl's CPU decoder: of lossless files, each with a named reason: XYB or YCbCr Modular regular frames, a
+ * squeeze on the colour channels (`cjxl -p`), delta palettes, float samples or more than 16 bits, grey images, ICC
+ * originals, images with extra channels, upsampling != 1, any frame flag, a loop filter, more than one pass, chroma
+ * subsampling, previews -- and every lossless file by the sequence calls and the partial call, as before; then
+ * animation / layers / any other sequence of frames (single-frame
  * calls; the sequence calls blend images with extra channels too when asked to, and refuse VarDCT
  * reference-only frames, regular frames saved before the colour transform and kSkipProgressive), previews,
  * reference frames of more than one group or with an RCT, squeeze or delta palette, patches on images with extra channels,
@@ -67,7 +82,12 @@ typedef struct jxlhip_codestream_info {
   uint32_t epf_iters, gab;
   uint32_t used_acs;
   uint32_t coeff_type;         /* JXLHIP_COEFF_I16, or I32 after the JXLHIP_ERR_RANGE redo */
-  uint32_t fused;              /* reserved */
+  uint32_t modular;            /* headers: 1 = a lossless file -- the image is not XYB encoded and its one frame is a
+                                  regular Modular frame.  The pixels are the original's integer samples:
+                                  out_format->transfer must be the one transfer_function above names (a
+                                  JXLHIP_OUT_LINEAR_RGB_F32 output wants a linear original), and epf_iters, gab,
+                                  used_acs and coeff_type stay 0.  (The word was reserved, and always 0, before lossless
+                                  files were taken: the struct's size and every other offset are what they were.) */
   /* headers: the image's extra channels (this front-end takes up to four, full resolution, integer samples) and the
      first one of type alpha: its bit depth (0 = the image has no alpha channel), whether it is premultiplied */
   uint32_t num_extra_channels, alpha_bits, alpha_premultiplied;
@@ -127,7 +147,7 @@ JXLHIP_EXPORT int jxlhip_codestream_display_info(const uint8_t* data, size_t siz
 JXLHIP_EXPORT int jxlhip_codestream_icc_profile(const uint8_t* data, size_t size, uint8_t* icc, size_t icc_capacity,
                                                 size_t* icc_size);
 
-/* Decodes the (single, VarDCT) frame of a .jxl file or bare codestream into device memory.
+/* Decodes the single frame -- VarDCT, or the regular Modular frame of a lossless file -- of a .jxl file or bare codestream into device memory.
  *   alpha                  : an alpha channel of the image is decoded (host, Modular) and written as the fourth
  *                            channel of a 4-channel JXLHIP_OUT_PACKED output; every other output ignores it (its bytes
  *                            are skipped), and a frame without one gives the opaque value.  Not un-premultiplied.
@@ -225,7 +245,7 @@ JXLHIP_EXPORT int jxlhip_decode_codestream_partial(jxlhip_ctx* ctx, jxlhip_paral
  * A DISPLAYED frame is what the reference's coalescing decoder reports (decode.cc:1346-1356): a regular frame with
  * is_last or duration > 0, blended over whatever its zero-duration layers and earlier frames left in its source slot.
  * Refused up front with JXLHIP_ERR_UNSUPPORTED and a named reason (jxlhip_last_error of the decode call): previews,
- * Modular regular frames, VarDCT kReferenceOnly frames, DC frames and kUseDcFrame, kSkipProgressive, regular frames
+ * Modular regular frames (lossless files included: an image that is not XYB encoded is refused at its header), VarDCT kReferenceOnly frames, DC frames and kUseDcFrame, kSkipProgressive, regular frames
  * saved before the colour transform; on an image with extra channels a frame with patches, an upsampled frame and
  * extra channels upsampled on their own; a frame that needs blending while display_nits is set; and everything the
  * single-frame calls refuse per frame.

@@ -404,6 +404,46 @@ JXLHIP_EXPORT int jxlhip_modular_frame_decode(const uint8_t* data, size_t size, 
                                               const jxlhip_frame_header* frame, float* const planes[3],
                                               size_t stride_floats, const char** why);
 
+/* ---- A regular Modular frame: what `cjxl -d 0` writes (lossless; the image is NOT XYB encoded) ----
+ * jxlhip_modular_image_decode reads every section of such a frame on the host -- DC global (DequantMatrices::DecodeDC and
+ * the global tree / global Modular image with the three colour channels, dec_modular.cc:207-316), the ModularDC stream of
+ * every DC group and the ModularAC stream of every group (:330-425), the groups on `runner` (NULL = calling thread) --
+ * and leaves the frame's three integer planes in the caller's memory, in coded channel order, with what is still to be
+ * undone per pixel: reversible colour transforms (RCT, modular/transform/rct.cc).  Any group_size_shift.
+ * The split: a stream whose transform list is nothing but 1..JXLHIP_MODULAR_MAX_RCTS RCTs over the three colour
+ * channels keeps them -- its samples are written as decoded and its program says which (group_rct[group], global_rct:
+ * the first-listed type | the second-listed type << 8; type 0 is the identity, so 0 = nothing to undo).  Whoever turns
+ * the planes into pixels applies to every pixel the inverse of its group's program, then of the global one, each
+ * last-listed first, in int32 arithmetic that wraps (k_modular_emit, jxlhip_decode_modular_frame in jxl_hip.h).  A stream
+ * with anything else in its list (palettes, an RCT elsewhere, more RCTs) has the whole list undone here, on the thread
+ * that decoded it, and program 0; when the GLOBAL list is of that kind every group is undone here as well and the global
+ * list once all are in.
+ * data / size / *bit_pos: the codestream, and the first bit behind the frame header (the TOC); *bit_pos advances to the
+ * first bit behind the frame's sections.  planes: see the struct.
+ * JXLHIP_ERR_UNSUPPORTED with *why (may be NULL) naming the case in a static string: an XYB or YCbCr Modular frame, a
+ * squeeze on the colour channels (`cjxl -p`), delta palettes, an image with extra channels, upsampling != 1, any frame
+ * flag, a loop filter, more than one pass, chroma subsampling, a frame that is not a full-size regular frame.  (The
+ * image-level cases -- float samples or more than 16 bits, grey images, ICC originals, previews -- are the whole-file
+ * calls', jxl_hip_codestream.h: this entry sees the frame header only.)  JXLHIP_ERR_RANGE: a sample does not fit
+ * JXLHIP_MODULAR_I16 planes (an image whose modular_16_bit_buffer_sufficient is wrong): decode again with
+ * JXLHIP_MODULAR_I32.  JXLHIP_ERR_BAD_STREAM where the reference rejects the stream and on truncation. */
+typedef struct jxlhip_modular_image_planes {  /* (JXLHIP_MODULAR_I16 / _I32, JXLHIP_MODULAR_MAX_RCTS: jxl_hip.h) */
+  /* in */
+  void* planes[3];          /* frame->ysize rows of stride_samples samples each; channel order as coded */
+  size_t stride_samples;    /* >= frame->xsize */
+  uint32_t sample_type;     /* JXLHIP_MODULAR_I16 (images with modular_16_bit_buffer_sufficient) or JXLHIP_MODULAR_I32 */
+  uint16_t* group_rct;      /* frame->num_groups entries, written by the call */
+  /* out */
+  uint16_t global_rct;      /* the global program */
+  uint32_t global_tree;     /* the DC-global section carries a global MA tree */
+  uint32_t global_on_host;  /* the global transform list was undone on the host (and with it every group's) */
+  uint32_t groups_on_device; /* groups whose program is not 0 */
+  uint32_t groups_on_host;  /* groups whose own transform list was undone on the host */
+} jxlhip_modular_image_planes;
+JXLHIP_EXPORT int jxlhip_modular_image_decode(const uint8_t* data, size_t size, size_t* bit_pos,
+                                              const jxlhip_frame_header* frame, jxlhip_parallel_runner runner,
+                                              void* runner_opaque, jxlhip_modular_image_planes* planes, const char** why);
+
 /* One DC group section (section 1 + dc_group of the TOC).  All outputs are FRAME-level arrays in the
  * layouts jxlhip_upload_side_info / jxlhip_dequant_dc take, of which this call fills the group's
  * rectangle (256x256 blocks at the default group size):

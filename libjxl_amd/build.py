@@ -21,7 +21,7 @@ LIB_SOURCES = ["kernels_fused.hip", "kernels_filters_fast_general.hip", "kernels
                "render_stages.hip", "handover.hip", "codestream.hip", "frame_decode.hip", "multi.hip",
                "kernels_filters.hip", "kernels_mfma.hip", "kernels_epf0.hip", "kernels_tables.hip", "kernels_noise.hip",
                "kernels_splines.hip", "kernels_upsample.hip", "kernels_patches.hip", "kernels_blend.hip", "kernels_blend_ec.hip",
-               "kernels_tonemap.hip", "kernels_dc_upsample.hip"]
+               "kernels_tonemap.hip", "kernels_dc_upsample.hip", "kernels_modular.hip"]
 RUNNER_SOURCES = ["runner.cc"]
 # Per-file flags.  kernels_blocks.hip: the SLP vectoriser pairs the butterflies of the in-register IDCTs into packed
 # fp32 operations (v_pk_fma / v_pk_add / v_pk_mul on aligned register PAIRS, stitched together with v_mov): the pairs
@@ -185,6 +185,7 @@ def build(verbose=False):
     check_no_scratch(lib, "k_blend")  # (12 background + 12 frame samples per thread: indexed by constants only)
     check_no_scratch(lib, "k_ec_blend")  # (... and up to four extra channels beside them, their alpha picked with selects)
     check_no_scratch(lib, "k_tone_map")  # (two pixels per thread and nothing indexed: scratch here means the register budget broke)
+    check_no_scratch(lib, "k_modular_emit")  # (a run of 8 pixels per thread, indexed by constants only: a streaming kernel has no business in scratch)
     check_no_scratch(lib, "k_dc_upsample8")  # (4 x 25 weights and 25 samples per thread live in registers: indexed by constants only)
     out = [lib]
     if have_runner:

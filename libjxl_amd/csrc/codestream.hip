@@ -4,6 +4,7 @@
 // lib/jxl/dec_frame.cc:96-189 around it).
 #include "codestream_plan.h"
 #include "frame_decode.h"
+#include "modular_image.h"
 
 namespace {
 
@@ -39,11 +40,13 @@ int ReadReferenceFrame(const uint8_t* cs, size_t n, const jxlhip_frame_header& f
   return JXLHIP_OK;
 }
 
-// image header + the reference frames + the visible frame's header + the eligibility rules of this back-end
-int ParseHeaders(const uint8_t* cs, size_t n, ParsedHeaders* h) {
+// image header + the reference frames + the visible frame's header + the eligibility rules of this back-end.
+// lossless: the caller takes a lossless file (an image that is not XYB encoded, in one regular Modular frame:
+// h->modular); the partial call does not, and the sequence calls have a walk of their own.
+int ParseHeaders(const uint8_t* cs, size_t n, ParsedHeaders* h, bool lossless) {
   size_t pos = 0;
   jxlhip_image_info info{};
-  int rc = ParseImagePart(cs, n, h, &pos, &info, false);
+  int rc = ParseImagePart(cs, n, h, &pos, &info, false, lossless);
   if (rc) return rc;
   const jxlhip_image_header& ih = h->ih;
   // any number of kReferenceOnly frames, then exactly one regular frame, the last of the file: every other sequence
@@ -55,6 +58,15 @@ int ParseHeaders(const uint8_t* cs, size_t n, ParsedHeaders* h) {
     if ((rc = ReadReferenceFrame(cs, n, h->fh, &pos, h))) return rc;
   }
   const jxlhip_frame_header& fh = h->fh;
+  if (h->modular) {  // the frame-level cases of the lossless path, each by name (ModularImageRefusal)
+    for (const ReferenceFrame& r : h->refs)
+      if (r.xsize != 0) return h->why = "a lossless file with reference frames", JXLHIP_ERR_UNSUPPORTED;
+    if (!fh.is_last) return h->why = "a lossless file of more than one frame", JXLHIP_ERR_UNSUPPORTED;
+    if (const char* what = ModularImageRefusal(&fh)) return h->why = what, JXLHIP_ERR_UNSUPPORTED;
+    if (fh.xsize != ih.xsize || fh.ysize != ih.ysize) return JXLHIP_ERR_UNSUPPORTED;
+    h->frame_bit_pos = pos;
+    return JXLHIP_OK;
+  }
   // (patches would have to blend the extra channels as well: refused for now)
   if ((fh.flags & JXLHIP_FLAG_PATCHES) && ih.num_extra_channels != 0) {
     h->why = "patches on an image with extra channels";
@@ -106,6 +118,7 @@ void FillInfo(const ParsedHeaders& h, bool container, jxlhip_codestream_info* in
     info->alpha_premultiplied = h.extra[h.alpha_index].alpha_associated;
   }
   info->upsampling = h.fh.upsampling;
+  info->modular = h.modular ? 1u : 0u;
 }
 
 // jxlhip_codestream_set_display applied to the parsed headers: the matrix and luminances of the requested space, the
@@ -122,6 +135,8 @@ int CheckDisplay(const jxlhip_display& d) {
 int ApplyDisplay(const jxlhip_display& d, ParsedHeaders* h, const char** why) {
   *why = "";
   if (d.display_nits == 0.0f && d.primaries == 0 && d.white_point == 0) return JXLHIP_OK;
+  // (a lossless file's samples are the original's: nothing between them and the output could take a display into account)
+  if (h->modular) return *why = "a display set for a lossless (Modular) file", JXLHIP_ERR_UNSUPPORTED;
   int rc = CheckDisplay(d);
   if (rc) {
     if (rc == JXLHIP_ERR_UNSUPPORTED) *why = "custom xy as the requested output space";
@@ -165,7 +180,7 @@ int jxlhip_codestream_basic_info(const uint8_t* data, size_t size, jxlhip_codest
   if (rc) return rc;
   ParsedHeaders h;
   try {
-    if ((rc = ParseHeaders(b.cs, b.n, &h))) return rc;
+    if ((rc = ParseHeaders(b.cs, b.n, &h, true))) return rc;
   } catch (const std::bad_alloc&) {
     return JXLHIP_ERR_OUT_OF_MEMORY;
   }
@@ -203,7 +218,7 @@ int jxlhip_codestream_display_info(const uint8_t* data, size_t size, const jxlhi
   try {
     ParsedHeaders h;
     Sequence s;
-    rc = ParseHeaders(b.cs, b.n, &h);
+    rc = ParseHeaders(b.cs, b.n, &h, true);
     const bool sequence = rc == JXLHIP_ERR_UNSUPPORTED;
     if (sequence && (rc = WalkSequence(b.cs, b.n, &s)) == JXLHIP_ERR_UNSUPPORTED) why = s.h.why;
     if (!rc && display) rc = ApplyDisplay(*display, sequence ? &s.h : &h, &why);
@@ -311,9 +326,16 @@ int DecodeCodestreamImpl(jxlhip_ctx* c, jxlhip_parallel_runner runner, void* run
   CodestreamBytes b;
   if ((rc = b.Open(data, size))) return Fail(c, rc, "not a JPEG XL codestream or container");
   ParsedHeaders h;
-  if ((rc = ParseHeaders(b.cs, b.n, &h)))
+  if ((rc = ParseHeaders(b.cs, b.n, &h, true)))
     return Fail(c, rc, rc == JXLHIP_ERR_UNSUPPORTED ? (h.why[0] ? h.why : "stream uses features outside the VarDCT back-end") : "invalid headers");
   if ((rc = ApplyDisplay(c, &h))) return rc;
+  if (h.modular) {  // a lossless file: a stage path of its own (frame_decode.hip)
+    jxlhip_codestream_info info;
+    FillInfo(h, b.container, &info);
+    if ((rc = DecodeModularFrameAt(c, b.cs, b.n, h, call.fc, call.clock, &info))) return rc;
+    if (info_out) *info_out = info;
+    return JXLHIP_OK;
+  }
   for (uint32_t slot = 0; slot < 4; slot++)
     if (h.refs[slot].xsize != 0 && (rc = SetReferenceSlot(c, slot, h.refs[slot]))) return rc;
   jxlhip_codestream_info info;
@@ -572,7 +594,7 @@ int ReadPartial(const uint8_t* data, size_t size, CodestreamBytes* b, ParsedHead
   int rc = b->Open(data, size, true);
   if (rc) return rc;
   // headers that end early do not parse: which of the two it is only more bytes can tell
-  rc = ParseHeaders(b->cs, b->n, h);
+  rc = ParseHeaders(b->cs, b->n, h, false);
   if (rc == JXLHIP_ERR_BAD_STREAM) return JXLHIP_ERR_NEED_MORE_INPUT;
   if (rc == JXLHIP_ERR_UNSUPPORTED) *why = h->why[0] ? h->why : "stream uses features outside the VarDCT back-end";
   if (rc) return rc;

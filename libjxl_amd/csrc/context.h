@@ -404,6 +404,11 @@ struct jxlhip_ctx {
   DevBuf<float> alpha_dev;  // jxlhip_set_alpha: the frame's alpha plane (xsize floats per row)
   PinnedBuf alpha_host;  // jxlhip_alpha_staging: pinned plane the caller fills
   DevBuf<int32_t> qdc_dev;  // jxlhip_decode_codestream: the quantized DC planes on their way to jxlhip_dequant_dc_groups
+  // jxlhip_decode_modular_frame: the three integer planes and the per-group RCT programs on the device; the pinned
+  // planes and programs a lossless file's host decode fills (jxlhip_decode_codestream)
+  DevBuf<uint8_t> modular_dev;
+  DevBuf<uint16_t> modular_rct_dev;
+  PinnedBuf modular_host;
   StageState st;  // the render stages of the current frame (jxlhip_frame_begin: ResetFrame)
   SlotState slots;  // the four reference / canvas slots: they outlive frames
   // jxlhip_codestream_set_display: sticky on the context (0 = not set), read by the whole-file decode calls

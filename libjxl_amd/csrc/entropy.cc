@@ -2541,6 +2541,7 @@ int jxlhip_icc_decode(const uint8_t* data, size_t size, size_t* bit_pos, uint8_t
 }
 
 #include "modular.inc"
+#include "modular_image.inc"
 
 int jxlhip_dequant_encodings_decode(const uint8_t* data, size_t size, size_t* bit_pos, jxlhip_quant_encoding* enc) {
   if (!data || !bit_pos || !enc) return JXLHIP_ERR_INVALID_ARGUMENT;

@@ -56,6 +56,13 @@ int DecodeFrameAt(jxlhip_ctx* c, const uint8_t* cs, size_t n, const ParsedHeader
                   size_t frame_bit_pos, const FrameCall& fc, PhaseClock& clock, bool verbose, jxlhip_codestream_info* info_p,
                   size_t* end_bit_pos);
 
+
+// The one frame of a lossless file (ParsedHeaders::modular: a regular Modular frame of an image that is not XYB
+// encoded), from its TOC to the pixels: the host decode of its sections into pinned integer planes
+// (modular_image.h), their upload and k_modular_emit (jxlhip_decode_modular_frame), jxlhip_sync.
+int DecodeModularFrameAt(jxlhip_ctx* c, const uint8_t* cs, size_t n, const ParsedHeaders& h, const FrameCall& fc, PhaseClock& clock,
+                         jxlhip_codestream_info* info);
+
 }  // namespace jxlhip
 
 #endif  // JXLHIP_FRAME_DECODE_H_

@@ -4,6 +4,7 @@
 #include "frame_decode.h"
 
 #include "codestream_plan.h"
+#include "modular_image.h"
 
 namespace jxlhip {
 namespace {
@@ -854,6 +855,126 @@ int DecodeFrameAt(jxlhip_ctx* c, const uint8_t* cs, size_t n, const ParsedHeader
   info.gab = fh.lf.gab;
   info.used_acs = d.used_acs;
   if (end_bit_pos) *end_bit_pos = (d.base + (size_t)d.total) * 8;
+  return JXLHIP_OK;
+}
+
+
+// ---- the one frame of a lossless file: a regular Modular frame.  No VarDCT part: DC global is the DC dequant bit and
+// the global Modular image, a DC group is its ModularDC stream, AC global is empty, an AC group is its ModularAC stream.
+// The entropy decode stays on the host (an MA-tree context per sample, an ANS state per stream: serial inside a group,
+// parallel over the groups on the runner); what it leaves -- three integer planes and the RCTs still to undo -- goes to
+// the device for one streaming kernel.
+namespace {
+
+struct ModularGroupsJob2 {
+  ModularImage* image;
+  const FrameDecode* d;
+  std::atomic<int> status{JXLHIP_OK};
+};
+void ModularImageGroupsFunc(void* opaque, uint32_t t, size_t) {
+  ModularGroupsJob2* j = static_cast<ModularGroupsJob2*>(opaque);
+  if (j->status.load(std::memory_order_relaxed) != JXLHIP_OK) return;
+  const FrameDecode& d = *j->d;
+  size_t pos = 0;
+  // (section 1 + ndc is AC global)
+  const int rc = t < d.ndc ? ModularImageDcGroup(j->image, t, d.sec(1 + t), d.sz[1 + t], &pos)
+                           : ModularImageAcGroup(j->image, t - d.ndc, d.sec(2 + t), d.sz[2 + t], &pos);
+  KeepFirst(j->status, rc);
+}
+
+// the output's transfer function a lossless file has to be asked for in: the original's (JXLHIP_TF_*)
+uint32_t OriginalTransfer(const jxlhip_color_encoding& ce) {
+  if (ce.all_default) return JXLHIP_TF_SRGB;
+  if (ce.have_gamma) return JXLHIP_TF_GAMMA;
+  switch (ce.transfer_function) {
+    case 1: return JXLHIP_TF_709;
+    case 8: return JXLHIP_TF_LINEAR;
+    case 13: return JXLHIP_TF_SRGB;
+    case 16: return JXLHIP_TF_PQ;
+    case 17: return JXLHIP_TF_GAMMA;
+    case 18: return JXLHIP_TF_HLG;
+    default: return ~0u;
+  }
+}
+
+}  // namespace
+
+int DecodeModularFrameAt(jxlhip_ctx* c, const uint8_t* cs, size_t n, const ParsedHeaders& h, const FrameCall& fc, PhaseClock& clock,
+                         jxlhip_codestream_info* info) {
+  const jxlhip_image_header& ih = h.ih;
+  const jxlhip_frame_header& fh = h.fh;
+  if (fc.output_kind == JXLHIP_OUT_XYB_PLANAR) return Fail(c, JXLHIP_ERR_UNSUPPORTED, "planar XYB of a lossless (Modular) file, which is not XYB");
+  // the pixels are the original's samples: nothing on this path converts between transfer functions (JxlDecoder without a
+  // CMS cannot either)
+  const uint32_t original = OriginalTransfer(ih.color_encoding);
+  const uint32_t asked = fc.output_kind == JXLHIP_OUT_PACKED ? fc.out_format->transfer : (uint32_t)JXLHIP_TF_LINEAR;
+  if (asked != original)
+    return Fail(c, JXLHIP_ERR_UNSUPPORTED, "a lossless (Modular) file comes out in its original's transfer function only (JXLHIP_TF_* %u asked, %u coded)",
+                asked, original);
+  if (fc.num_extra_planes) return Fail(c, JXLHIP_ERR_UNSUPPORTED, "extra-channel planes of a lossless (Modular) file");
+  FrameDecode d{c, cs, n, h, ih, fh, fc, clock, false};
+  int rc;
+  if ((rc = d.ReadToc(h.frame_bit_pos))) return rc;
+  if (!d.single && d.off.size() != 2 + (size_t)d.ndc + d.ng) return Fail(c, JXLHIP_ERR_BAD_STREAM, "section count of a Modular frame");
+  // pinned planes (rows of a multiple of 64 samples) and programs: int16 when the image header says 16-bit buffers do
+  const uint32_t stride = (fh.xsize + 63u) & ~63u;
+  HIPCHK(c, hipSetDevice(c->device));
+  for (uint32_t type = ih.modular_16_bit_buffer_sufficient ? JXLHIP_MODULAR_I16 : JXLHIP_MODULAR_I32; type <= JXLHIP_MODULAR_I32; type++) {
+    const size_t ssz = type == JXLHIP_MODULAR_I16 ? 2 : 4;
+    const size_t plane = ((size_t)stride * fh.ysize * ssz + 255) & ~(size_t)255;
+    const size_t need = 3 * plane + (size_t)d.ng * sizeof(uint16_t);
+    if (need > c->modular_host.bytes) {
+      if ((rc = jxlhip_sync(c))) return rc;  // (nothing may still be reading the old planes)
+      if (c->modular_host.Alloc(&c->mm, need)) return Fail(c, JXLHIP_ERR_OUT_OF_MEMORY, "pinned Modular planes of %zu bytes", need);
+    }
+    uint8_t* base = static_cast<uint8_t*>(c->modular_host.p);
+    jxlhip_modular_image_planes pl{};
+    for (int ch = 0; ch < 3; ch++) pl.planes[ch] = base + ch * plane;
+    pl.stride_samples = stride;
+    pl.sample_type = type;
+    pl.group_rct = reinterpret_cast<uint16_t*>(base + 3 * plane);
+    // ---- DC global: the DC dequant bit, the global tree, the global Modular image
+    const char* why = "";
+    ModularImage* raw = nullptr;
+    d.spos = 0;
+    if ((rc = ModularImageBegin(d.sec(0), d.sz[0], &d.spos, &fh, &pl, &raw, &why)))
+      return Fail(c, rc, "%s", rc == JXLHIP_ERR_UNSUPPORTED && why[0] ? why : "invalid DC global section of a Modular frame");
+    std::unique_ptr<ModularImage, void (*)(ModularImage*)> image(raw, ModularImageDestroy);
+    clock.Mark(JXLHIP_PHASE_HEADERS);
+    // ---- ModularDC per DC group, ModularAC per group: on the runner
+    if (d.single) {
+      if ((rc = ModularImageDcGroup(raw, 0, d.sec(0), d.sz[0], &d.spos)) || (rc = ModularImageAcGroup(raw, 0, d.sec(0), d.sz[0], &d.spos)))
+        return Fail(c, rc, "invalid Modular group");
+    } else {
+      ModularGroupsJob2 job{raw, &d};
+      if ((rc = d.RunJob(&job, NoInit, ModularImageGroupsFunc, d.ndc + d.ng))) return rc;
+      if ((rc = job.status.load()))
+        return Fail(c, rc, rc == JXLHIP_ERR_UNSUPPORTED ? "a Modular group with a delta palette or a squeeze" : "invalid Modular group");
+    }
+    rc = ModularImageFinish(raw);
+    clock.Mark(JXLHIP_PHASE_AC_GROUPS);
+    if (rc == JXLHIP_ERR_RANGE && type == JXLHIP_MODULAR_I16) continue;  // (the header's promise did not hold: int32 planes)
+    if (rc) return Fail(c, rc, "invalid Modular frame");
+    // ---- upload, k_modular_emit, sync
+    jxlhip_modular_frame m{};
+    m.xsize = fh.xsize;
+    m.ysize = fh.ysize;
+    for (int ch = 0; ch < 3; ch++) m.planes[ch] = pl.planes[ch];
+    m.stride_samples = stride;
+    m.sample_type = type;
+    m.bits_per_sample = ih.bit_depth.bits_per_sample;
+    m.group_dim = fh.group_dim;
+    m.group_rct = pl.group_rct;
+    m.global_rct = pl.global_rct;
+    if ((rc = jxlhip_decode_modular_frame(c, &m, fc.output_kind, fc.out_format, fc.out, fc.out_stride, fc.undo_orientation ? ih.orientation : 0)))
+      return rc;
+    if ((rc = jxlhip_sync(c))) return rc;
+    clock.Mark(JXLHIP_PHASE_KERNELS);
+    break;
+  }
+  info->num_passes = d.np;
+  info->num_groups = d.ng;
+  info->num_dc_groups = d.ndc;
   return JXLHIP_OK;
 }
 

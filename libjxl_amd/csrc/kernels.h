@@ -270,6 +270,22 @@ void ToneMapHostConstants(float orig, float desired, const float luminances[3], 
 // (JXLHIP_OUT_LINEAR_RGB_F32 / JXLHIP_OUT_PACKED) into p.out.  False for another kind or bad geometry.
 bool LaunchToneMap(const ToneMapArgs& A, const FilterParams& p, int output_kind, hipStream_t st);
 
+// A regular Modular frame (kernels_modular.hip): three integer planes, the RCT programs the host left, the scale.
+struct ModularEmitArgs {
+  uint32_t xsize, ysize;
+  const void* plane[3];        // device, 16-byte aligned: rows of ns samples of sample_type, channel order as coded
+  uint32_t ns;                 // a multiple of 8, >= xsize rounded up to 8
+  uint32_t sample_type;        // JXLHIP_MODULAR_I16 / JXLHIP_MODULAR_I32
+  uint32_t group_shift, xsg;   // groups of (1 << group_shift) pixels (7 .. 10), xsg of them to the row
+  const uint16_t* group_rct;   // device: per group, the first-listed RCT type | the second-listed << 8 (0 = none)
+  uint32_t global_rct;         // the same for the whole frame, undone behind the group's
+  float factor;                // (float)(1.0 / (2^bits_per_sample - 1))
+};
+// k_modular_emit: inverse RCTs, int -> float and the output tail of `output_kind` (JXLHIP_OUT_LINEAR_RGB_F32 /
+// JXLHIP_OUT_PACKED; p.fmt.transfer is not read: the tail runs with the identity) into p.out.  False for another kind or
+// bad geometry / alignment.
+bool LaunchModularEmit(const ModularEmitArgs& A, const FilterParams& p, int output_kind, hipStream_t st);
+
 // Upsampling (kernels_upsample.hip).  The coded frame is cut into 64 x 16 tiles; every coded pixel gives n x n output
 // pixels, each a 25-tap sum over its 5 x 5 neighbourhood clamped to the neighbourhood's range.
 struct UpsampleArgs {

@@ -20,6 +20,9 @@
 // several channels with the implicit colour-cube entries) and the squeeze `cjxl -p` puts on the global image behind
 // them (RCT, delta palettes, a squeeze inside a group stream or in front of another transform), LZ77 with the 2-D
 // special distances, and chroma subsampling (the back-end is 4:4:4).
+// The streams of a regular Modular frame (a lossless file: modular_image.inc, ModularStreamOptions below) also carry
+//   the reversible colour transforms, all 42         modular/transform/transform.cc:36-90, rct.cc:29-148
+// which are read, and undone here (UndoRct) or left for the device, and LZ77.
 
 struct jxlhip_modular_tree;
 
@@ -156,6 +159,23 @@ int DecodeMaTree(BitReader* br, size_t size_limit, jxlhip_modular_tree* t) {
 // channel that uses few of its values, enc_modular.cc:400-440,1427-1440)
 struct ModularPalette {
   uint32_t begin_c = 0, num_c = 1, nb_colors = 0;
+  // the same list also carries the RCTs of a regular Modular frame's streams (ModularStreamOptions::rct), in coded order:
+  // rct: channels begin_c .. begin_c + 2 went through reversible colour transform rct_type (0 .. 41, rct.cc:97-148)
+  bool rct = false;
+  uint32_t rct_type = 0;
+};
+// What the streams of a regular Modular frame (jxlhip_modular_image_decode) may carry beyond the slice above, and what
+// becomes of their RCTs
+constexpr uint32_t kMaxDeviceRcts = 2;  // JXLHIP_MODULAR_MAX_RCTS
+struct ModularStreamOptions {
+  bool rct = false;         // RCTs are read (otherwise JXLHIP_ERR_UNSUPPORTED, as ever)
+  bool lz77 = false;        // as ModularDecodeImage's allow_lz77
+  bool leave_rcts = false;  // a transform list that is nothing but 1 .. kMaxDeviceRcts RCTs over the three channels of a
+                            // three-channel image is NOT undone: `program` says which they were
+  // out
+  bool transforms = false;  // the stream's header listed transforms
+  bool left = false;        // ... and they were left (leave_rcts)
+  uint16_t program = 0;     // left: the first-listed type | the second-listed type << 8 (type 0 is the identity)
 };
 struct SqueezeStep {  // SqueezeParams (squeeze_params.cc:15-24)
   bool horizontal = false, in_place = false;
@@ -170,7 +190,7 @@ struct ModularSqueeze {
 // transform is refused (before a pixel is decoded).  squeeze == NULL: a squeeze is refused too; otherwise ONE squeeze
 // is taken when it is the last transform (behind the palettes: the order libjxl's encoder writes, enc_modular.cc)
 int ReadModularGroupHeader(BitReader* br, bool* use_global_tree, WpHeader* wp, std::vector<ModularPalette>* palettes,
-                           ModularSqueeze* squeeze = nullptr) {
+                           ModularSqueeze* squeeze = nullptr, bool allow_rct = false) {
   FieldReader r(br);
   *use_global_tree = r.Bool();
   *wp = WpHeader();
@@ -207,6 +227,18 @@ int ReadModularGroupHeader(BitReader* br, bool* use_global_tree, WpHeader* wp, s
         q.num_c = r.U32(kNumC);
       }
       if (!br->Healthy()) return kBad;
+      continue;
+    }
+    if (id == 0 && allow_rct) {  // transform.cc:47-60
+      ModularPalette t;
+      static const U32Dist kBeginC = {{3, 6, 10, 13}, {0, 8, 72, 1096}};
+      t.begin_c = r.U32(kBeginC);
+      static const U32Dist kRctType = {{0, 2, 4, 6}, {6, 0, 2, 10}};
+      t.rct_type = r.U32(kRctType);
+      if (!br->Healthy() || t.rct_type >= 42) return kBad;
+      t.rct = true;
+      t.num_c = 3;
+      palettes->push_back(t);
       continue;
     }
     if (id != 1) return JXLHIP_ERR_UNSUPPORTED;  // RCT; squeeze of a group stream
@@ -1035,12 +1067,61 @@ inline int32_t PaletteValue(const int32_t* table, int32_t index, uint32_t c, int
   return (int32_t)(((i % 5) * top) >> 2);
 }
 
+// InvRCT (rct.cc:29-148) on channels begin_c .. begin_c + 2, in place: type = 7 * permutation + custom; custom 6 is
+// YCoCg, otherwise bit 0 adds the first channel to the third and the bits above add the first (1) or the average of
+// the first and the third (2) to the second; the permutation says where the three results go.  int32 arithmetic that
+// wraps, like the reference's Add / PixelAdd, and its arithmetic >> 1.
+inline void InvRctPixel(uint32_t custom, int32_t* a, int32_t* b, int32_t* c) {
+  const uint32_t first = (uint32_t)*a, second = (uint32_t)*b, third = (uint32_t)*c;
+  if (custom == 6) {
+    const uint32_t tmp = first - (uint32_t)((int32_t)third >> 1);  // Y - (Cg >> 1)
+    const uint32_t g = third + tmp;
+    const uint32_t bl = tmp - (uint32_t)((int32_t)second >> 1);
+    *a = (int32_t)(bl + second);
+    *b = (int32_t)g;
+    *c = (int32_t)bl;
+    return;
+  }
+  uint32_t s2 = second, s3 = third;
+  if (custom & 1) s3 += first;
+  if ((custom >> 1) == 1) s2 += first;
+  else if ((custom >> 1) == 2) s2 += (uint32_t)((int32_t)(first + s3) >> 1);
+  *b = (int32_t)s2;
+  *c = (int32_t)s3;
+}
+int UndoRct(std::vector<ModularChannel>& image, uint32_t begin_c, uint32_t type) {
+  if ((uint64_t)begin_c + 2 >= image.size() || type >= 42) return kBad;
+  ModularChannel* ch = &image[begin_c];
+  const size_t n = (size_t)ch[0].w * ch[0].h;
+  for (int i = 0; i < 3; i++)
+    if (ch[i].w != ch[0].w || ch[i].h != ch[0].h || ch[i].px.size() != n) return kBad;
+  if (type == 0) return kOk;
+  const uint32_t perm = type / 7, custom = type % 7;
+  const uint32_t to[3] = {perm % 3, (perm + 1 + perm / 3) % 3, (perm + 2 - perm / 3) % 3};
+  int32_t* out[3] = {ch[to[0]].px.data(), ch[to[1]].px.data(), ch[to[2]].px.data()};
+  const int32_t *in0 = ch[0].px.data(), *in1 = ch[1].px.data(), *in2 = ch[2].px.data();
+  for (size_t i = 0; i < n; i++) {
+    int32_t a = in0[i], b = in1[i], c = in2[i];  // (all three are read before any is written: out is a permutation of in)
+    InvRctPixel(custom, &a, &b, &c);
+    out[0][i] = a;
+    out[1][i] = b;
+    out[2][i] = c;
+  }
+  return kOk;
+}
+
 // InvPalette without deltas (palette.cc:29-100), last transform first: the index channel becomes num_c channels
 // again; one-channel palettes clamp the index into the table, the others use the implicit entries
 int UndoPalettes(std::vector<ModularChannel>& image, std::vector<ModularPalette>& palettes, uint32_t* nb_meta,
                  uint32_t image_bits) {
   const uint32_t bit_depth = std::min<uint32_t>(image_bits, 24);
   while (!palettes.empty()) {
+    if (palettes.back().rct) {
+      const int rc = UndoRct(image, palettes.back().begin_c, palettes.back().rct_type);
+      if (rc) return rc;
+      palettes.pop_back();
+      continue;
+    }
     const uint32_t c0 = palettes.back().begin_c + 1;
     if (*nb_meta < 1 || c0 >= image.size()) return kBad;
     const uint32_t nb = image[0].h;
@@ -1093,9 +1174,10 @@ struct PendingTransforms {  // of the frame's global image, until every group is
 int ModularDecodeImage(BitReader* br, std::vector<ModularChannel>& image, uint32_t stream_id,
                        const jxlhip_modular_tree* global, uint32_t max_chan_size, uint32_t image_bits,
                        PendingTransforms* pending = nullptr, const std::function<int(uint32_t)>* after_channel = nullptr,
-                       bool allow_lz77 = false, const char** why = nullptr) {
+                       bool allow_lz77 = false, const char** why = nullptr, ModularStreamOptions* opt = nullptr) {
   // allow_lz77: an entropy code with LZ77 is read with the 2-D special distances (jxlhip_modular_frame_decode; the
   // other callers keep refusing it).  why: where JXLHIP_ERR_UNSUPPORTED came from, as a static string.
+  // opt: the stream belongs to a regular Modular frame (ModularStreamOptions).
   // after_channel(c): channel c's samples are final -- called between the channels of a stream WITHOUT transforms only
   // (with a palette or a squeeze nothing is final before the end); a non-zero return stops the decode with that status
   if (image.empty()) return kOk;  // not even a group header (encoding.cc:558)
@@ -1103,9 +1185,17 @@ int ModularDecodeImage(BitReader* br, std::vector<ModularChannel>& image, uint32
   WpHeader wp;
   std::vector<ModularPalette> palettes;
   ModularSqueeze squeeze;
-  int rc = ReadModularGroupHeader(br, &use_global_tree, &wp, &palettes, pending ? &squeeze : nullptr);
-  if (rc == JXLHIP_ERR_UNSUPPORTED && why) *why = "a transform of the Modular frame (RCT, squeeze, delta palette)";
+  allow_lz77 = allow_lz77 || (opt && opt->lz77);
+  int rc = ReadModularGroupHeader(br, &use_global_tree, &wp, &palettes, pending ? &squeeze : nullptr, opt && opt->rct);
+  if (rc == JXLHIP_ERR_UNSUPPORTED && why)
+    *why = opt && opt->rct ? "a delta palette, or a squeeze inside a group's stream or in front of another transform"
+                           : "a transform of the Modular frame (RCT, squeeze, delta palette)";
   if (rc) return rc;
+  if (opt) opt->transforms = !palettes.empty() || squeeze.present;
+  // the hand-over rule of a regular Modular frame: nothing but RCTs over the three channels of a three-channel image
+  bool leave = opt && opt->leave_rcts && !squeeze.present && image.size() == 3 && !palettes.empty() &&
+               palettes.size() <= kMaxDeviceRcts;
+  for (const ModularPalette& t : palettes) leave = leave && t.rct && t.begin_c == 0;
   // MetaPalette with begin_c == end_c (palette.cc:171-200): the palette becomes channel 0 (nb_colors x 1, shifts -1),
   // the channel itself now holds indices
   // (several channels, begin_c .. begin_c + num_c - 1, of one shape share a table of num_c rows and leave ONE index
@@ -1118,6 +1208,7 @@ int ModularDecodeImage(BitReader* br, std::vector<ModularChannel>& image, uint32
       if (image[c].w != image[first].w || image[c].h != image[first].h || image[c].hshift != image[first].hshift ||
           image[c].vshift != image[first].vshift)
         return kBad;
+    if (t.rct) continue;  // (an RCT changes no shape: its MetaApply is that check, transform.cc:112-114)
     if (first >= nb_meta) nb_meta++;
     else nb_meta = nb_meta + 2 - t.num_c;  // (last < nb_meta: at least one stays)
     image.erase(image.begin() + (size_t)first + 1, image.begin() + (size_t)last + 1);
@@ -1135,6 +1226,11 @@ int ModularDecodeImage(BitReader* br, std::vector<ModularChannel>& image, uint32
     for (uint32_t i = 0; i < image.size() && !stops(i); i++) image[i].Resize(image[i].w, image[i].h);
   }
   auto undo = [&]() -> int {
+    if (leave) {  // the device undoes them per pixel (k_modular_emit), last-listed first
+      opt->left = true;
+      opt->program = (uint16_t)(palettes[0].rct_type | (palettes.size() > 1 ? palettes[1].rct_type << 8 : 0u));
+      return kOk;
+    }
     // (a squeezed global image stays squeezed even when this section held all of it: the groups look for THEIR
     // channels in the squeezed list and find none, dec_modular.cc:344-350; FinalizeDecoding undoes it)
     if (pending && (!complete || squeeze.present)) {  // the groups fill the rest first
@@ -1315,7 +1411,8 @@ int jxlhip_modular_ac_group_decode(jxlhip_modular_tree* global, const jxlhip_fra
 // (DecodeGroup's rectangle x0, y0, dim x dim in frame pixels, its shift bracket and stream)
 static int ModularGroupRects(const jxlhip_modular_tree* global, uint32_t x0, uint32_t y0, uint32_t dim, int min_shift,
                              int max_shift, uint32_t stream_id, const uint8_t* data, size_t size, size_t* bit_pos,
-                             std::vector<ModularChannel>* gi, std::vector<uint32_t>* which) {
+                             std::vector<ModularChannel>* gi, std::vector<uint32_t>* which,
+                             ModularStreamOptions* opt = nullptr) {
   ModularFull& f = *global->full;
   for (uint32_t c = f.FirstGroupChannel(); c < f.ch.size(); c++) {
     const ModularChannel& fc = f.ch[c];
@@ -1334,7 +1431,7 @@ static int ModularGroupRects(const jxlhip_modular_tree* global, uint32_t x0, uin
   }
   if (gi->empty()) return kOk;
   BitReader br(data, size, *bit_pos);
-  const int rc = ModularDecodeImage(&br, *gi, stream_id, global, 0xFFFFFFu, f.image_bits);
+  const int rc = ModularDecodeImage(&br, *gi, stream_id, global, 0xFFFFFFu, f.image_bits, nullptr, nullptr, false, nullptr, opt);
   if (rc) return rc;
   if (!br.Healthy() || gi->size() != which->size()) return kBad;
   for (size_t i = 0; i < which->size(); i++) {

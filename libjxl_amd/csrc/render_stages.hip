@@ -799,3 +799,98 @@ int jxlhip::DecodeFrameToneMapped(jxlhip_ctx* c, void* out, size_t out_stride) {
   HIPCHK(c, hipGetLastError());
   return JXLHIP_OK;
 }
+
+// ---- a regular Modular frame (lossless files): the host's integer planes and RCT programs onto the device, k_modular_emit
+// (kernels_modular.hip) into the caller's output -- through the orientation staging frame when undo_orientation asks.
+int jxlhip_decode_modular_frame(jxlhip_ctx* c, const jxlhip_modular_frame* m, uint32_t output_kind, const jxlhip_output_format* out_format,
+                                void* out, size_t out_stride, uint32_t undo_orientation) {
+  if (!c || !m) return JXLHIP_ERR_INVALID_ARGUMENT;
+  JXLHIP_NO_MULTI(c);
+  if (output_kind == JXLHIP_OUT_XYB_PLANAR) return Fail(c, JXLHIP_ERR_UNSUPPORTED, "planar XYB of a Modular frame that is not XYB");
+  if (output_kind > JXLHIP_OUT_PACKED || (output_kind == JXLHIP_OUT_PACKED && !out_format) || undo_orientation > 8)
+    return Fail(c, JXLHIP_ERR_INVALID_ARGUMENT, "bad output kind / orientation");
+  if (m->xsize == 0 || m->ysize == 0 || m->xsize > (1u << 19) || m->ysize > (1u << 19) || !m->planes[0] || !m->planes[1] || !m->planes[2] ||
+      m->stride_samples < m->xsize || m->sample_type > JXLHIP_MODULAR_I32 || m->bits_per_sample == 0 || m->bits_per_sample > 16)
+    return Fail(c, JXLHIP_ERR_INVALID_ARGUMENT, "bad Modular frame: %ux%u, %u bits, sample type %u, stride %zu", m->xsize, m->ysize,
+                m->bits_per_sample, m->sample_type, m->stride_samples);
+  uint32_t shift = 0;
+  while (shift < 11 && (1u << shift) != m->group_dim) shift++;
+  if (shift < 7 || shift > 10) return Fail(c, JXLHIP_ERR_INVALID_ARGUMENT, "group dimension %u", m->group_dim);
+  jxlhip_output_format fmt{};
+  if (output_kind == JXLHIP_OUT_PACKED) {  // (as jxlhip_frame_begin; the transfer function is not read)
+    fmt = *out_format;
+    const uint32_t max_bits = fmt.sample_type == JXLHIP_SAMPLE_U8 ? 8 : 16;
+    if (fmt.sample_type > JXLHIP_SAMPLE_F16 || (fmt.num_channels != 3 && fmt.num_channels != 4) || fmt.swap_endianness > 1 ||
+        ((fmt.sample_type == JXLHIP_SAMPLE_U8 || fmt.sample_type == JXLHIP_SAMPLE_U16) && (fmt.bits_per_sample == 0 || fmt.bits_per_sample > max_bits)))
+      return Fail(c, JXLHIP_ERR_INVALID_ARGUMENT, "bad output format");
+  }
+  const uint32_t W = m->xsize, H = m->ysize;
+  const uint32_t xsg = ((W - 1) >> shift) + 1, ysg = ((H - 1) >> shift) + 1;
+  const size_t ng = (size_t)xsg * ysg;
+  auto bad_program = [](uint32_t p) { return (p & 0xFFu) > 41u || (p >> 8) > 41u; };
+  bool bad = bad_program(m->global_rct);
+  for (size_t g = 0; m->group_rct && g < ng; g++) bad = bad || bad_program(m->group_rct[g]);
+  if (bad) return Fail(c, JXLHIP_ERR_INVALID_ARGUMENT, "an RCT type above 41");
+  // the target: the caller's buffer, or -- undo_orientation -- the staging frame k_orient reads
+  OutTarget t{output_kind, fmt, FilterParams{}};
+  const size_t bpp = OutPixelBytes(output_kind, fmt);
+  const bool oriented = undo_orientation > 1, transposed = undo_orientation >= 5;
+  t.fp.out = out;
+  t.fp.out_stride = out_stride;
+  t.fp.fmt = fmt;
+  int rc;
+  if ((rc = CheckOutArgs(c, t, transposed ? H : W, transposed ? W : H))) return rc;
+  HIPCHK(c, hipSetDevice(c->device));
+  if (oriented) {
+    const size_t row = ((size_t)W * bpp + 255) & ~(size_t)255;
+    if ((rc = c->orient_dev.Reserve(c, (size_t)H * row))) return rc;
+    t.fp.out = c->orient_dev;
+    t.fp.out_stride = row;
+  }
+  if (output_kind == JXLHIP_OUT_PACKED) {
+    const bool is_int = fmt.sample_type == JXLHIP_SAMPLE_U8 || fmt.sample_type == JXLHIP_SAMPLE_U16;
+    t.fp.sample_mul = is_int ? (float)((1u << fmt.bits_per_sample) - 1u) : 1.0f;  // stage_write.cc:528
+    t.fp.dither = c->tables + kTabDither;
+  }
+  {  // the 8-bit dither pattern follows the flipped coordinates (jxlhip_frame_begin)
+    const uint32_t o = undo_orientation;
+    const bool fx = o == 2 || o == 3 || o == 7 || o == 8, fy = o == 3 || o == 4 || o == 6 || o == 7;
+    t.fp.dither_x0 = fx ? (int32_t)W - 1 : 0;
+    t.fp.dither_xs = fx ? -1 : 1;
+    t.fp.dither_y0 = fy ? (int32_t)H - 1 : 0;
+    t.fp.dither_ys = fy ? -1 : 1;
+  }
+  // the planes and the programs onto the device: rows padded to 64 samples, planes to 256 bytes
+  const size_t ssz = m->sample_type == JXLHIP_MODULAR_I16 ? 2 : 4;
+  const uint32_t ns = (W + 63u) & ~63u;
+  const size_t plane_bytes = ((size_t)ns * H * ssz + 255) & ~(size_t)255;
+  if ((3 * plane_bytes > c->modular_dev.n || ng > c->modular_rct_dev.n) && Capturing(c->stream))  // (a synchronise and an allocation)
+    return Fail(c, JXLHIP_ERR_UNSUPPORTED, "a Modular frame while the stream is being captured and its planes have to grow");
+  if ((rc = c->modular_dev.Reserve(c, 3 * plane_bytes))) return rc;
+  if ((rc = c->modular_rct_dev.Reserve(c, ng))) return rc;
+  ModularEmitArgs A{};
+  for (int ch = 0; ch < 3; ch++) {
+    uint8_t* dst = c->modular_dev + ch * plane_bytes;
+    HIPCHK(c, hipMemcpy2DAsync(dst, (size_t)ns * ssz, m->planes[ch], m->stride_samples * ssz, (size_t)W * ssz, H, hipMemcpyHostToDevice, c->stream));
+    A.plane[ch] = dst;
+  }
+  if (m->group_rct) HIPCHK(c, hipMemcpyAsync(c->modular_rct_dev, m->group_rct, ng * sizeof(uint16_t), hipMemcpyHostToDevice, c->stream));
+  else HIPCHK(c, hipMemsetAsync(c->modular_rct_dev, 0, ng * sizeof(uint16_t), c->stream));
+  A.xsize = W;
+  A.ysize = H;
+  A.ns = ns;
+  A.sample_type = m->sample_type;
+  A.group_shift = shift;
+  A.xsg = xsg;
+  A.group_rct = c->modular_rct_dev;
+  A.global_rct = m->global_rct;
+  A.factor = (float)(1.0 / (double)((1u << m->bits_per_sample) - 1u));  // dec_modular.cc:584-586
+  if (!LaunchModularEmit(A, t.fp, (int)output_kind, c->stream)) return Fail(c, JXLHIP_ERR_INVALID_ARGUMENT, "Modular emit launch arguments");
+  HIPCHK(c, hipGetLastError());
+  if (oriented) {
+    if (!LaunchOrient(c->orient_dev, t.fp.out_stride, W, H, (uint32_t)bpp, undo_orientation, out, out_stride, c->stream))
+      return Fail(c, JXLHIP_ERR_UNSUPPORTED, "undo_orientation %u with %zu-byte pixels", undo_orientation, bpp);
+    HIPCHK(c, hipGetLastError());
+  }
+  return JXLHIP_OK;
+}

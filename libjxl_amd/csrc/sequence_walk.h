@@ -33,19 +33,40 @@ struct ParsedHeaders {
   float luminances[3];   // luminance weights of that space
   size_t icc_size;       // size of the original's ICC profile (0 = an enumerated colour encoding)
   float display_nits = 0.0f;  // jxlhip_codestream_set_display: the display's peak when the frames are tone-mapped to it (0: not)
+  bool modular = false;  // a lossless file: the image is not XYB encoded and its one frame is a regular Modular frame
 };
 
 // the image header, the ICC profile, the extra channels' eligibility and the colour set-up; *pos_out = the first frame
 // header, *info_out = what the frame headers' conditions read from the image header.  sequence: the caller walks every
-// frame of the file (WalkSequence) and takes animations.
-inline int ParseImagePart(const uint8_t* cs, size_t n, ParsedHeaders* h, size_t* pos_out, jxlhip_image_info* info_out, bool sequence) {
+// frame of the file (WalkSequence) and takes animations.  lossless: the caller takes an image that is not XYB encoded (a
+// lossless file: jxlhip_codestream_basic_info, jxlhip_decode_codestream[_extra]); h->modular then says it is one, and
+// the image-level cases that path refuses are named in h->why.
+inline int ParseImagePart(const uint8_t* cs, size_t n, ParsedHeaders* h, size_t* pos_out, jxlhip_image_info* info_out, bool sequence,
+                          bool lossless = false) {
   size_t pos = 0;
   int rc = jxlhip_image_header_decode(cs, n, &pos, h->extra, 4, &h->ih);
   if (rc) return rc;
   const jxlhip_image_header& ih = h->ih;
   h->icc_size = 0;
   if (sequence && ih.have_preview) h->why = "a preview";
-  if (!ih.xyb_encoded || ih.num_extra_channels > 4 || ih.have_preview || (ih.have_animation && !sequence)) return JXLHIP_ERR_UNSUPPORTED;
+  if (!ih.xyb_encoded && !lossless) return JXLHIP_ERR_UNSUPPORTED;
+  h->modular = !ih.xyb_encoded;
+  if (h->modular) {  // the samples are the original's integers: what the Modular path cannot turn into pixels
+    auto refuse = [&](const char* why) {
+      h->why = why;
+      return JXLHIP_ERR_UNSUPPORTED;
+    };
+    const jxlhip_color_encoding& ce = ih.color_encoding;
+    if (ih.have_preview) return refuse("a lossless file with a preview");
+    if (ih.have_animation) return refuse("a lossless animation");
+    if (ih.num_extra_channels != 0) return refuse("a lossless image with extra channels");
+    if (ih.bit_depth.floating_point_sample || ih.bit_depth.bits_per_sample == 0 || ih.bit_depth.bits_per_sample > 16)
+      return refuse("a lossless image of float samples or more than 16 bits");
+    if (ce.want_icc) return refuse("a lossless image with an ICC profile");
+    if (!ce.all_default && ce.color_space == JXLHIP_CS_GRAY) return refuse("a lossless grey (one-channel) image");
+    if (!ce.all_default && ce.color_space != JXLHIP_CS_RGB) return refuse("a lossless image in a colour space other than RGB");
+  }
+  if (ih.num_extra_channels > 4 || ih.have_preview || (ih.have_animation && !sequence)) return JXLHIP_ERR_UNSUPPORTED;
   // an ICC original: the coded profile sits between the image header and the frame; it has to be decoded to find
   // its end (jxlhip_codestream_icc_profile hands it out).  Pixels: linear sRGB, like the reference without a CMS
   if (ih.color_encoding.want_icc && (rc = jxlhip_icc_decode(cs, n, &pos, nullptr, 0, &h->icc_size))) return rc;
@@ -64,7 +85,13 @@ inline int ParseImagePart(const uint8_t* cs, size_t n, ParsedHeaders* h, size_t*
   // matrix is adapted to the original's primaries / white point as OutputEncodingInfo::SetColorEncoding does
   // (dec_xyb.cc:180-249); the caller applies the original's transfer function through out_format (the info struct
   // says which).  ICC and grey originals are outside this front-end.
-  if ((rc = jxlhip_output_opsin_matrix(&ih, h->inv_matrix, h->luminances))) return rc;
+  if (h->modular) {  // (no XYB stage: the matrix is not used; the luminances are sRGB's, for the info struct)
+    static const float kIdentity[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1}, kLuminances[3] = {0.2126f, 0.7152f, 0.0722f};
+    memcpy(h->inv_matrix, kIdentity, sizeof(kIdentity));
+    memcpy(h->luminances, kLuminances, sizeof(kLuminances));
+  } else if ((rc = jxlhip_output_opsin_matrix(&ih, h->inv_matrix, h->luminances))) {
+    return rc;
+  }
   jxlhip_image_info info{};
   info.xsize = ih.xsize;
   info.ysize = ih.ysize;
