@@ -640,6 +640,35 @@ typedef struct jxlhip_modular_frame {
 JXLHIP_EXPORT int jxlhip_decode_modular_frame(jxlhip_ctx* ctx, const jxlhip_modular_frame* frame, uint32_t output_kind,
                                               const jxlhip_output_format* out_format, void* out, size_t out_stride,
                                               uint32_t undo_orientation);
+/* jxlhip_decode_modular_channels: the same stage for what jxlhip_modular_image_decode_channels (jxl_hip_frame.h) leaves
+ * of an image with an alpha channel and / or a grey image.  jxlhip_decode_modular_frame is this call with num_color = 3
+ * and no alpha plane, and that case -- also three colour planes whose alpha cannot reach the output -- is launched as
+ * k_modular_emit exactly as before; everything else is the sibling kernel k_modular_planes:
+ *   alpha_plane: a fourth integer plane, same rows and sample type as the colour (uploaded as integers: half or a quarter
+ *     of a float plane), converted in the kernel with ITS factor, (float)(1.0 / (2^alpha_bits - 1)) -- alpha_bits need
+ *     not be bits_per_sample --, and written as the fourth channel of a 4-channel JXLHIP_OUT_PACKED output like a colour
+ *     channel, minus the transfer function (stage_write.cc:350-366); never un-premultiplied.  Every other output (three
+ *     floats, 3 channels) has no room for it: the plane is neither uploaded nor read.  NULL: the opaque value.
+ *   num_color = 1: a grey image -- planes[0] alone, no RCT (a non-zero program is JXLHIP_ERR_INVALID_ARGUMENT), the
+ *     sample written to R, G and B, as the reference's pipeline carries a grey image.
+ * Everything else as jxlhip_decode_modular_frame.  JXLHIP_ERR_INVALID_ARGUMENT also for num_color outside {1, 3} and
+ * alpha_bits outside 1..16 with an alpha plane. */
+typedef struct jxlhip_modular_channels {
+  uint32_t xsize, ysize;
+  uint32_t num_color;         /* 3, or 1 (grey) */
+  const void* planes[3];      /* host; planes[1], planes[2] not read when num_color == 1 */
+  const void* alpha_plane;    /* host, NULL = none */
+  uint32_t alpha_bits;        /* of the alpha channel: 1..16 */
+  size_t stride_samples;      /* of every plane, >= xsize */
+  uint32_t sample_type;       /* of every plane */
+  uint32_t bits_per_sample;   /* of the colour: 1..16 */
+  uint32_t group_dim;
+  const uint16_t* group_rct;
+  uint16_t global_rct;
+} jxlhip_modular_channels;
+JXLHIP_EXPORT int jxlhip_decode_modular_channels(jxlhip_ctx* ctx, const jxlhip_modular_channels* frame, uint32_t output_kind,
+                                                 const jxlhip_output_format* out_format, void* out, size_t out_stride,
+                                                 uint32_t undo_orientation);
 
 /* Debug/test taps on context-owned intermediates (device pointers).
  * export_xyb: row-major copy of the phase-1 result, rows [first row of the

@@ -26,12 +26,16 @@
  * jxlhip_set_patches), of images without extra channels.  The four reference slots of the context are cleared at the
  * start of every call; the info struct describes the visible frame.
  * Also taken: lossless files -- an image that is NOT XYB encoded in one regular Modular frame, what `cjxl -d 0` writes
- * (info->modular = 1): 8..16-bit integer RGB samples with an enumerated colour encoding, any group_size_shift, RCTs (all
- * 42 types, global and per group), palettes without deltas, LZ77.  Such a frame has a stage path of its own
+ * (info->modular = 1): 8..16-bit integer RGB or grey samples with an enumerated colour encoding, up to four extra channels
+ * (alpha, depth, ...: full size, integer, at most 16 bits; info reports them as for VarDCT files; alpha_associated is
+ * taken and nothing un-premultiplies), any group_size_shift, RCTs (all 42 types, global and per group), palettes without
+ * deltas, LZ77.  The first alpha channel is the fourth channel of a 4-channel JXLHIP_OUT_PACKED output (uploaded as an
+ * integer plane, converted by the kernel); jxlhip_decode_codestream_extra fills extra_planes with
+ * v * (float)(1.0 / (2^bits - 1)) of each channel's own depth, what a VarDCT file's channels get.  Such a frame has a stage path of its own
  * (frame_decode.hip: DecodeModularFrameAt): headers; DC global = the DC dequant bit and the global Modular image; the
  * ModularDC stream of every DC group and the ModularAC stream of every group on the runner (jxlhip_modular_image_decode's
  * stages, jxl_hip_frame.h); the integer planes and RCT programs uploaded and turned into pixels by ONE kernel
- * (jxlhip_decode_modular_frame, jxl_hip.h); jxlhip_sync.  The pixels are the original's samples: out_format->transfer
+ * (jxlhip_decode_modular_channels, jxl_hip.h); jxlhip_sync.  The pixels are the original's samples: out_format->transfer
  * must be the original's (info->transfer_function; JXLHIP_OUT_LINEAR_RGB_F32 wants a linear original), anything else is
  * JXLHIP_ERR_UNSUPPORTED with the reason in jxlhip_last_error -- JxlDecoder without a CMS cannot convert either --, and so
  * are JXLHIP_OUT_XYB_PLANAR and a display (jxlhip_codestream_set_display) with any field set.  jxlhip_codestream_phase_ms
@@ -42,9 +46,10 @@
  * jxlhip_decode_codestream_next below (blended on the device, jxlhip_set_blending); the single-frame calls refuse them.
  * Everything this front-end does not decode is refused with JXLHIP_ERR_UNSUPPORTED so that the caller can hand the
  * file to libjxl's CPU decoder: of lossless files, each with a named reason: XYB or YCbCr Modular regular frames, a
- * squeeze on the colour channels (`cjxl -p`), delta palettes, float samples or more than 16 bits, grey images, ICC
- * originals, images with extra channels, upsampling != 1, any frame flag, a loop filter, more than one pass, chroma
- * subsampling, previews -- and every lossless file by the sequence calls and the partial call, as before; then
+ * squeeze on the colour channels (`cjxl -p`), delta palettes, float samples or more than 16 bits, ICC originals, more
+ * than four extra channels, a sub-sampled extra channel (dim_shift != 0 or an upsampling factor of its own), float extra
+ * channels or ones deeper than 16 bits, a colour or extra-channel blend mode other than kReplace, upsampling != 1, any
+ * frame flag, a loop filter, more than one pass, chroma subsampling, previews -- and every lossless file by the sequence calls and the partial call, as before; then
  * animation / layers / any other sequence of frames (single-frame
  * calls; the sequence calls blend images with extra channels too when asked to, and refuse VarDCT
  * reference-only frames, regular frames saved before the colour transform and kSkipProgressive), previews,

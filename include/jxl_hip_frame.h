@@ -421,10 +421,11 @@ JXLHIP_EXPORT int jxlhip_modular_frame_decode(const uint8_t* data, size_t size, 
  * data / size / *bit_pos: the codestream, and the first bit behind the frame header (the TOC); *bit_pos advances to the
  * first bit behind the frame's sections.  planes: see the struct.
  * JXLHIP_ERR_UNSUPPORTED with *why (may be NULL) naming the case in a static string: an XYB or YCbCr Modular frame, a
- * squeeze on the colour channels (`cjxl -p`), delta palettes, an image with extra channels, upsampling != 1, any frame
- * flag, a loop filter, more than one pass, chroma subsampling, a frame that is not a full-size regular frame.  (The
- * image-level cases -- float samples or more than 16 bits, grey images, ICC originals, previews -- are the whole-file
- * calls', jxl_hip_codestream.h: this entry sees the frame header only.)  JXLHIP_ERR_RANGE: a sample does not fit
+ * squeeze on the colour channels (`cjxl -p`), delta palettes, an image with extra channels (THIS entry: the one below
+ * takes them, and grey images), upsampling != 1, any frame flag, a loop filter, more than one pass, chroma subsampling,
+ * a frame that is not a full-size regular frame.  (The image-level cases -- float samples or more than 16 bits, ICC
+ * originals, previews, float or deeper-than-16-bit or sub-sampled extra channels, more than four of them -- are the
+ * whole-file calls', jxl_hip_codestream.h: this entry sees the frame header only.)  JXLHIP_ERR_RANGE: a sample does not fit
  * JXLHIP_MODULAR_I16 planes (an image whose modular_16_bit_buffer_sufficient is wrong): decode again with
  * JXLHIP_MODULAR_I32.  JXLHIP_ERR_BAD_STREAM where the reference rejects the stream and on truncation. */
 typedef struct jxlhip_modular_image_planes {  /* (JXLHIP_MODULAR_I16 / _I32, JXLHIP_MODULAR_MAX_RCTS: jxl_hip.h) */
@@ -443,6 +444,42 @@ typedef struct jxlhip_modular_image_planes {  /* (JXLHIP_MODULAR_I16 / _I32, JXL
 JXLHIP_EXPORT int jxlhip_modular_image_decode(const uint8_t* data, size_t size, size_t* bit_pos,
                                               const jxlhip_frame_header* frame, jxlhip_parallel_runner runner,
                                               void* runner_opaque, jxlhip_modular_image_planes* planes, const char** why);
+
+/* The same frame of an image WITH extra channels (alpha, depth, ...: what an RGBA PNG becomes) and / or of a GREY image:
+ * jxlhip_modular_image_decode_channels.  The three-plane entry above keeps refusing both and is this entry with
+ * num_color = 3, num_extra = 0.  The global Modular image has num_color + num_extra channels: the colour channels --
+ * three, or ONE for a grey image, whose frame has colour transform none (dec_modular.cc:215-219) -- and behind them the
+ * extra channels, each at the frame's size.  The caller says which from the IMAGE header (the frame header does not know
+ * a grey image): num_color, and for each extra channel a plane of its own and its bit depth.
+ * The split, with N channels: a stream's list stays (group_rct / global_rct) only when it is 1..JXLHIP_MODULAR_MAX_RCTS
+ * RCTs with begin_c == 0 on an image of THREE colour channels -- they touch the colour planes alone.  Everything else is
+ * undone on the host as above: any palette (the 4-channel RGBA palette included), an RCT that starts at another channel
+ * and so reaches an extra channel, every list of a grey image.  Extra-channel planes are final: nobody transforms them.
+ * sample_type covers ALL planes: JXLHIP_ERR_RANGE when a sample of any of them does not fit JXLHIP_MODULAR_I16.
+ * Refused by name beyond the list above: more than JXLHIP_MODULAR_MAX_EXTRA extra channels, a sub-sampled extra channel
+ * (ec_upsampling != 1), a colour or extra-channel blend mode other than kReplace on this one full-size frame.  (Float
+ * extra channels and ones deeper than 16 bits are image-level: the whole-file calls name them.)  alpha_associated is no
+ * refusal: nothing un-premultiplies, like JxlDecoder by default.  JXLHIP_ERR_INVALID_ARGUMENT: num_color not 1 or 3,
+ * num_extra != frame->num_extra_channels, a NULL plane among the num_color + num_extra, extra_bits outside 1..16. */
+#define JXLHIP_MODULAR_MAX_EXTRA 4
+typedef struct jxlhip_modular_image_channels {
+  /* in */
+  uint32_t num_color;       /* 3, or 1: a grey image (planes[1], planes[2] are not read) */
+  uint32_t num_extra;       /* frame->num_extra_channels: 0..JXLHIP_MODULAR_MAX_EXTRA */
+  void* planes[3];          /* the colour planes, as jxlhip_modular_image_planes */
+  void* extra_planes[JXLHIP_MODULAR_MAX_EXTRA];  /* extra channel e: same rows, same sample type */
+  uint32_t extra_bits[JXLHIP_MODULAR_MAX_EXTRA]; /* its bits_per_sample (1..16): what its samples are divided by later */
+  size_t stride_samples;
+  uint32_t sample_type;
+  uint16_t* group_rct;
+  /* out: as jxlhip_modular_image_planes */
+  uint16_t global_rct;
+  uint32_t global_tree, global_on_host, groups_on_device, groups_on_host;
+} jxlhip_modular_image_channels;
+JXLHIP_EXPORT int jxlhip_modular_image_decode_channels(const uint8_t* data, size_t size, size_t* bit_pos,
+                                                       const jxlhip_frame_header* frame, jxlhip_parallel_runner runner,
+                                                       void* runner_opaque, jxlhip_modular_image_channels* channels,
+                                                       const char** why);
 
 /* One DC group section (section 1 + dc_group of the TOC).  All outputs are FRAME-level arrays in the
  * layouts jxlhip_upload_side_info / jxlhip_dequant_dc take, of which this call fills the group's

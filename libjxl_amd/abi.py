@@ -20,6 +20,7 @@ BLEND_REPLACE, BLEND_ADD, BLEND_BLEND, BLEND_ALPHA_WEIGHTED_ADD, BLEND_MUL = ran
 BLEND_NO_SAVE = 0xFFFFFFFF
 MODULAR_I16, MODULAR_I32 = 0, 1  # jxlhip_modular_frame::sample_type / jxlhip_modular_image_planes::sample_type
 MODULAR_MAX_RCTS = 2
+MODULAR_MAX_EXTRA = 4  # jxlhip_modular_image_channels: extra channels beside the colour
 # the sequence calls take frames that need blending on images with extra channels: JXLHIP_SEQUENCE_EXTRA_CHANNELS
 # (jxlhip_codestream_sequence_info_ex's flags), JXLHIP_OUT_BLEND_EXTRA_CHANNELS (jxlhip_decode_codestream_next's output_kind)
 SEQUENCE_EXTRA_CHANNELS = 1
@@ -202,6 +203,23 @@ class ModularFrame(C.Structure):
                 ("group_rct", C.c_void_p), ("global_rct", C.c_uint16)]
 
 
+class ModularImageChannels(C.Structure):
+    """jxlhip_modular_image_channels (include/jxl_hip_frame.h)."""
+    _fields_ = [("num_color", C.c_uint32), ("num_extra", C.c_uint32), ("planes", C.c_void_p * 3),
+                ("extra_planes", C.c_void_p * 4), ("extra_bits", C.c_uint32 * 4), ("stride_samples", C.c_size_t),
+                ("sample_type", C.c_uint32), ("group_rct", C.c_void_p), ("global_rct", C.c_uint16),
+                ("global_tree", C.c_uint32), ("global_on_host", C.c_uint32), ("groups_on_device", C.c_uint32),
+                ("groups_on_host", C.c_uint32)]
+
+
+class ModularChannels(C.Structure):
+    """jxlhip_modular_channels (include/jxl_hip.h)."""
+    _fields_ = [("xsize", C.c_uint32), ("ysize", C.c_uint32), ("num_color", C.c_uint32), ("planes", C.c_void_p * 3),
+                ("alpha_plane", C.c_void_p), ("alpha_bits", C.c_uint32), ("stride_samples", C.c_size_t),
+                ("sample_type", C.c_uint32), ("bits_per_sample", C.c_uint32), ("group_dim", C.c_uint32),
+                ("group_rct", C.c_void_p), ("global_rct", C.c_uint16)]
+
+
 class PartialInfo(C.Structure):
     """jxlhip_partial_info"""
     _fields_ = [(n, C.c_uint32) for n in ("complete", "num_passes", "num_groups", "groups_complete", "groups_partial",
@@ -319,7 +337,7 @@ EXPORTS = [
     "jxlhip_frame_begin", "jxlhip_frame_set_inputs", "jxlhip_upload_side_info",
     "jxlhip_submit_group", "jxlhip_set_alpha", "jxlhip_set_noise", "jxlhip_noise_rng_state", "jxlhip_set_splines", "jxlhip_set_upsampling", "jxlhip_set_dc_only_groups", "jxlhip_set_reference_frame", "jxlhip_set_patches", "jxlhip_set_blending", "jxlhip_set_tone_mapping", "jxlhip_tone_mapping_constants", "jxlhip_canvas_read", "jxlhip_set_blending_extra", "jxlhip_canvas_read_extra", "jxlhip_frame_extra_read", "jxlhip_profile_read_ex", "jxlhip_alpha_staging", "jxlhip_decode_blocks", "jxlhip_halo_rows",
     "jxlhip_halo_export", "jxlhip_halo_import", "jxlhip_decode_filters", "jxlhip_decode_filters_rows", "jxlhip_stripe_begin",
-    "jxlhip_stripe_finish", "jxlhip_decode_frame", "jxlhip_decode_modular_frame",
+    "jxlhip_stripe_finish", "jxlhip_decode_frame", "jxlhip_decode_modular_frame", "jxlhip_decode_modular_channels",
     "jxlhip_decode_frame_host", "jxlhip_decode_frame_pinned",
     "jxlhip_sync", "jxlhip_export_xyb", "jxlhip_get_sigma",
     "jxlhip_set_concurrency_hint", "jxlhip_debug_prepare_launches", "jxlhip_profile_enable", "jxlhip_profile_read",
@@ -338,6 +356,7 @@ EXPORTS = [
     "jxlhip_modular_ac_group_decode", "jxlhip_modular_ac_group_decode_f32", "jxlhip_modular_extra_channel_f32",
     "jxlhip_modular_groups_are_final", "jxlhip_modular_uses_dc_groups", "jxlhip_modular_finalize",
     "jxlhip_modular_extra_channel_rows_f32", "jxlhip_modular_ac_group_decode_f32_strided", "jxlhip_modular_image_decode",
+    "jxlhip_modular_image_decode_channels",
     # include/jxl_hip_codestream.h
     "jxlhip_codestream_basic_info", "jxlhip_decode_codestream", "jxlhip_decode_codestream_extra",
     "jxlhip_codestream_icc_profile", "jxlhip_codestream_phase_ms", "jxlhip_codestream_sequence_info", "jxlhip_codestream_sequence_info_ex",
@@ -491,6 +510,9 @@ def load_library():
     L.jxlhip_modular_image_decode.argtypes = [vp, sz, C.POINTER(sz), C.POINTER(FrameHeader), vp, vp, C.POINTER(ModularImagePlanes),
                                               C.POINTER(C.c_char_p)]
     L.jxlhip_decode_modular_frame.argtypes = [vp, C.POINTER(ModularFrame), u32, C.POINTER(OutputFormat), vp, sz, u32]
+    L.jxlhip_modular_image_decode_channels.argtypes = [vp, sz, C.POINTER(sz), C.POINTER(FrameHeader), vp, vp,
+                                                       C.POINTER(ModularImageChannels), C.POINTER(C.c_char_p)]
+    L.jxlhip_decode_modular_channels.argtypes = [vp, C.POINTER(ModularChannels), u32, C.POINTER(OutputFormat), vp, sz, u32]
     L.jxlhip_ac_global_decode_at.argtypes = [vp, sz, C.POINTER(sz), u32, u32, u32, vp, vp, C.POINTER(u32), C.POINTER(vp)]
     _lib = L
     return L

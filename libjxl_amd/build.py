@@ -186,6 +186,7 @@ def build(verbose=False):
     check_no_scratch(lib, "k_ec_blend")  # (... and up to four extra channels beside them, their alpha picked with selects)
     check_no_scratch(lib, "k_tone_map")  # (two pixels per thread and nothing indexed: scratch here means the register budget broke)
     check_no_scratch(lib, "k_modular_emit")  # (a run of 8 pixels per thread, indexed by constants only: a streaming kernel has no business in scratch)
+    check_no_scratch(lib, "k_modular_planes")  # (its sibling for an alpha plane and for grey frames: the same run, one more plane)
     check_no_scratch(lib, "k_dc_upsample8")  # (4 x 25 weights and 25 samples per thread live in registers: indexed by constants only)
     out = [lib]
     if have_runner:

@@ -58,11 +58,11 @@ int ParseHeaders(const uint8_t* cs, size_t n, ParsedHeaders* h, bool lossless) {
     if ((rc = ReadReferenceFrame(cs, n, h->fh, &pos, h))) return rc;
   }
   const jxlhip_frame_header& fh = h->fh;
-  if (h->modular) {  // the frame-level cases of the lossless path, each by name (ModularImageRefusal)
+  if (h->modular) {  // the frame-level cases of the lossless path, each by name (ModularImageChannelsRefusal)
     for (const ReferenceFrame& r : h->refs)
       if (r.xsize != 0) return h->why = "a lossless file with reference frames", JXLHIP_ERR_UNSUPPORTED;
     if (!fh.is_last) return h->why = "a lossless file of more than one frame", JXLHIP_ERR_UNSUPPORTED;
-    if (const char* what = ModularImageRefusal(&fh)) return h->why = what, JXLHIP_ERR_UNSUPPORTED;
+    if (const char* what = ModularImageChannelsRefusal(&fh)) return h->why = what, JXLHIP_ERR_UNSUPPORTED;
     if (fh.xsize != ih.xsize || fh.ysize != ih.ysize) return JXLHIP_ERR_UNSUPPORTED;
     h->frame_bit_pos = pos;
     return JXLHIP_OK;
@@ -329,10 +329,14 @@ int DecodeCodestreamImpl(jxlhip_ctx* c, jxlhip_parallel_runner runner, void* run
   if ((rc = ParseHeaders(b.cs, b.n, &h, true)))
     return Fail(c, rc, rc == JXLHIP_ERR_UNSUPPORTED ? (h.why[0] ? h.why : "stream uses features outside the VarDCT back-end") : "invalid headers");
   if ((rc = ApplyDisplay(c, &h))) return rc;
+  FrameCall& fc = call.fc;
+  fc.extra_planes = extra_planes;
+  fc.num_extra_planes = num_extra_planes;
+  fc.extra_stride = extra_stride;
   if (h.modular) {  // a lossless file: a stage path of its own (frame_decode.hip)
     jxlhip_codestream_info info;
     FillInfo(h, b.container, &info);
-    if ((rc = DecodeModularFrameAt(c, b.cs, b.n, h, call.fc, call.clock, &info))) return rc;
+    if ((rc = DecodeModularFrameAt(c, b.cs, b.n, h, fc, call.clock, &info))) return rc;
     if (info_out) *info_out = info;
     return JXLHIP_OK;
   }
@@ -340,10 +344,6 @@ int DecodeCodestreamImpl(jxlhip_ctx* c, jxlhip_parallel_runner runner, void* run
     if (h.refs[slot].xsize != 0 && (rc = SetReferenceSlot(c, slot, h.refs[slot]))) return rc;
   jxlhip_codestream_info info;
   FillInfo(h, b.container, &info);
-  FrameCall& fc = call.fc;
-  fc.extra_planes = extra_planes;
-  fc.num_extra_planes = num_extra_planes;
-  fc.extra_stride = extra_stride;
   fc.out_xsize = h.ih.xsize;
   fc.out_ysize = h.ih.ysize;
   if ((rc = DecodeFrameAt(c, b.cs, b.n, h, h.fh, h.frame_bit_pos, fc, call.clock, call.verbose, &info, nullptr))) return rc;

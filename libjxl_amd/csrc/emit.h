@@ -297,5 +297,103 @@ __device__ __forceinline__ void StorePackedPair(const FilterParams& P, DitherPtr
   }
 }
 
+// ---- The same three with the pixel's alpha sample handed in by the caller instead of read from FilterParams::alpha (a
+// float plane): k_modular_planes converts it from the frame's integer alpha plane in the lane that converts the colour.
+// alpha goes out like a colour channel, minus the transfer function (stage_write.cc:350-366); 1.0f is the opaque value.
+template <typename Sel, typename DitherPtr>
+__device__ __forceinline__ void PackSamples(const FilterParams& P, DitherPtr dither, int x, int y,
+                                            const float* rgb, float alpha, uint32_t* q) {
+  const jxlhip_output_format& F = P.fmt;
+  const uint32_t st = Sel::sample_type(F);
+  const uint32_t tf = Sel::transfer(F);
+  float v[4] = {rgb[0], rgb[1], rgb[2], alpha};
+  if (tf == JXLHIP_TF_HLG) HlgOotf(P, v);
+#pragma unroll
+  for (int c = 0; c < 3; c++) v[c] = ApplyTransfer(tf, v[c], P.tf_scale);
+  const bool dithered = st == JXLHIP_SAMPLE_U8;
+  if (st == JXLHIP_SAMPLE_U8 || st == JXLHIP_SAMPLE_U16) {
+#pragma unroll
+    for (int c = 0; c < 4; c++) q[c] = ToUnsigned(P, dither, v[c], x, y, c, dithered);
+    if (dithered) return;
+  } else if (st == JXLHIP_SAMPLE_F16) {
+#pragma unroll
+    for (int c = 0; c < 4; c++) q[c] = HalfBits(v[c]);
+  } else {
+#pragma unroll
+    for (int c = 0; c < 4; c++) q[c] = __float_as_uint(v[c]);
+  }
+  if (Sel::swap(F)) {
+#pragma unroll
+    for (int c = 0; c < 4; c++)
+      q[c] = st == JXLHIP_SAMPLE_F32 ? __builtin_bswap32(q[c]) : (uint32_t)Bswap16((uint16_t)q[c]);
+  }
+}
+
+template <typename Sel, typename DitherPtr>
+__device__ __forceinline__ void StorePackedPixel(const FilterParams& P, DitherPtr dither, char* row,
+                                                 int x, int y, const float* rgb, float alpha) {
+  const jxlhip_output_format& F = P.fmt;
+  const int nc = (int)Sel::channels(F);
+  const uint32_t st = Sel::sample_type(F);
+  uint32_t q[4];
+  PackSamples<Sel>(P, dither, x, y, rgb, alpha, q);
+  if (st == JXLHIP_SAMPLE_U8) {
+    uint8_t* d = (uint8_t*)row + (size_t)x * nc;
+    for (int c = 0; c < nc; c++) d[c] = (uint8_t)q[c];  // (the row may start at any byte: no wider store)
+  } else if (st == JXLHIP_SAMPLE_F32) {
+    uint32_t* d = (uint32_t*)row + (size_t)x * nc;
+    for (int c = 0; c < nc; c++) d[c] = q[c];
+  } else {
+    uint16_t* d = (uint16_t*)row + (size_t)x * nc;
+    for (int c = 0; c < nc; c++) d[c] = (uint16_t)q[c];
+  }
+}
+
+template <typename Sel, typename DitherPtr>
+__device__ __forceinline__ void StorePackedPair(const FilterParams& P, DitherPtr dither, char* row, int x, int y,
+                                                const float* rgb0, const float* rgb1, float alpha0, float alpha1) {
+  typedef uint32_t u2 __attribute__((ext_vector_type(2), aligned(4)));
+  typedef uint32_t u4 __attribute__((ext_vector_type(4), aligned(4)));
+  const jxlhip_output_format& F = P.fmt;
+  const bool rgba = Sel::channels(F) == 4;
+  const uint32_t st = Sel::sample_type(F);
+  uint32_t a[4], b[4];
+  PackSamples<Sel>(P, dither, x, y, rgb0, alpha0, a);
+  PackSamples<Sel>(P, dither, x + 1, y, rgb1, alpha1, b);
+  if (st == JXLHIP_SAMPLE_U8) {
+    if (rgba) {
+      __builtin_nontemporal_store(u2{a[0] | (a[1] << 8) | (a[2] << 16) | (a[3] << 24),
+                                     b[0] | (b[1] << 8) | (b[2] << 16) | (b[3] << 24)},
+                                  (u2*)(row + (size_t)x * 4));
+    } else {  // 6 bytes at a 2-byte aligned address
+      uint16_t* d = (uint16_t*)(row + (size_t)x * 3);
+      d[0] = (uint16_t)(a[0] | (a[1] << 8));
+      d[1] = (uint16_t)(a[2] | (b[0] << 8));
+      d[2] = (uint16_t)(b[1] | (b[2] << 8));
+    }
+  } else if (st == JXLHIP_SAMPLE_F32) {
+    uint32_t* d = (uint32_t*)row + (size_t)x * Sel::channels(F);
+    if (rgba) {
+      __builtin_nontemporal_store(u4{a[0], a[1], a[2], a[3]}, (u4*)d);
+      __builtin_nontemporal_store(u4{b[0], b[1], b[2], b[3]}, (u4*)(d + 4));
+    } else {  // (the fence: see the pair above)
+      __builtin_nontemporal_store(u4{a[0], a[1], a[2], b[0]}, (u4*)d);
+      asm volatile("" ::: "memory");
+      __builtin_nontemporal_store(u2{b[1], b[2]}, (u2*)(d + 4));
+    }
+  } else {  // 16-bit samples
+    uint32_t* d = (uint32_t*)(row + (size_t)x * Sel::channels(F) * 2);
+    if (rgba) {
+      __builtin_nontemporal_store(u4{a[0] | (a[1] << 16), a[2] | (a[3] << 16), b[0] | (b[1] << 16),
+                                     b[2] | (b[3] << 16)},
+                                  (u4*)d);
+    } else {
+      __builtin_nontemporal_store(u2{a[0] | (a[1] << 16), a[2] | (b[0] << 16)}, (u2*)d);
+      asm volatile("" ::: "memory");
+      __builtin_nontemporal_store(b[1] | (b[2] << 16), d + 2);
+    }
+  }
+}
+
 }  // namespace jxlhip
 #endif

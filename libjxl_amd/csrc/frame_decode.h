@@ -59,7 +59,8 @@ int DecodeFrameAt(jxlhip_ctx* c, const uint8_t* cs, size_t n, const ParsedHeader
 
 // The one frame of a lossless file (ParsedHeaders::modular: a regular Modular frame of an image that is not XYB
 // encoded), from its TOC to the pixels: the host decode of its sections into pinned integer planes
-// (modular_image.h), their upload and k_modular_emit (jxlhip_decode_modular_frame), jxlhip_sync.
+// (modular_image.h), their upload and k_modular_emit or k_modular_planes (jxlhip_decode_modular_channels), jxlhip_sync.
+// An alpha channel goes up as a fourth integer plane; extra-channel planes the caller asked for are filled on the host.
 int DecodeModularFrameAt(jxlhip_ctx* c, const uint8_t* cs, size_t n, const ParsedHeaders& h, const FrameCall& fc, PhaseClock& clock,
                          jxlhip_codestream_info* info);
 

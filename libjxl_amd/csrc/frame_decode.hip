@@ -911,7 +911,19 @@ int DecodeModularFrameAt(jxlhip_ctx* c, const uint8_t* cs, size_t n, const Parse
   if (asked != original)
     return Fail(c, JXLHIP_ERR_UNSUPPORTED, "a lossless (Modular) file comes out in its original's transfer function only (JXLHIP_TF_* %u asked, %u coded)",
                 asked, original);
-  if (fc.num_extra_planes) return Fail(c, JXLHIP_ERR_UNSUPPORTED, "extra-channel planes of a lossless (Modular) file");
+  // the channels: three colour planes, or the one of a grey image; behind them the image's extra channels.  The first
+  // alpha channel goes to the device when the output has a fourth channel for it; the others are decoded, as they must
+  // be, into ordinary memory and handed to the caller as float planes where asked for (jxlhip_decode_codestream_extra)
+  const jxlhip_color_encoding& ce = ih.color_encoding;
+  const uint32_t num_color = !ce.all_default && ce.color_space == JXLHIP_CS_GRAY ? 1 : 3, nec = ih.num_extra_channels;
+  const bool want_alpha = h.alpha_index >= 0 && fc.output_kind == JXLHIP_OUT_PACKED && fc.out_format->num_channels == 4;
+  float* user_plane[4] = {nullptr, nullptr, nullptr, nullptr};
+  bool want_planes = false;
+  for (uint32_t i = 0; i < nec && i < fc.num_extra_planes && i < 4; i++) {
+    user_plane[i] = fc.extra_planes[i];
+    want_planes = want_planes || user_plane[i];
+  }
+  if (want_planes && fc.extra_stride < ih.xsize) return Fail(c, JXLHIP_ERR_INVALID_ARGUMENT, "extra_stride below the image width");
   FrameDecode d{c, cs, n, h, ih, fh, fc, clock, false};
   int rc;
   if ((rc = d.ReadToc(h.frame_bit_pos))) return rc;
@@ -922,17 +934,26 @@ int DecodeModularFrameAt(jxlhip_ctx* c, const uint8_t* cs, size_t n, const Parse
   for (uint32_t type = ih.modular_16_bit_buffer_sufficient ? JXLHIP_MODULAR_I16 : JXLHIP_MODULAR_I32; type <= JXLHIP_MODULAR_I32; type++) {
     const size_t ssz = type == JXLHIP_MODULAR_I16 ? 2 : 4;
     const size_t plane = ((size_t)stride * fh.ysize * ssz + 255) & ~(size_t)255;
-    const size_t need = 3 * plane + (size_t)d.ng * sizeof(uint16_t);
+    const uint32_t dev_planes = num_color + (want_alpha ? 1u : 0u);
+    const size_t need = dev_planes * plane + (size_t)d.ng * sizeof(uint16_t);
     if (need > c->modular_host.bytes) {
       if ((rc = jxlhip_sync(c))) return rc;  // (nothing may still be reading the old planes)
       if (c->modular_host.Alloc(&c->mm, need)) return Fail(c, JXLHIP_ERR_OUT_OF_MEMORY, "pinned Modular planes of %zu bytes", need);
     }
     uint8_t* base = static_cast<uint8_t*>(c->modular_host.p);
-    jxlhip_modular_image_planes pl{};
-    for (int ch = 0; ch < 3; ch++) pl.planes[ch] = base + ch * plane;
+    jxlhip_modular_image_channels pl{};
+    pl.num_color = num_color;
+    pl.num_extra = nec;
+    for (uint32_t ch = 0; ch < num_color; ch++) pl.planes[ch] = base + ch * plane;
+    std::vector<uint8_t> others;  // the extra channels that do not go to the device
+    others.resize((size_t)(nec - (want_alpha ? 1u : 0u)) * plane);
+    for (uint32_t e = 0, k = 0; e < nec; e++) {
+      pl.extra_planes[e] = want_alpha && (int)e == h.alpha_index ? base + num_color * plane : others.data() + (k++) * plane;
+      pl.extra_bits[e] = h.extra[e].bit_depth.bits_per_sample;
+    }
     pl.stride_samples = stride;
     pl.sample_type = type;
-    pl.group_rct = reinterpret_cast<uint16_t*>(base + 3 * plane);
+    pl.group_rct = reinterpret_cast<uint16_t*>(base + dev_planes * plane);
     // ---- DC global: the DC dequant bit, the global tree, the global Modular image
     const char* why = "";
     ModularImage* raw = nullptr;
@@ -955,18 +976,39 @@ int DecodeModularFrameAt(jxlhip_ctx* c, const uint8_t* cs, size_t n, const Parse
     clock.Mark(JXLHIP_PHASE_AC_GROUPS);
     if (rc == JXLHIP_ERR_RANGE && type == JXLHIP_MODULAR_I16) continue;  // (the header's promise did not hold: int32 planes)
     if (rc) return Fail(c, rc, "invalid Modular frame");
-    // ---- upload, k_modular_emit, sync
-    jxlhip_modular_frame m{};
+    // ---- the caller's extra-channel planes: v * (float)(1.0 / (2^bits - 1)) with the channel's own depth, what
+    // jxlhip_modular_extra_channel_f32 gives a VarDCT file's channels (dec_modular.cc:726-731)
+    for (uint32_t e = 0; e < nec && e < 4; e++) {
+      if (!user_plane[e]) continue;
+      const float factor = (float)(1.0 / (double)((1u << pl.extra_bits[e]) - 1u));
+      for (uint32_t y = 0; y < fh.ysize; y++) {
+        float* to = user_plane[e] + (size_t)y * fc.extra_stride;
+        if (type == JXLHIP_MODULAR_I16) {
+          const int16_t* from = static_cast<const int16_t*>(pl.extra_planes[e]) + (size_t)y * stride;
+          for (uint32_t x = 0; x < fh.xsize; x++) to[x] = (float)from[x] * factor;
+        } else {
+          const int32_t* from = static_cast<const int32_t*>(pl.extra_planes[e]) + (size_t)y * stride;
+          for (uint32_t x = 0; x < fh.xsize; x++) to[x] = (float)from[x] * factor;
+        }
+      }
+    }
+    // ---- upload, k_modular_emit or k_modular_planes, sync
+    jxlhip_modular_channels m{};
     m.xsize = fh.xsize;
     m.ysize = fh.ysize;
-    for (int ch = 0; ch < 3; ch++) m.planes[ch] = pl.planes[ch];
+    m.num_color = num_color;
+    for (uint32_t ch = 0; ch < num_color; ch++) m.planes[ch] = pl.planes[ch];
+    if (want_alpha) {
+      m.alpha_plane = pl.extra_planes[h.alpha_index];
+      m.alpha_bits = pl.extra_bits[h.alpha_index];
+    }
     m.stride_samples = stride;
     m.sample_type = type;
     m.bits_per_sample = ih.bit_depth.bits_per_sample;
     m.group_dim = fh.group_dim;
     m.group_rct = pl.group_rct;
     m.global_rct = pl.global_rct;
-    if ((rc = jxlhip_decode_modular_frame(c, &m, fc.output_kind, fc.out_format, fc.out, fc.out_stride, fc.undo_orientation ? ih.orientation : 0)))
+    if ((rc = jxlhip_decode_modular_channels(c, &m, fc.output_kind, fc.out_format, fc.out, fc.out_stride, fc.undo_orientation ? ih.orientation : 0)))
       return rc;
     if ((rc = jxlhip_sync(c))) return rc;
     clock.Mark(JXLHIP_PHASE_KERNELS);

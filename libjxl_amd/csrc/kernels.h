@@ -285,6 +285,17 @@ struct ModularEmitArgs {
 // JXLHIP_OUT_PACKED; p.fmt.transfer is not read: the tail runs with the identity) into p.out.  False for another kind or
 // bad geometry / alignment.
 bool LaunchModularEmit(const ModularEmitArgs& A, const FilterParams& p, int output_kind, hipStream_t st);
+// The same frame with an integer alpha plane and / or ONE colour plane (a grey image): k_modular_planes, the sibling of
+// k_modular_emit for the two cases that kernel cannot express.
+struct ModularPlanesArgs {
+  ModularEmitArgs e;     // num_color == 1: plane[0] alone is read, and every program must be 0 (group_rct may be NULL)
+  uint32_t num_color;    // 3, or 1: the sample goes to R, G and B
+  const void* alpha;     // device, 16-byte aligned, rows of e.ns samples of e.sample_type; NULL = the opaque value
+  float alpha_factor;    // (float)(1.0 / (2^alpha_bits - 1))
+};
+// Three colour planes without an alpha plane that reaches the output (none, or an output without a fourth channel) are
+// k_modular_emit's launch, unchanged; everything else is k_modular_planes.  False as LaunchModularEmit.
+bool LaunchModularPlanes(const ModularPlanesArgs& A, const FilterParams& p, int output_kind, hipStream_t st);
 
 // Upsampling (kernels_upsample.hip).  The coded frame is cut into 64 x 16 tiles; every coded pixel gives n x n output
 // pixels, each a 25-tap sum over its 5 x 5 neighbourhood clamped to the neighbourhood's range.

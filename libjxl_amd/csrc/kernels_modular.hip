@@ -18,6 +18,8 @@
 // sample type: float RGB (96 contiguous bytes per run), the general packed tail FmtSel<-1> (pairs of pixels through
 // StorePackedPair), and 8-bit RGB / RGBA with the format fixed at compile time and the run stored as 24 / 32 contiguous
 // bytes (taken when the output rows are 4-byte aligned).
+// Below it k_modular_planes: the same stage for frames with an integer alpha plane and for grey frames
+// (jxlhip_decode_modular_channels); RGB without alpha stays k_modular_emit's.
 #include "dev_common.h"
 #include "emit.h"
 #include "kernels.h"
@@ -201,6 +203,193 @@ bool LaunchTyped(const ModularEmitArgs& A, const FilterParams& p, int output_kin
   return true;
 }
 
+// ---- k_modular_planes: the sibling of k_modular_emit for the two cases that kernel cannot express -- an integer ALPHA
+// plane beside the colour (a fourth 16-byte load per piece; converted with a factor of its own, (float)(1.0 / (2^alpha_bits
+// - 1)); packed like a colour channel minus the transfer function: emit.h's forms that take the alpha sample) and a GREY
+// image (NC = 1: one colour plane, no programs, the sample replicated into R, G and B as the reference's pipeline carries
+// it).  Same shape and budget: a lane owns a run of 8 pixels that never straddles a group, the scalar tail takes the
+// right edge, no LDS, no scratch, at most 64 registers.  Three colour planes without alpha never come here.
+template <typename S, int NC, bool ALPHA, int OUTK, int FMT>
+__global__ __launch_bounds__(kRunsPerBlock) __attribute__((amdgpu_waves_per_eu(8))) void k_modular_planes(ModularPlanesArgs B, FilterParams P) {
+  static_assert(NC == 1 || NC == 3, "one colour plane or three");
+  static_assert(NC == 1 || ALPHA, "three planes without alpha are k_modular_emit's");
+  static_assert(!(ALPHA && OUTK == JXLHIP_OUT_LINEAR_RGB_F32), "three floats have no room for alpha");
+  typedef uint32_t u2 __attribute__((ext_vector_type(2), aligned(4)));
+  typedef uint32_t u4 __attribute__((ext_vector_type(4), aligned(4)));
+  typedef int32_t i4 __attribute__((ext_vector_type(4)));
+  typedef int16_t s8 __attribute__((ext_vector_type(8)));
+  const ModularEmitArgs& A = B.e;
+  const uint32_t x0 = (uint32_t)kRun * (blockIdx.x * kRunsPerBlock + threadIdx.x);
+  if (x0 >= A.xsize) return;
+  const bool whole = x0 + kRun <= A.xsize;
+  const uint32_t gx = x0 >> A.group_shift;
+  const S* const pl0 = (const S*)A.plane[0];
+  const S* const pl1 = (const S*)A.plane[NC == 3 ? 1 : 0];
+  const S* const pl2 = (const S*)A.plane[NC == 3 ? 2 : 0];
+  const S* const pa = (const S*)B.alpha;
+  for (uint32_t y = blockIdx.y; y < A.ysize; y += gridDim.y) {
+    uint32_t prog = 0;
+    if constexpr (NC == 3) prog = A.group_rct[(size_t)(y >> A.group_shift) * A.xsg + gx];
+    const size_t o = (size_t)y * A.ns + x0;  // (A.ns is a multiple of 8: a run starts at a 16-byte boundary)
+    char* const orow = (char*)P.out + (size_t)y * P.out_stride;
+    if (!whole) {  // the scalar tail
+      for (uint32_t x = x0; x < A.xsize; x++) {
+        const size_t at = o + (x - x0);
+        float rgb[3];
+        if constexpr (NC == 3) {
+          int32_t t[3][1] = {{(int32_t)pl0[at]}, {(int32_t)pl1[at]}, {(int32_t)pl2[at]}};
+          UndoPrograms(prog, A.global_rct, t);
+          rgb[0] = (float)t[0][0] * A.factor, rgb[1] = (float)t[1][0] * A.factor, rgb[2] = (float)t[2][0] * A.factor;
+        } else {
+          rgb[0] = rgb[1] = rgb[2] = (float)(int32_t)pl0[at] * A.factor;
+        }
+        float alpha = 1.0f;
+        if constexpr (ALPHA) alpha = (float)(int32_t)pa[at] * B.alpha_factor;
+        if constexpr (OUTK == JXLHIP_OUT_LINEAR_RGB_F32) {
+          uint32_t* d = (uint32_t*)orow + 3u * (size_t)x;
+          d[0] = __float_as_uint(rgb[0]);
+          d[1] = __float_as_uint(rgb[1]);
+          d[2] = __float_as_uint(rgb[2]);
+        } else {
+          StorePackedPixel<FmtSel<FMT>>(P, P.dither, orow, (int)x, (int)y, rgb, alpha);
+        }
+      }
+      continue;
+    }
+    constexpr int kPiece = sizeof(S) == 2 ? kRun : kRun / 2;  // (as k_modular_emit: 16 bytes per plane and piece)
+    constexpr int kNc = (FMT >> 5) & 1 ? 4 : 3;
+    // (three colour planes through the general tail fill the 64 registers on their own -- k_modular_emit's is at 64 --:
+    // there the alpha samples come pair by pair, one 4- or 8-byte load behind each pair's column fence, instead of a
+    // 16-byte load per piece that would sit in registers through the whole piece)
+    constexpr bool kAlphaPerPair = ALPHA && NC == 3 && FMT < 0 && OUTK == JXLHIP_OUT_PACKED;
+    uint32_t w8[2 * kNc];
+#pragma unroll
+    for (int k = 0; k < 2 * kNc; k++) w8[k] = 0;
+#pragma unroll
+    for (int h = 0; h < kRun / kPiece; h++) {
+      int32_t s[NC][kPiece], sa[kPiece];
+      if constexpr (sizeof(S) == 2) {
+        const s8 a = __builtin_nontemporal_load((const s8*)(pl0 + o));
+#pragma unroll
+        for (int i = 0; i < kPiece; i++) s[0][i] = a[i];
+        if constexpr (NC == 3) {
+          const s8 b = __builtin_nontemporal_load((const s8*)(pl1 + o));
+          const s8 c = __builtin_nontemporal_load((const s8*)(pl2 + o));
+#pragma unroll
+          for (int i = 0; i < kPiece; i++) s[NC - 2][i] = b[i], s[NC - 1][i] = c[i];
+        }
+        if constexpr (ALPHA && !kAlphaPerPair) {
+          const s8 d = __builtin_nontemporal_load((const s8*)(pa + o));
+#pragma unroll
+          for (int i = 0; i < kPiece; i++) sa[i] = d[i];
+        }
+      } else {
+        const i4 a = __builtin_nontemporal_load((const i4*)(pl0 + o) + h);
+#pragma unroll
+        for (int i = 0; i < kPiece; i++) s[0][i] = a[i];
+        if constexpr (NC == 3) {
+          const i4 b = __builtin_nontemporal_load((const i4*)(pl1 + o) + h);
+          const i4 c = __builtin_nontemporal_load((const i4*)(pl2 + o) + h);
+#pragma unroll
+          for (int i = 0; i < kPiece; i++) s[NC - 2][i] = b[i], s[NC - 1][i] = c[i];
+        }
+        if constexpr (ALPHA && !kAlphaPerPair) {
+          const i4 d = __builtin_nontemporal_load((const i4*)(pa + o) + h);
+#pragma unroll
+          for (int i = 0; i < kPiece; i++) sa[i] = d[i];
+        }
+      }
+      if constexpr (NC == 3) UndoPrograms(prog, A.global_rct, s);
+      // pixel i of the piece: its three colour samples (a grey sample three times) and its alpha
+      auto colour = [&](int i, float* rgb) {
+#pragma unroll
+        for (int ch = 0; ch < 3; ch++) rgb[ch] = (float)s[NC == 3 ? ch : 0][i] * A.factor;
+      };
+      auto alpha_of = [&](int i) { return ALPHA ? (float)sa[i] * B.alpha_factor : 1.0f; };
+      const uint32_t xp = x0 + (uint32_t)(h * kPiece);  // the piece's first column
+      if constexpr (OUTK == JXLHIP_OUT_LINEAR_RGB_F32) {  // 12 contiguous bytes per pixel
+        uint32_t* d = (uint32_t*)orow + 3u * (size_t)xp;
+#pragma unroll
+        for (int k = 0; k < 3 * kPiece / 4; k++) {  // word 4k + j of the piece is sample (4k + j) % 3 of pixel (4k + j) / 3
+          u4 w;
+#pragma unroll
+          for (int j = 0; j < 4; j++) w[j] = __float_as_uint((float)s[NC == 3 ? (4 * k + j) % 3 : 0][(4 * k + j) / 3] * A.factor);
+          __builtin_nontemporal_store(w, (u4*)d + k);
+        }
+      } else if constexpr (FMT < 0) {
+#pragma unroll
+        for (int i = 0; i < kPiece; i += 2) {
+          float p0[3], p1[3];
+          colour(i, p0);
+          colour(i + 1, p1);
+          int xi = (int)xp + i;
+          asm volatile("" : "+v"(xi)::"memory");  // (as k_modular_emit: one pair's dither addresses at a time)
+          if constexpr (kAlphaPerPair) {
+            typedef S pair_t __attribute__((ext_vector_type(2)));
+            const pair_t d = __builtin_nontemporal_load((const pair_t*)(pa + (size_t)y * A.ns + (uint32_t)xi));
+            StorePackedPair<FmtSel<FMT>>(P, P.dither, orow, xi, (int)y, p0, p1, (float)(int32_t)d[0] * B.alpha_factor,
+                                         (float)(int32_t)d[1] * B.alpha_factor);
+          } else {
+            StorePackedPair<FmtSel<FMT>>(P, P.dither, orow, xi, (int)y, p0, p1, alpha_of(i), alpha_of(i + 1));
+          }
+        }
+      } else {  // 8-bit samples, 3 or 4 to the pixel: the run as 24 / 32 contiguous bytes
+        static_assert(((FMT >> 3) & 3) == JXLHIP_SAMPLE_U8, "the fixed formats are the 8-bit ones");
+        uint32_t* const d = (uint32_t*)(orow + (size_t)x0 * kNc);
+#pragma unroll
+        for (int j = 0; j < kPiece; j++) {  // byte kNc * i + ch of the run is sample ch of pixel i
+          const int i = h * kPiece + j;
+          float rgb[3];
+          colour(j, rgb);
+          uint32_t q[4];
+          int xi = (int)x0 + i;
+          asm volatile("" : "+v"(xi)::"memory");  // (as above)
+          PackSamples<FmtSel<FMT>>(P, P.dither, xi, (int)y, rgb, alpha_of(j), q);
+#pragma unroll
+          for (int ch = 0; ch < kNc; ch++) w8[(kNc * i + ch) / 4] |= q[ch] << (8 * ((kNc * i + ch) % 4));
+          if ((kNc * (i + 1)) / 16 > (kNc * i) / 16) {  // a 16-byte piece of the run goes out as soon as it is full
+            const int k = 4 * ((kNc * (i + 1)) / 16 - 1);
+            __builtin_nontemporal_store(u4{w8[k], w8[k + 1], w8[k + 2], w8[k + 3]}, (u4*)(d + k));
+          }
+          if (kNc == 3 && i == kRun - 1) __builtin_nontemporal_store(u2{w8[4], w8[5]}, (u2*)(d + 4));
+        }
+      }
+    }
+  }
+}
+
+// The launch table: every k_modular_planes instantiation, one X per line -- sample type, colour planes, alpha, output
+// kind, format (-1 = the general packed tail, which takes every sample type, 3 or 4 channels, dither and endianness).
+// {int16, int32} x {grey, grey + alpha, RGB + alpha}; the float kind drops alpha, so only grey comes here for it; the
+// fixed 8-bit tails for what users hit: RGB + alpha to RGBA8 from both sample types, and 8-bit grey images (int16
+// planes) to RGB8 / RGBA8.  A case without a fixed tail of its own goes through the general one.
+constexpr int kRgb8 = FormatId(JXLHIP_TF_LINEAR, JXLHIP_SAMPLE_U8, 3), kRgba8 = FormatId(JXLHIP_TF_LINEAR, JXLHIP_SAMPLE_U8, 4);
+#define JXLHIP_MODULAR_PLANES_KERNELS(X)               \
+  X(int16_t, 1, false, JXLHIP_OUT_LINEAR_RGB_F32, -1)  \
+  X(int32_t, 1, false, JXLHIP_OUT_LINEAR_RGB_F32, -1)  \
+  X(int16_t, 1, false, JXLHIP_OUT_PACKED, -1)          \
+  X(int32_t, 1, false, JXLHIP_OUT_PACKED, -1)          \
+  X(int16_t, 1, true, JXLHIP_OUT_PACKED, -1)           \
+  X(int32_t, 1, true, JXLHIP_OUT_PACKED, -1)           \
+  X(int16_t, 3, true, JXLHIP_OUT_PACKED, -1)           \
+  X(int32_t, 3, true, JXLHIP_OUT_PACKED, -1)           \
+  X(int16_t, 3, true, JXLHIP_OUT_PACKED, kRgba8)       \
+  X(int32_t, 3, true, JXLHIP_OUT_PACKED, kRgba8)       \
+  X(int16_t, 1, false, JXLHIP_OUT_PACKED, kRgb8)       \
+  X(int16_t, 1, false, JXLHIP_OUT_PACKED, kRgba8)      \
+  X(int16_t, 1, true, JXLHIP_OUT_PACKED, kRgba8)
+
+struct PlanesKernel {
+  uint32_t sample_type, num_color;
+  bool alpha;
+  int output_kind, fmt;
+  void (*kernel)(ModularPlanesArgs, FilterParams);
+};
+#define JXLHIP_X(S, NC, ALPHA, OUTK, FMT) \
+  {sizeof(S) == 2 ? JXLHIP_MODULAR_I16 : JXLHIP_MODULAR_I32, NC, ALPHA, OUTK, FMT, k_modular_planes<S, NC, ALPHA, OUTK, FMT>},
+const PlanesKernel kPlanesKernels[] = {JXLHIP_MODULAR_PLANES_KERNELS(JXLHIP_X)};
+#undef JXLHIP_X
+
 }  // namespace
 
 bool LaunchModularEmit(const ModularEmitArgs& A, const FilterParams& fp, int output_kind, hipStream_t st) {
@@ -217,6 +406,45 @@ bool LaunchModularEmit(const ModularEmitArgs& A, const FilterParams& fp, int out
   const dim3 grid((runs + kRunsPerBlock - 1) / kRunsPerBlock, std::min(A.ysize, kMaxGridRows));
   return A.sample_type == JXLHIP_MODULAR_I16 ? LaunchTyped<int16_t>(A, p, output_kind, grid, st)
                                              : LaunchTyped<int32_t>(A, p, output_kind, grid, st);
+}
+
+bool LaunchModularPlanes(const ModularPlanesArgs& B, const FilterParams& fp, int output_kind, hipStream_t st) {
+  const ModularEmitArgs& A = B.e;
+  if (B.num_color != 1 && B.num_color != 3) return false;
+  // an alpha plane reaches the output only through a fourth packed channel
+  const bool alpha = B.alpha && output_kind == JXLHIP_OUT_PACKED && fp.fmt.num_channels == 4;
+  if (B.num_color == 3 && !alpha) return LaunchModularEmit(A, fp, output_kind, st);
+  if (A.xsize == 0 || A.ysize == 0 || A.ns < ((A.xsize + 7u) & ~7u) || (A.ns & 7u) || A.group_shift < 7 || A.group_shift > 10 ||
+      A.xsg != ((A.xsize - 1) >> A.group_shift) + 1 || !fp.out || A.sample_type > JXLHIP_MODULAR_I32)
+    return false;
+  for (uint32_t c = 0; c < B.num_color; c++)
+    if (!A.plane[c] || ((uintptr_t)A.plane[c] & 15u)) return false;
+  if (alpha && ((uintptr_t)B.alpha & 15u)) return false;
+  if (B.num_color == 3 ? !A.group_rct : A.global_rct != 0) return false;  // (a grey frame has no programs at all)
+  if (output_kind == JXLHIP_OUT_LINEAR_RGB_F32 && ((((uintptr_t)fp.out | fp.out_stride) & 3u) != 0)) return false;
+  if (output_kind != JXLHIP_OUT_LINEAR_RGB_F32 && output_kind != JXLHIP_OUT_PACKED) return false;
+  FilterParams p = fp;
+  p.fmt.transfer = JXLHIP_TF_LINEAR;  // the identity hand-over: the samples are encoded already
+  // the fixed 8-bit tails want rows they can store 16 bytes at a time into; everything else is the general tail's
+  const jxlhip_output_format& o = p.fmt;
+  const bool rows4 = (((uintptr_t)p.out | p.out_stride) & 3u) == 0;
+  int fmt = -1;
+  if (output_kind == JXLHIP_OUT_PACKED && o.sample_type == JXLHIP_SAMPLE_U8 && o.swap_endianness == 0 && rows4)
+    fmt = o.num_channels == 4 ? kRgba8 : kRgb8;
+  const PlanesKernel* k = nullptr;
+  for (int pass = 0; pass < 2 && !k; pass++, fmt = -1)
+    for (const PlanesKernel& e : kPlanesKernels)
+      if (e.sample_type == A.sample_type && e.num_color == B.num_color && e.alpha == alpha && e.output_kind == output_kind && e.fmt == fmt) {
+        k = &e;
+        break;
+      }
+  if (!k) return false;
+  ModularPlanesArgs args = B;
+  if (!alpha) args.alpha = nullptr;
+  const uint32_t runs = (A.xsize + kRun - 1) / kRun;
+  const dim3 grid((runs + kRunsPerBlock - 1) / kRunsPerBlock, std::min(A.ysize, kMaxGridRows));
+  hipLaunchKernelGGL(k->kernel, grid, dim3(kRunsPerBlock), 0, st, args, p);
+  return true;
 }
 
 }  // namespace jxlhip

@@ -170,8 +170,10 @@ constexpr uint32_t kMaxDeviceRcts = 2;  // JXLHIP_MODULAR_MAX_RCTS
 struct ModularStreamOptions {
   bool rct = false;         // RCTs are read (otherwise JXLHIP_ERR_UNSUPPORTED, as ever)
   bool lz77 = false;        // as ModularDecodeImage's allow_lz77
-  bool leave_rcts = false;  // a transform list that is nothing but 1 .. kMaxDeviceRcts RCTs over the three channels of a
-                            // three-channel image is NOT undone: `program` says which they were
+  bool leave_rcts = false;  // a transform list that is nothing but 1 .. kMaxDeviceRcts RCTs over the three colour
+                            // channels (begin_c == 0) of an image of `channels` channels is NOT undone: `program` says
+                            // which they were
+  uint32_t channels = 3;    // ... three colour channels and the image's extra channels behind them
   // out
   bool transforms = false;  // the stream's header listed transforms
   bool left = false;        // ... and they were left (leave_rcts)
@@ -1192,8 +1194,8 @@ int ModularDecodeImage(BitReader* br, std::vector<ModularChannel>& image, uint32
                            : "a transform of the Modular frame (RCT, squeeze, delta palette)";
   if (rc) return rc;
   if (opt) opt->transforms = !palettes.empty() || squeeze.present;
-  // the hand-over rule of a regular Modular frame: nothing but RCTs over the three channels of a three-channel image
-  bool leave = opt && opt->leave_rcts && !squeeze.present && image.size() == 3 && !palettes.empty() &&
+  // the hand-over rule of a regular Modular frame: nothing but RCTs over the three colour channels, which lead the image
+  bool leave = opt && opt->leave_rcts && !squeeze.present && opt->channels >= 3 && image.size() == opt->channels && !palettes.empty() &&
                palettes.size() <= kMaxDeviceRcts;
   for (const ModularPalette& t : palettes) leave = leave && t.rct && t.begin_c == 0;
   // MetaPalette with begin_c == end_c (palette.cc:171-200): the palette becomes channel 0 (nb_colors x 1, shifts -1),

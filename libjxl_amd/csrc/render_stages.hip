@@ -801,15 +801,36 @@ int jxlhip::DecodeFrameToneMapped(jxlhip_ctx* c, void* out, size_t out_stride) {
 }
 
 // ---- a regular Modular frame (lossless files): the host's integer planes and RCT programs onto the device, k_modular_emit
-// (kernels_modular.hip) into the caller's output -- through the orientation staging frame when undo_orientation asks.
-int jxlhip_decode_modular_frame(jxlhip_ctx* c, const jxlhip_modular_frame* m, uint32_t output_kind, const jxlhip_output_format* out_format,
+// or -- an alpha plane, a grey frame -- k_modular_planes (kernels_modular.hip) into the caller's output, through the
+// orientation staging frame when undo_orientation asks.
+int jxlhip_decode_modular_frame(jxlhip_ctx* c, const jxlhip_modular_frame* f, uint32_t output_kind, const jxlhip_output_format* out_format,
                                 void* out, size_t out_stride, uint32_t undo_orientation) {
+  if (!c || !f) return JXLHIP_ERR_INVALID_ARGUMENT;
+  jxlhip_modular_channels m{};  // three colour planes, no alpha: k_modular_emit's launch
+  m.xsize = f->xsize;
+  m.ysize = f->ysize;
+  m.num_color = 3;
+  for (int ch = 0; ch < 3; ch++) m.planes[ch] = f->planes[ch];
+  m.stride_samples = f->stride_samples;
+  m.sample_type = f->sample_type;
+  m.bits_per_sample = f->bits_per_sample;
+  m.group_dim = f->group_dim;
+  m.group_rct = f->group_rct;
+  m.global_rct = f->global_rct;
+  return jxlhip_decode_modular_channels(c, &m, output_kind, out_format, out, out_stride, undo_orientation);
+}
+
+int jxlhip_decode_modular_channels(jxlhip_ctx* c, const jxlhip_modular_channels* m, uint32_t output_kind,
+                                   const jxlhip_output_format* out_format, void* out, size_t out_stride, uint32_t undo_orientation) {
   if (!c || !m) return JXLHIP_ERR_INVALID_ARGUMENT;
   JXLHIP_NO_MULTI(c);
   if (output_kind == JXLHIP_OUT_XYB_PLANAR) return Fail(c, JXLHIP_ERR_UNSUPPORTED, "planar XYB of a Modular frame that is not XYB");
   if (output_kind > JXLHIP_OUT_PACKED || (output_kind == JXLHIP_OUT_PACKED && !out_format) || undo_orientation > 8)
     return Fail(c, JXLHIP_ERR_INVALID_ARGUMENT, "bad output kind / orientation");
-  if (m->xsize == 0 || m->ysize == 0 || m->xsize > (1u << 19) || m->ysize > (1u << 19) || !m->planes[0] || !m->planes[1] || !m->planes[2] ||
+  if (m->num_color != 1 && m->num_color != 3) return Fail(c, JXLHIP_ERR_INVALID_ARGUMENT, "bad Modular frame: %u colour planes", m->num_color);
+  const uint32_t nc = m->num_color;
+  if (m->alpha_plane && (m->alpha_bits == 0 || m->alpha_bits > 16)) return Fail(c, JXLHIP_ERR_INVALID_ARGUMENT, "bad Modular frame: %u alpha bits", m->alpha_bits);
+  if (m->xsize == 0 || m->ysize == 0 || m->xsize > (1u << 19) || m->ysize > (1u << 19) || !m->planes[0] || (nc == 3 && (!m->planes[1] || !m->planes[2])) ||
       m->stride_samples < m->xsize || m->sample_type > JXLHIP_MODULAR_I32 || m->bits_per_sample == 0 || m->bits_per_sample > 16)
     return Fail(c, JXLHIP_ERR_INVALID_ARGUMENT, "bad Modular frame: %ux%u, %u bits, sample type %u, stride %zu", m->xsize, m->ysize,
                 m->bits_per_sample, m->sample_type, m->stride_samples);
@@ -831,6 +852,14 @@ int jxlhip_decode_modular_frame(jxlhip_ctx* c, const jxlhip_modular_frame* m, ui
   bool bad = bad_program(m->global_rct);
   for (size_t g = 0; m->group_rct && g < ng; g++) bad = bad || bad_program(m->group_rct[g]);
   if (bad) return Fail(c, JXLHIP_ERR_INVALID_ARGUMENT, "an RCT type above 41");
+  if (nc == 1) {  // one colour plane: there is nothing an RCT could run over
+    bool any = m->global_rct != 0;
+    for (size_t g = 0; m->group_rct && g < ng; g++) any = any || m->group_rct[g] != 0;
+    if (any) return Fail(c, JXLHIP_ERR_INVALID_ARGUMENT, "an RCT program on a grey (one-plane) Modular frame");
+  }
+  // the alpha plane goes up only when it reaches the output: the fourth channel of a packed format
+  const bool alpha = m->alpha_plane && output_kind == JXLHIP_OUT_PACKED && out_format->num_channels == 4;
+  const uint32_t np = nc + (alpha ? 1u : 0u);
   // the target: the caller's buffer, or -- undo_orientation -- the staging frame k_orient reads
   OutTarget t{output_kind, fmt, FilterParams{}};
   const size_t bpp = OutPixelBytes(output_kind, fmt);
@@ -864,16 +893,21 @@ int jxlhip_decode_modular_frame(jxlhip_ctx* c, const jxlhip_modular_frame* m, ui
   const size_t ssz = m->sample_type == JXLHIP_MODULAR_I16 ? 2 : 4;
   const uint32_t ns = (W + 63u) & ~63u;
   const size_t plane_bytes = ((size_t)ns * H * ssz + 255) & ~(size_t)255;
-  if ((3 * plane_bytes > c->modular_dev.n || ng > c->modular_rct_dev.n) && Capturing(c->stream))  // (a synchronise and an allocation)
+  if ((np * plane_bytes > c->modular_dev.n || ng > c->modular_rct_dev.n) && Capturing(c->stream))  // (a synchronise and an allocation)
     return Fail(c, JXLHIP_ERR_UNSUPPORTED, "a Modular frame while the stream is being captured and its planes have to grow");
-  if ((rc = c->modular_dev.Reserve(c, 3 * plane_bytes))) return rc;
+  if ((rc = c->modular_dev.Reserve(c, np * plane_bytes))) return rc;
   if ((rc = c->modular_rct_dev.Reserve(c, ng))) return rc;
-  ModularEmitArgs A{};
-  for (int ch = 0; ch < 3; ch++) {
+  ModularPlanesArgs B{};
+  ModularEmitArgs& A = B.e;
+  for (uint32_t ch = 0; ch < np; ch++) {
     uint8_t* dst = c->modular_dev + ch * plane_bytes;
-    HIPCHK(c, hipMemcpy2DAsync(dst, (size_t)ns * ssz, m->planes[ch], m->stride_samples * ssz, (size_t)W * ssz, H, hipMemcpyHostToDevice, c->stream));
-    A.plane[ch] = dst;
+    const void* src = ch < nc ? m->planes[ch] : m->alpha_plane;
+    HIPCHK(c, hipMemcpy2DAsync(dst, (size_t)ns * ssz, src, m->stride_samples * ssz, (size_t)W * ssz, H, hipMemcpyHostToDevice, c->stream));
+    if (ch < nc) A.plane[ch] = dst;
+    else B.alpha = dst;
   }
+  B.num_color = nc;
+  if (alpha) B.alpha_factor = (float)(1.0 / (double)((1u << m->alpha_bits) - 1u));
   if (m->group_rct) HIPCHK(c, hipMemcpyAsync(c->modular_rct_dev, m->group_rct, ng * sizeof(uint16_t), hipMemcpyHostToDevice, c->stream));
   else HIPCHK(c, hipMemsetAsync(c->modular_rct_dev, 0, ng * sizeof(uint16_t), c->stream));
   A.xsize = W;
@@ -885,7 +919,7 @@ int jxlhip_decode_modular_frame(jxlhip_ctx* c, const jxlhip_modular_frame* m, ui
   A.group_rct = c->modular_rct_dev;
   A.global_rct = m->global_rct;
   A.factor = (float)(1.0 / (double)((1u << m->bits_per_sample) - 1u));  // dec_modular.cc:584-586
-  if (!LaunchModularEmit(A, t.fp, (int)output_kind, c->stream)) return Fail(c, JXLHIP_ERR_INVALID_ARGUMENT, "Modular emit launch arguments");
+  if (!LaunchModularPlanes(B, t.fp, (int)output_kind, c->stream)) return Fail(c, JXLHIP_ERR_INVALID_ARGUMENT, "Modular emit launch arguments");
   HIPCHK(c, hipGetLastError());
   if (oriented) {
     if (!LaunchOrient(c->orient_dev, t.fp.out_stride, W, H, (uint32_t)bpp, undo_orientation, out, out_stride, c->stream))

@@ -59,12 +59,18 @@ inline int ParseImagePart(const uint8_t* cs, size_t n, ParsedHeaders* h, size_t*
     const jxlhip_color_encoding& ce = ih.color_encoding;
     if (ih.have_preview) return refuse("a lossless file with a preview");
     if (ih.have_animation) return refuse("a lossless animation");
-    if (ih.num_extra_channels != 0) return refuse("a lossless image with extra channels");
+    // extra channels (alpha, depth, ...): integer planes like the colour, up to four as on the VarDCT path
+    if (ih.num_extra_channels > 4) return refuse("a lossless image with more than four extra channels");
+    for (uint32_t i = 0; i < ih.num_extra_channels; i++) {
+      const jxlhip_extra_channel& e = h->extra[i];
+      if (e.dim_shift != 0) return refuse("a lossless image with a sub-sampled extra channel");
+      if (e.bit_depth.floating_point_sample || e.bit_depth.bits_per_sample == 0 || e.bit_depth.bits_per_sample > 16)
+        return refuse("a lossless image with a float extra channel or one of more than 16 bits");
+    }
     if (ih.bit_depth.floating_point_sample || ih.bit_depth.bits_per_sample == 0 || ih.bit_depth.bits_per_sample > 16)
       return refuse("a lossless image of float samples or more than 16 bits");
     if (ce.want_icc) return refuse("a lossless image with an ICC profile");
-    if (!ce.all_default && ce.color_space == JXLHIP_CS_GRAY) return refuse("a lossless grey (one-channel) image");
-    if (!ce.all_default && ce.color_space != JXLHIP_CS_RGB) return refuse("a lossless image in a colour space other than RGB");
+    if (!ce.all_default && ce.color_space != JXLHIP_CS_RGB && ce.color_space != JXLHIP_CS_GRAY) return refuse("a lossless image in a colour space other than RGB or grey");
   }
   if (ih.num_extra_channels > 4 || ih.have_preview || (ih.have_animation && !sequence)) return JXLHIP_ERR_UNSUPPORTED;
   // an ICC original: the coded profile sits between the image header and the frame; it has to be decoded to find

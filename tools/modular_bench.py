@@ -1,7 +1,7 @@
 """The two figures DESIGN.md section 3 "Modular frames" quotes.
 
-(a) k_modular_emit on a synthetic 7680x4320 frame, int16 planes -> 8-bit RGB and int32 planes -> float RGB, every group
-    with one RCT (YCoCg): run this under `rocprofv3 --kernel-trace --stats -- python tools/modular_bench.py --kernel`
+(a) k_modular_emit on a synthetic 7680x4320 frame, int16 planes -> 8-bit RGB and int32 planes -> float RGB, and its
+    sibling k_modular_planes, int16 planes + an int16 alpha plane -> 8-bit RGBA, every group with one RCT (YCoCg): run this under `rocprofv3 --kernel-trace --stats -- python tools/modular_bench.py --kernel`
     and read the kernel's time there (the call also uploads the planes, which is not the kernel's time); the script
     prints the bytes each launch must move.
 (b) the jxlhip_codestream_phase_ms split of a lossless file (`--file`: oracle.feature_stream("modular", 2100, 300) by
@@ -43,6 +43,22 @@ def kernel(reps):
             assert L.jxlhip_sync(dec.ctx) == 0
         moved = w * h * (3 * planes.itemsize + out_bytes) + ng * 2
         print("%s: %d launches of k_modular_emit, %.1f MB moved per launch (planes read + pixels written)" % (name, reps, moved / 1e6))
+    # the sibling: the same int16 planes and an alpha plane of 8-bit values -> RGBA8 (12 bytes per pixel against 9)
+    planes = rng.integers(0, 256, (4, h, w)).astype(np.int16)
+    m = abi.ModularChannels()
+    m.xsize, m.ysize, m.stride_samples, m.num_color = w, h, w, 3
+    for c in range(3):
+        m.planes[c] = planes[c].ctypes.data
+    m.alpha_plane, m.alpha_bits = planes[3].ctypes.data, 8
+    m.sample_type, m.bits_per_sample, m.group_dim, m.group_rct, m.global_rct = abi.MODULAR_I16, 8, gd, rct.ctypes.data, 0
+    fmt = abi.OutputFormat(1, 1, 4, 8, 0, 0.0, (0.2126, 0.7152, 0.0722))
+    out = torch.empty(h * w * 4, dtype=torch.uint8, device="cuda")
+    for _ in range(reps):
+        rc = L.jxlhip_decode_modular_channels(dec.ctx, C.byref(m), 2, C.byref(fmt), out.data_ptr(), w * 4, 0)
+        assert rc == 0, L.jxlhip_last_error(dec.ctx)
+        assert L.jxlhip_sync(dec.ctx) == 0
+    moved = w * h * (4 * 2 + 4) + ng * 2
+    print("int16 + alpha -> u8 RGBA: %d launches of k_modular_planes, %.1f MB moved per launch (planes read + pixels written)" % (reps, moved / 1e6))
     dec.close()
 
 
